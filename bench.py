@@ -17,6 +17,12 @@ other 2-bit kernel (`vdot4_ab`: k_dotq2, north_star's literal "no MFMA" formulat
 
 Weak scaling: every rank holds --m markers (m_global = N * m); `value` counts passes over m markers
 by all ranks per second, i.e. N * (global sweeps/s).  Prints ONE JSON line on rank 0.
+
+A plain run measures the headline only: set-up (genotypes, phenotype, Gram blocks, burn-in), --warmup untimed steps, --steps
+timed steps, the line. --full adds everything else the benchmark measures: the in-situ roofline of the mat-vec (stamped sweeps,
+isolated replay, streaming-read ceiling), the side legs (other mat-vec kernel, int8 columns, --secondary, --tertiary), the CPU
+baseline, the all-reduce timing and strong-scaling leg of a sharded run, and the full record in profiles/bench_last_full.json.
+--dump-outputs DIR writes what the timed path computed in its last step as DIR/<name>.npy (float64): see dump_outputs().
 """
 import argparse
 import ctypes as ct
@@ -63,17 +69,19 @@ def _leg(b, name):
 def compact_line(res, full_path):
     """The ONE JSON line the driver parses: the contract's top-level keys, a config of five keys, ONE roofline block and ONE
     cpu_baseline block of scalars, and one small object per side leg. Everything else (in-situ statistics, regime curves, states,
-    notes) is in the full record written to `full_path`. Kept under LINE_LIMIT bytes (asserted here and in tests/test_host_logic.py)."""
+    notes) is in the full record written to `full_path`. Kept under LINE_LIMIT bytes (asserted here and in tests/test_host_logic.py).
+    A plain run (no --full) has no roofline, regime, side legs or full record: the line then holds the contract's keys and config."""
     top = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data")
     line = {k: _r(res.get(k)) for k in top}
     cfg = res.get("config", {})
     line["config"] = {"workload": str(cfg.get("workload", ""))[:160], "model": cfg.get("model"), "n": cfg.get("n"), "m": cfg.get("m_per_gpu"),
                       "m_global": cfg.get("m_global"), "bits": cfg.get("resident_genotype_bits")}
-    rf = res.get("roofline", {})
-    line["roofline"] = {k: _r(rf.get(k)) for k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "bytes_per_launch", "avg_launch_ms",
-                                                   "launches_per_sweep", "measured_copy_GBps", "frac_of_measured_copy")}
-    line["roofline"]["isolated_frac"] = _r(rf.get("isolated", {}).get("frac"), 4)
-    line["regime"] = res.get("regime")
+    rf = res.get("roofline")
+    if rf:
+        line["roofline"] = {k: _r(rf.get(k)) for k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "bytes_per_launch", "avg_launch_ms",
+                                                       "launches_per_sweep", "measured_copy_GBps", "frac_of_measured_copy")}
+        line["roofline"]["isolated_frac"] = _r(rf.get("isolated", {}).get("frac"), 4)
+        line["regime"] = res.get("regime")
     line["achieved_GBps"] = _r(res.get("achieved_GBps"))                        # the metric's second half: resident genotype bytes x sweeps/s, all ranks
     line["achieved_frac_of_hbm_peak"] = _r(res.get("achieved_frac_of_hbm_peak"), 4)
     cb = res.get("cpu_baseline")
@@ -95,13 +103,16 @@ def compact_line(res, full_path):
             legs.append(_leg(conv, name + "_converged"))
     for b in res.get("all_move", []) or []:
         legs.append(_leg(b, "all_move"))
-    line["legs"] = legs
+    if legs:
+        line["legs"] = legs
     if res.get("n_gpus", 1) > 1:
         pr = res.get("per_rank_ms_per_step") or {}
         line["per_rank_ms_per_step"] = {"min": _r(pr.get("min")), "max": _r(pr.get("max"))}
-        ar = res.get("allreduce") or {}
-        line["allreduce"] = {"ms_per_call": _r(ar.get("ms_per_call_back_to_back")), "bytes": ar.get("bytes"), "collective": str(cfg.get("collective", ""))[:90]}
-        line["ranks_counted_by_all_reduce"] = res.get("ranks_counted_by_all_reduce")
+        ar = res.get("allreduce")
+        if isinstance(ar, dict):
+            line["allreduce"] = {"ms_per_call": _r(ar.get("ms_per_call_back_to_back")), "bytes": ar.get("bytes"), "collective": str(cfg.get("collective", ""))[:90]}
+        if "ranks_counted_by_all_reduce" in res:
+            line["ranks_counted_by_all_reduce"] = res["ranks_counted_by_all_reduce"]
         st = res.get("strong")
         if isinstance(st, dict):
             line["strong_value"] = _r(st.get("value"))
@@ -116,18 +127,39 @@ def compact_line(res, full_path):
 
 
 def write_full(res):
-    """the full record (everything round 5 printed on the line) beside the compact line: profiles/bench_last_full.json, and
-    gpurun_out/ when that exists (it is what travels back from a gpurun box)"""
+    """--full: the full record (everything round 5 printed on the line) beside the compact line, in profiles/bench_last_full.json
+    (kept out of git: every --full run rewrites it)"""
     path = os.path.join("profiles", "bench_last_full.json")
-    for d in ("profiles", "gpurun_out"):
-        try:
-            if d == "gpurun_out" and not os.path.isdir(os.path.join(ROOT, d)):
-                continue
-            with open(os.path.join(ROOT, d, "bench_last_full.json"), "w") as f:
-                json.dump(res, f, indent=1)
-        except OSError:
-            pass
+    try:
+        with open(os.path.join(ROOT, path), "w") as f:
+            json.dump(res, f, indent=1)
+    except OSError:
+        pass
     return path
+
+
+DUMP_CAP = 1 << 22   # values per dumped array (32 MB of float64); a larger one is written as a fixed, seeded sample
+
+
+def dump_outputs(d, ctx, info, n_pi, seed):
+    """--dump-outputs DIR: what a caller of the timed path (hb_run_step) receives after its last timed step, one float64 .npy each —
+    the marker effects (`alpha`) and the adjusted phenotype yadj (`residual`) the context holds, and the hyper-parameters hb_run_state
+    reports (`mu`, `vare`, `varg`, `vara`, `nnz`, `pi`). Written before anything else runs on the chain. An array longer than DUMP_CAP
+    is replaced by the values at DUMP_CAP indices drawn once from `seed` (sorted; the indices go to <name>_index.npy).
+    The inputs are the same from run to run, the f64 sums of a sweep are not bit for bit: two runs of one build agree to rounding
+    (at the defaults: the same markers in the model, alpha within 1e-15, residual within 1e-12), so compare with a tolerance."""
+    os.makedirs(d, exist_ok=True)
+    g, _, _ = ctx.get_effects()
+    r, _ = ctx.get_residual()
+    out = {"alpha": g, "residual": r, "mu": [info.mu], "vare": [info.vare], "varg": [info.varg], "vara": [info.vara], "nnz": [info.nnz],
+           "pi": [info.pi[j] for j in range(n_pi)]}
+    for name, a in out.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.size > DUMP_CAP:
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, DUMP_CAP, replace=False))
+            np.save(os.path.join(d, name + "_index.npy"), idx.astype(np.float64))
+            a = a[idx]
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def parse():
@@ -187,6 +219,11 @@ def parse():
     ap.add_argument("--cpu-m", type=int, default=8000, help="markers of the bounded CPU-baseline sample")
     ap.add_argument("--cpu-sweeps", type=int, default=4)
     ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline (roofline, side legs, CPU baseline, sharded-run extras) and write "
+                         "the full record; a plain run times the headline only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the headline's last step computed to DIR/<name>.npy (see dump_outputs())")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher check (no GPU needed): the ranks rendezvous, count each other with one all-reduce and rank 0 prints "
                          "a JSON line with n_gpus = the world size; nothing is measured")
@@ -440,8 +477,10 @@ def prior(model):
     return [0.95, 0.05], None
 
 
-def measure(H, L, ctx, y, model, K, W, args, rank, local_rank, world, m_offset, m_global, comm, torch, note, burn=0, g_init=None, warm=None):
+def measure(H, L, ctx, y, model, K, W, args, rank, local_rank, world, m_offset, m_global, comm, torch, note, burn=0, g_init=None, warm=None,
+            dump=None):
     """burn set-up sweeps, W warm-up iterations, then exactly K iterations between barriers; returns the result dict pieces.
+    dump(info): called right after the timed iterations (before the stamped sweeps of --full) with their hb_run_state.
     g_init + warm: effects and hyper-parameters (hb_warm_state) the chain starts from — a leg that CONTINUES in the regime an
     earlier leg reached (same markers in the model, same pi / varg / vare) instead of re-admitting markers from the prior
     defaults. measure.final = (effects, WarmState) after the leg's last sweep."""
@@ -528,10 +567,12 @@ def measure(H, L, ctx, y, model, K, W, args, rank, local_rank, world, m_offset, 
         elapsed = float(mine.max().item())              # the contract: MAX over ranks
     info = RunInfo()
     check(L.hb_run_state(run, ct.byref(info)))
+    if dump is not None:
+        dump(info)
     # ---- in-situ duration of the dominant kernel: the SAME run goes on for a few sweeps with every block of every mat-vec
     # launch stamped (device clock, 100 MHz); chain workgroup and update rows beside them exactly as in the timed region ----
     insitu = None
-    if args.stamped > 0 and args.precise == 2:
+    if args.full and args.stamped > 0 and args.precise == 2:
         ctx.set_profiling(8)
         check(L.hb_run_step(run, 1, ct.byref(fin)))     # (re-captures the sweep with the stamp pointers: untimed)
         sync()
@@ -708,8 +749,13 @@ def main():
         g_start = np.zeros(m)
         g_start[z["idx"]] = z["val"]
         warm_start = WarmState.make(float(z["mu"]), float(z["vare"]), float(z["varg"]), [float(x) for x in z["pi"]])
+    dump = None
+    if args.dump_outputs and rank == 0:
+        def dump(info):
+            dump_outputs(args.dump_outputs, ctx, info, len(prior(args.model)[0]), args.seed)
+            note("outputs of the last timed step written to %s" % args.dump_outputs)
     elapsed, mean_events, nnz, misses = measure(H, L, ctx, y, args.model, K, W, args, rank, local_rank, world, m_offset,
-                                        m_global, comm, torch, note, burn=args.burnin, g_init=g_start, warm=warm_start)
+                                        m_global, comm, torch, note, burn=args.burnin, g_init=g_start, warm=warm_start, dump=dump)
     replayed_main = getattr(measure, "replayed", 0)
     redo_main = getattr(measure, "redo", None)
     per_rank_main = getattr(measure, "per_rank_ms", None)
@@ -718,14 +764,16 @@ def main():
     curve_main = list(getattr(measure, "curve", []))
     curve_main.append({"sweeps": "timed region", "moves_per_sweep": round(mean_events, 1), "sweeps_per_s": round(world * K / elapsed, 2)})
     insitu_main = measure.insitu
-    # the dominant kernel on its own (kept beside the in-situ figure as roofline.isolated): the sweep's mat-vec launches without
-    # update rows and without the chain, back to back, HIP events on their stream
-    ctx.time_matvec(reps=1)                                   # (untimed: clocks and TLBs as in the steady state of a run)
-    iso_ms, launches, cols = ctx.time_matvec(reps=5)
-    kernel_main = (("k_dotq2m" if kind_main == 2 else "k_dotq2r" if kind_main == 1 else "k_dotq2") if bits == 2 else "k_dotq") if args.precise == 2 else "k_dot"
-    copy_main = copy_ceiling(ctx, note)
-    roof = roofline_block(args, n, cols, launches, insitu_main, iso_ms, pmc_traffic(n, cols, kernel_main), bits, kind_main, copy_main)
-    note("mat-vec timing pass done")
+    roof = None
+    if args.full:
+        # the dominant kernel on its own (kept beside the in-situ figure as roofline.isolated): the sweep's mat-vec launches without
+        # update rows and without the chain, back to back, HIP events on their stream
+        ctx.time_matvec(reps=1)                                   # (untimed: clocks and TLBs as in the steady state of a run)
+        iso_ms, launches, cols = ctx.time_matvec(reps=5)
+        kernel_main = (("k_dotq2m" if kind_main == 2 else "k_dotq2r" if kind_main == 1 else "k_dotq2") if bits == 2 else "k_dotq") if args.precise == 2 else "k_dot"
+        copy_main = copy_ceiling(ctx, note)
+        roof = roofline_block(args, n, cols, launches, insitu_main, iso_ms, pmc_traffic(n, cols, kernel_main), bits, kind_main, copy_main)
+        note("mat-vec timing pass done")
 
     # one unit = one pass over m_ref markers (the metric's m = 500k); all ranks together pass over m_global markers per step
     m_ref = float(os.environ.get("HB_BENCH_M", "500000")) if args.scaling == "weak" else 500000.0
@@ -748,7 +796,7 @@ def main():
                    "mean_changed_markers_per_sweep": mean_events, "row_cache_misses_per_sweep": misses, "NumNZSnp_last": nnz,
                    "chain_rounds_rolled_back_per_sweep": redo_main,
                    "sweeps_replayed_after_a_device_time_out": replayed_main,
-                   "matvec_kernel": roof["kernel"],
+                   "matvec_kernel": roof["kernel"] if roof else None,
                    "resident_genotype_bits": bits, "setup_seconds": {"generate": gen_s, "gram": gram_s, "pack_2bit": pack_s}},
         # PHYSICAL bytes: the genotypes the resident layout holds are read once per sweep by the mat-vec (the Gram rows, digit planes and
         # residual updates of a stationary BayesCpi sweep add < 2 %); the n x m-priced figure of earlier rounds is `genotype_rate`
@@ -756,16 +804,16 @@ def main():
         "achieved_frac_of_hbm_peak": (K / elapsed) * n * m_global * bits / 8 / 1e9 / (HBM_PEAK_GBPS * world),
         "genotype_rate": {"value": (K / elapsed) * n * m_global / 1e9, "unit": "G genotypes/s",
                           "what": "n x m genotypes per sweep (SURVEY 8d's unit; = GB/s at one byte per genotype)"},
-        "roofline": roof,
         "regime_curve": curve_main,   # sweeps/s is set by the serial chain, i.e. by how many markers change per sweep
         "state_after": state_main,
     }
-    res.update(regime_tag(elapsed / K * 1e3, insitu_main))
-    roof["regime"] = res["regime"]
-    roof["traffic_source"] = ("separate rocprofv3 --pmc FETCH_SIZE pass of the same launch shape, read from the tracked profiles/r05_pmc_traffic.json "
-                              "(counters cannot be collected inside this process)") if roof.get("traffic") is not None else "none (no counter pass on file for this launch shape)"
-
-    copy_by_bits = {bits: copy_main}
+    if args.full:
+        res["roofline"] = roof
+        res.update(regime_tag(elapsed / K * 1e3, insitu_main))
+        roof["regime"] = res["regime"]
+        roof["traffic_source"] = ("separate rocprofv3 --pmc FETCH_SIZE pass of the same launch shape, read from the tracked profiles/r05_pmc_traffic.json "
+                                  "(counters cannot be collected inside this process)") if roof.get("traffic") is not None else "none (no counter pass on file for this launch shape)"
+        copy_by_bits = {bits: copy_main}
 
     def leg_block(model, el, Kx, Wx, ev, nnzx, missx, ins, iso, launches_x, cols_x, bits_x, kind, geo_x, burn_x, curve=None):
         if bits_x not in copy_by_bits:
@@ -786,7 +834,7 @@ def main():
             b["regime_curve"] = curve
         return b
 
-    single = world == 1
+    single = world == 1 and args.full      # (the side legs below are --full only)
     # ---- A/B: the same sweep with the OTHER 2-bit mat-vec kernel (headline on the matrix-core k_dotq2m: the v_dot4 k_dotq2, north_star's literal
     # "no MFMA" formulation and the default until round 4; headline on k_dotq2: k_dotq2m). Same exact integers, same chain. ----
     ab_key, ab_kind = ("vdot4_ab", 0) if kind_main == 2 else ("mfma_ab", 2)
@@ -828,7 +876,7 @@ def main():
     for tm in [x for x in args.tertiary.split(",") if x]:
         sides.append((tm, "all_move", 20, max(10, K // 8), 5))
     for side, key, burn_s, K2, W2 in sides:
-        if not side or side == args.model or world != 1 or (key == "all_move" and side == args.secondary):
+        if not side or side == args.model or not single or (key == "all_move" and side == args.secondary):
             continue
         try:  # a side model is a reported side number: its failure must not take the headline line with it
             # the other model families of BASELINE.json's configs on the same genotypes, shorter runs
@@ -909,8 +957,9 @@ def main():
             else:
                 res[key] = {"model": side, "error": repr(e)}
     if world > 1:
-        # what the scaling curve is made of: every rank's own time per step, and the exchange a sweep ends with on its own
+        # what the scaling curve is made of: every rank's own time per step, and (--full) the exchange a sweep ends with on its own
         res["per_rank_ms_per_step"] = {"min": min(per_rank_main), "max": max(per_rank_main), "all": per_rank_main} if per_rank_main else None
+    if world > 1 and args.full:
         try:
             xc = int(L.hb_exchange_count(n))
             buf = torch.zeros(xc, dtype=torch.float64, device=comm.device)
@@ -928,20 +977,20 @@ def main():
                                         "inside a sweep the library enqueues the same collective on the sweep stream" % args.backend}
         except Exception as e:  # noqa: BLE001
             res["allreduce"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         try:
             res["cpu_baseline"] = cpu_baseline(ctx, y, args, Pi, fold, g_main)
         except Exception as e:  # the baseline is a reported side number, never the measured path
             res["cpu_baseline"] = {"error": repr(e)}
     ctx.close()
-    if world > 1:
+    if world > 1 and args.full:
         try:
             ones = torch.ones(1, dtype=torch.float64, device=comm.device)
             comm.dist.all_reduce(ones)
             res["ranks_counted_by_all_reduce"] = int(ones.item())
         except Exception as e:  # noqa: BLE001
             res["ranks_counted_by_all_reduce"] = repr(e)
-    if world > 1 and args.scaling == "weak" and not args.no_strong:
+    if world > 1 and args.full and args.scaling == "weak" and not args.no_strong:
         # BASELINE.json configs[3] in the SAME invocation (the driver passes no extra flags): --m-global markers (2 000 000) sharded
         # over the ranks, the headline model, 2-bit resident — `strong_value` in passes over 500 000 markers per second
         try:
@@ -973,7 +1022,7 @@ def main():
         except Exception as e:  # noqa: BLE001  (a side leg: its failure must not take the line with it)
             res["strong"] = {"error": repr(e)[:200]}
     if rank == 0:
-        print(compact_line(res, write_full(res)), flush=True)
+        print(compact_line(res, write_full(res) if args.full else None), flush=True)
     if comm is not None:
         comm.dist.destroy_process_group()
 

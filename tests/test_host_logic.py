@@ -237,6 +237,65 @@ def test_bench_line_stays_small_enough_for_the_driver_to_parse():
     assert out8["strong_value"] == 900.0 and out8["ranks_counted_by_all_reduce"] == 8 and out8["per_rank_ms_per_step"]["max"] == 2.3 and out8["allreduce"]["ms_per_call"] == 0.05
 
 
+def test_plain_bench_line_holds_the_contract_without_the_full_blocks():
+    """A plain `bench.py` run (no --full) measures the headline only: its line still carries the contract's keys, and no roofline, regime,
+    side legs, CPU baseline or full-record path (those need --full)."""
+    import json
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    full = json.load(open(os.path.join(root, "profiles", "r05_bench_driver_args.json")))
+    res = {k: full[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+                                "dtype", "data", "config", "achieved_GBps", "achieved_frac_of_hbm_peak")}
+    out = json.loads(bench.compact_line(res, None))
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup"):
+        assert out[k] == res[k], k
+    assert out["value"] == pytest.approx(res["value"], rel=1e-5) and out["ms_per_step"] == pytest.approx(res["ms_per_step"], rel=1e-5)
+    assert not {"roofline", "regime", "legs", "cpu_baseline"} & set(out) and out["full"] is None
+    import sys
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py", "--steps", "7", "--warmup", "3"]
+        a = bench.parse()
+        assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 3, False, "")
+        sys.argv = ["bench.py", "--full", "--dump-outputs", "d"]
+        a = bench.parse()
+        assert a.full and a.dump_outputs == "d"
+    finally:
+        sys.argv = argv
+
+
+def test_bench_dump_outputs_writes_float64_arrays(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the effects, the residual and the hyper-parameters of the last timed step, float64 .npy each; an array
+    above the cap becomes the same seeded sample every time."""
+    import bench
+    from hibayes_amd._lib import RunInfo
+
+    class Ctx:
+        def get_effects(self):
+            return np.arange(10.0), np.zeros(10, dtype=np.uint8), np.zeros(10)
+
+        def get_residual(self):
+            return np.linspace(-1.0, 1.0, 4), np.zeros(4)
+
+    info = RunInfo()
+    info.mu, info.vare, info.varg, info.vara, info.nnz = 1.5, 2.0, 0.25, 0.0, 3.0
+    info.pi[0], info.pi[1] = 0.9, 0.1
+    bench.dump_outputs(str(tmp_path / "a"), Ctx(), info, 2, 5)
+    got = {f[:-4]: np.load(str(tmp_path / "a" / f)) for f in os.listdir(str(tmp_path / "a"))}
+    assert set(got) == {"alpha", "residual", "mu", "vare", "varg", "vara", "nnz", "pi"}
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert np.array_equal(got["alpha"], np.arange(10.0)) and got["residual"].shape == (4,)
+    assert got["mu"].tolist() == [1.5] and got["nnz"].tolist() == [3.0] and got["pi"].tolist() == [0.9, 0.1]
+    monkeypatch.setattr(bench, "DUMP_CAP", 6)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), Ctx(), info, 2, 5)
+    idx = np.load(str(tmp_path / "b" / "alpha_index.npy"))
+    assert idx.size == 6 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(np.load(str(tmp_path / "b" / "alpha.npy")), idx)          # alpha[i] == i here
+    assert np.array_equal(np.load(str(tmp_path / "c" / "alpha.npy")), np.load(str(tmp_path / "b" / "alpha.npy")))
+    assert not os.path.exists(str(tmp_path / "b" / "residual_index.npy"))
+
+
 def test_hot_kernels_are_built_without_register_spills():
     """The compiler's per-kernel resource report of the last build (hibayes_amd/csrc/hb_kernels.res.txt, written by the Makefile).
     The headline chain kernel sits at the 256-register limit of a 512-thread workgroup: in round 6 five spilled registers — caused by nothing

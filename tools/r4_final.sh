@@ -3,7 +3,7 @@
 O=gpurun_out
 ( time timeout 1500 python -m pytest tests -m gpu -x -q ) > $O/r04_gpu_tests_final.txt 2>&1
 grep -n "passed\|failed" $O/r04_gpu_tests_final.txt | tail -2
-timeout 900 python bench.py > $O/r04_bench_final.json 2> $O/r04_bench_final.err
+timeout 900 python bench.py --full > $O/r04_bench_final.json 2> $O/r04_bench_final.err
 python - <<'PY'
 import json
 d=json.loads(open('gpurun_out/r04_bench_final.json').read().strip().splitlines()[-1])

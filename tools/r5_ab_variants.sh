@@ -4,7 +4,7 @@ cd /root/repo
 O=gpurun_out
 python -m pytest tests/test_gpu_depth.py tests/test_gpu_parity.py -m gpu -x -q 2>&1 | grep -E "passed|failed|error" | tail -3
 for rep in 1 2; do for v in "$@"; do lib=build/variants/$v.so; [ $v = base ] && lib=hibayes_amd/libhibayes_gpu.so
-  HIBAYES_GPU_LIB=$PWD/$lib python bench.py --steps 200 --warmup 100 --no-cpu --no-ab --secondary '' --tertiary '' > $O/r5_v_$v.json 2> $O/r5_v_$v.err
+  HIBAYES_GPU_LIB=$PWD/$lib python bench.py --full --steps 200 --warmup 100 --no-cpu --no-ab --secondary '' --tertiary '' > $O/r5_v_$v.json 2> $O/r5_v_$v.err
   python - <<PY
 import json
 d=json.loads(open('$O/r5_v_$v.json').read().strip().splitlines()[-1])

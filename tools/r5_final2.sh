@@ -4,8 +4,8 @@ cd /root/repo
 O=gpurun_out
 ( time timeout 1500 python -m pytest tests -m gpu -x -q --durations=12 ) > $O/r05_gpu_tests.txt 2>&1
 grep -n "passed\|failed" $O/r05_gpu_tests.txt | tail -2
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/r05_bench_driver_args.json 2> $O/r05_bench_driver_args.err
-timeout 900 python bench.py > $O/r05_bench_default.json 2> $O/r05_bench_default.err
+timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/r05_bench_driver_args.json 2> $O/r05_bench_driver_args.err
+timeout 900 python bench.py --full > $O/r05_bench_default.json 2> $O/r05_bench_default.err
 python - <<'PY'
 import json
 for f in ('r05_bench_driver_args', 'r05_bench_default'):
@@ -19,7 +19,7 @@ GT_BITS=2 python tools/group_timeline.py BayesCpi 300 > $O/r05_group_phases_fina
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 rm -rf $O/trace_f
-rocprofv3 --kernel-trace --stats -d $O/trace_f -o bench -- python $R/bench.py --steps 100 --warmup 30 --no-ab --no-cpu --secondary "" --tertiary "" > $O/r05_bench_under_rocprof_2bit_mfma.json 2> $O/trace_f.err
+rocprofv3 --kernel-trace --stats -d $O/trace_f -o bench -- python $R/bench.py --full --steps 100 --warmup 30 --no-ab --no-cpu --secondary "" --tertiary "" > $O/r05_bench_under_rocprof_2bit_mfma.json 2> $O/trace_f.err
 db=$(find $O/trace_f -name "*.db" | head -1)
 python $R/tools/rocprof_window.py $db --after 11 --sweeps 100 > $O/r05_kernel_trace_timed_window_2bit_mfma.txt 2>&1
 head -6 $O/r05_kernel_trace_timed_window_2bit_mfma.txt | cut -c1-170

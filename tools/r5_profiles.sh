@@ -7,7 +7,7 @@ leg() { # name, env..., -- bench args
   name=$1; shift
   envs=(); while [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift
   rm -rf $O/trace_$name
-  env "${envs[@]}" rocprofv3 --kernel-trace --stats -d $O/trace_$name -o bench -- python $R/bench.py --steps 100 --warmup 30 --no-ab --no-cpu --burnin-converged 0 "$@" > $O/r05_bench_under_rocprof_$name.json 2> $O/trace_$name.err
+  env "${envs[@]}" rocprofv3 --kernel-trace --stats -d $O/trace_$name -o bench -- python $R/bench.py --full --steps 100 --warmup 30 --no-ab --no-cpu --burnin-converged 0 "$@" > $O/r05_bench_under_rocprof_$name.json 2> $O/trace_$name.err
   db=$(find $O/trace_$name -name "*.db" | head -1)
   python $R/tools/rocprof_window.py $db --after 11 --sweeps 100 > $O/r05_kernel_trace_timed_window_$name.txt 2>&1
   head -8 $O/r05_kernel_trace_timed_window_$name.txt | cut -c1-170
@@ -32,4 +32,4 @@ run_pmc fetch_2bit_vdot4_d7 FETCH_SIZE HB_MV_BITS=2 HB_TIME_MATVEC_D=7 HB_DOTQ2_
 run_pmc fetch_int8_d7 FETCH_SIZE HB_MV_BITS=8 HB_TIME_MATVEC_D=7
 run_pmc sq_k_dotq2m "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT" HB_MV_BITS=2 HB_TIME_MATVEC_D=7
 # two ranks sharing the one GPU of this box over gloo (what can be checked of `bench.py --gpus N` without a node): the line's per-rank and all-reduce fields
-cd $R && HB_BENCH_M=100000 timeout 600 python bench.py --gpus 2 --backend gloo --collective torch --steps 10 --warmup 5 --burnin 30 --no-cpu > $O/r05_bench_gpus2_gloo_one_gpu_box.json 2> $O/r05_bench_gpus2_gloo_one_gpu_box.err; tail -c 1500 $O/r05_bench_gpus2_gloo_one_gpu_box.json | head -c 1500; tail -3 $O/r05_bench_gpus2_gloo_one_gpu_box.err
+cd $R && HB_BENCH_M=100000 timeout 600 python bench.py --full --gpus 2 --backend gloo --collective torch --steps 10 --warmup 5 --burnin 30 --no-cpu > $O/r05_bench_gpus2_gloo_one_gpu_box.json 2> $O/r05_bench_gpus2_gloo_one_gpu_box.err; tail -c 1500 $O/r05_bench_gpus2_gloo_one_gpu_box.json | head -c 1500; tail -3 $O/r05_bench_gpus2_gloo_one_gpu_box.err

@@ -7,7 +7,7 @@ out=gpurun_out/r06_bayesr_conv_$1.txt
 IFS='|' read -ra ENVS <<< "$2"
 for geo in $3; do
   for e in "${ENVS[@]}"; do
-    env $e HB_BENCH_GEO_BayesR=$geo python bench.py --steps 40 --warmup 5 --burnin 100 --burnin-secondary 20 --tertiary '' --no-ab --no-cpu > /tmp/b.json 2> /tmp/b.err
+    env $e HB_BENCH_GEO_BayesR=$geo python bench.py --full --steps 40 --warmup 5 --burnin 100 --burnin-secondary 20 --tertiary '' --no-ab --no-cpu > /tmp/b.json 2> /tmp/b.err
     python - "$geo" "$e" >> $out <<'P'
 import json, sys
 full = json.load(open("profiles/bench_last_full.json"))

@@ -6,7 +6,7 @@ out=gpurun_out/r06_bayesr_geo${TAG}.txt
 : > $out
 for geo in $1; do
   for ck in ${CHAINS:-1}; do
-    HB_CHAIN=$ck HB_BENCH_GEO_BayesR=$geo python bench.py --steps 20 --warmup 5 --tertiary '' --no-ab --no-cpu --burnin-converged ${CONV:-0} > /tmp/b.json 2> /tmp/b.err
+    HB_CHAIN=$ck HB_BENCH_GEO_BayesR=$geo python bench.py --full --steps 20 --warmup 5 --tertiary '' --no-ab --no-cpu --burnin-converged ${CONV:-0} > /tmp/b.json 2> /tmp/b.err
     python - "$geo" "$ck" >> $out <<'P'
 import json, sys
 full = json.load(open("profiles/bench_last_full.json"))

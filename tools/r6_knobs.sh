@@ -1,6 +1,6 @@
 #!/bin/bash
 # round 6, closing check: the headline (BayesCpi, 2-bit, certified group chain) under the knobs that were tuned in earlier rounds — are the defaults still the best?
-B='python bench.py --steps 60 --warmup 10 --no-cpu --secondary "" --tertiary "" --no-ab --stamped 0'
+B='python bench.py --full --steps 60 --warmup 10 --no-cpu --secondary "" --tertiary "" --no-ab --stamped 0'
 run() { label="$1"; shift; v=$(env "$@" timeout 120 bash -c "$B" 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('%.1f sweeps/s, launch %.2f us' % (d['value'], d['roofline']['avg_launch_ms']*1e3))"); echo "$label: $v"; }
 run "defaults" HB_X=0
 run "defaults again" HB_X=0

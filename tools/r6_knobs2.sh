@@ -1,6 +1,6 @@
 #!/bin/bash
 # round 6, closing check at the new default geometry (2, 7): structural switches of the headline's chain
-B='python bench.py --steps 60 --warmup 10 --no-cpu --secondary "" --tertiary "" --no-ab --stamped 0'
+B='python bench.py --full --steps 60 --warmup 10 --no-cpu --secondary "" --tertiary "" --no-ab --stamped 0'
 run() { label="$1"; shift; v=$(env "$@" timeout 120 bash -c "$B" 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('%.1f sweeps/s, launch %.2f us' % (d['value'], d['roofline']['avg_launch_ms']*1e3))"); echo "$label: $v"; }
 run "defaults" HB_X=0
 run "HB_FWD=0 (the chain folds everything itself)" HB_FWD=0

@@ -1,8 +1,8 @@
 #!/bin/bash
 # round 6, closing check: BayesR converged (from the stored state, group chain at (2, 2)) and 300 sweeps after a cold start, under the tuning knobs
 R=${GRAFT_REPO_ROOT:-.}
-BC="python bench.py --steps 60 --warmup 10 --no-cpu --secondary \"\" --tertiary \"\" --no-ab --stamped 0 --model BayesR --init-state $R/profiles/state/bayesr_config3.npz --burnin 40"
-BK="python bench.py --steps 40 --warmup 5 --no-cpu --secondary \"\" --tertiary \"\" --no-ab --stamped 0 --model BayesR --burnin 300"
+BC="python bench.py --full --steps 60 --warmup 10 --no-cpu --secondary \"\" --tertiary \"\" --no-ab --stamped 0 --model BayesR --init-state $R/profiles/state/bayesr_config3.npz --burnin 40"
+BK="python bench.py --full --steps 40 --warmup 5 --no-cpu --secondary \"\" --tertiary \"\" --no-ab --stamped 0 --model BayesR --burnin 300"
 run() { what="$1"; shift; label="$1"; shift; if [ "$what" = conv ]; then B="$BC"; else B="$BK"; fi
   v=$(env "$@" timeout 150 bash -c "$B" 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('%.1f sweeps/s (%s)' % (d['value'], d['config']['workload'][-28:]))"); echo "$what | $label: $v"; }
 run conv "defaults" HB_X=0
