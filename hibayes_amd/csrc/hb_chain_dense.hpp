@@ -414,57 +414,3 @@ __global__ __launch_bounds__(256) void k_fold_dense(chain_view v, persist_view p
         if (t == 0) atomicAdd(pv.flags + 14, 1u);
     }
 }
-
-// ---------------------------------------------------------------------------------------------
-// k_warm_dense: the chain workgroup's own reads — the diagonal blocks and strips of the NEXT panels' Gram blocks, 576 KB per panel —
-// pulled into ITS L2 ahead of time. One compute unit gets ~18 bytes per clock out of HBM however many loads it keeps in flight,
-// but ~64 out of its XCD's L2, and with the serial pass at 28 cycles per marker the chain would otherwise wait for
-// its strips. 8 x per_xcd workgroups are launched; those that did not land on the chain's XCD (it publishes HB_FLAG_XCC) leave.
-// The order is static, so this is exact prefetching: rows k of panel q from the diagonal block's first column to the row's end,
-// one workgroup per row residue, paced `ahead` panels in front of chain_done. A hint with no dependency: results are discarded.
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_warm_dense(chain_view v, persist_view pv, int per_xcd, int ahead, int *__restrict__ sink)
-{
-    __shared__ int s_rank;
-    constexpr int P = HBD_P;
-    const int t = threadIdx.x;
-    if (t == 0) {
-        unsigned my;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(my));
-        my &= 15u;
-        unsigned want = 0;
-        const unsigned long long t0 = wall_clock64();
-        while ((want = ld_flag(pv.flags + HB_FLAG_XCC)) == 0u) {
-            if (ld_flag(pv.flags + HB_FLAG_ABORT) || wall_clock64() - t0 > 100000000ull) break; // (1 s: the chain never started)
-            __builtin_amdgcn_s_sleep(16);
-        }
-        s_rank = (want == my + 1u) ? (int)(blockIdx.x >> 3) % per_xcd : -1;
-    }
-    __syncthreads();
-    const int rank = s_rank;
-    if (rank < 0) return;
-    const int np = pv.npanels;
-    const size_t PP = (size_t)P * P, pblk = (size_t)(pv.Lg + 1) * PP;
-    int acc = 0;
-    for (int q = pv.p0 + 1; q < np; q++) {
-        unsigned done;
-        const unsigned long long t0 = wall_clock64();
-        for (;;) {
-            done = ld_flag(pv.flags + HB_FLAG_CHAIN_DONE);
-            if ((int)done + ahead >= q || ld_flag(pv.flags + HB_FLAG_ABORT) || wall_clock64() - t0 > HB_TIMEOUT_TICKS) break;
-            __builtin_amdgcn_s_sleep(8);
-        }
-        if ((int)done >= np || ld_flag(pv.flags + HB_FLAG_ABORT) || (int)done + ahead < q) break;
-        if (q <= (int)done) continue; // the chain is already past this panel
-        const int32_t *gp = v.gram + (size_t)q * pblk;
-        // two rows per pass (128 lanes x 16 bytes each); row k is read from column 64 (k / 64) on
-        for (int k = 2 * rank + (t >> 7); k < P; k += 2 * per_xcd) {
-            const int c = 4 * (t & 127);
-            if (c >= (k & ~63)) {
-                const int4 x = *reinterpret_cast<const int4 *>(gp + (size_t)k * P + c);
-                acc += x.x ^ x.y ^ x.z ^ x.w;
-            }
-        }
-    }
-    if (acc == 0x7fffffff) *sink = acc; // (keeps the loads alive)
-}

@@ -47,10 +47,6 @@
 // Template shape: HBG_DM = panels per group the register arrays are sized for (>= D), HBG_FW = panels ahead a move is folded into
 // (>= Lv * D), HBG_CH = moves whose rows are requested together — HBG_CH * (HBG_DM + HBG_FW) loads per lane and trip, ~60: a narrow
 // geometry (few rows per move) takes many moves per trip, the wide one of the stationary point-mass sweep three.
-// G16 (round 5): the rows of a move come from the compact band (hb_ctx.gram16: int16 residuals of G - ga (x) gB, half the bytes), one short per
-// lane and row, and every entry is rebuilt exactly, G[k][j] = g16[k][j] + ga[k] * gB[j] (one integer multiply-add), before it is used: the fold's
-// arithmetic is the int32 band's bit for bit. (tools/rowfetch2_bench.hip: 80 cycles per row this way against 111 for int32 rows; whole rows per
-// wave-load staged through LDS, by dwordx4 loads or by LDS-DMA: 127-131 — tried in the kernel too, profiles/r05_group_phases_g16b_*.txt.)
 // CERT (round 5): the violation check of a round WITHOUT the Gram rows of the group's own panels. With G[k][j] = ga[k] gB[j] + c[k][j] and
 // |c[k][j]| <= gcmax[k] (hb_ctx gcert arrays: exact integers from the band), a passed-over marker j ends the round at
 //     rhs_j - gB[j] * A_j - eps_j,   A_j = sum of ga[k] d_k over the moves before j,   |eps_j| <= E = sum_k gcmax[k] |d_k|,
@@ -75,7 +71,7 @@
 #ifndef HBG_CERT_MARGIN
 #define HBG_CERT_MARGIN 1.0
 #endif
-template <int K1, int HBG_DM, int HBG_FW, int HBG_CH, bool G16 = false, bool CERT = false, bool FRESH = false>
+template <int K1, int HBG_DM, int HBG_FW, int HBG_CH, bool CERT = false>
 __device__ __forceinline__ void chain_group_body(const hb_sweep_in *__restrict__ pin, const chain_view &v, const persist_view &pv, char *smem)
 {
     const int P = v.P, S = P >> 6;
@@ -101,9 +97,8 @@ __device__ __forceinline__ void chain_group_body(const hb_sweep_in *__restrict__
     int *res_c = cs_pos + 64;                                   // ... new classes
     int *ev_pos = res_c + 64;                                   // the round's moves: position
     int *cg = ev_pos + 64;                                      // [64][64] Gram entries among the round's candidates (k < c)
-    int *cs_ga = cg + 64 * 64;                                  // [64] G16: the candidates' ga[]
-    int *ev_ga = cs_ga + 64;                                    // [64] G16: ga[] of the round's movers
-    int *cs_cm = ev_ga + 64;                                    // [64] CERT: the candidates' gcmax[]
+    int *cs_ga = cg + 64 * 64;                                  // [64] CERT: the candidates' ga[]
+    int *cs_cm = cs_ga + 64;                                    // [64] CERT: the candidates' gcmax[]
     int *wcnt = cs_cm + 64;                                     // [HBG_DM][8] candidates per (panel of the group, wave)
     int *misc = wcnt + 64;                                      // [0] moves of the round, [1] position the round ends at, [2] abort, [8..15] violations per wave, [16..23] moves published per panel, [24..31] CERT: per wave, a marker not proven to stay
     for (int l = 0; l < R; l++) corr[(size_t)l * P + t] = 0.0;
@@ -165,20 +160,12 @@ __device__ __forceinline__ void chain_group_body(const hb_sweep_in *__restrict__
         // ---- (1) the group's dots, filter words and owed corrections ----
         double r0[HBG_DM];
         float fl[HBG_DM];
-        int gBi[(G16 || CERT) ? HBG_DM : 1], gBf[G16 ? HBG_FW : 1]; // gB of this thread's markers in the group (G16, CERT) and in the panels ahead (G16)
-        float sqf[CERT ? HBG_DM : 1];                                // CERT: lower bound of sqrt(threshold) of this thread's markers
-        (void)gBi; (void)gBf; (void)sqf;
-        if constexpr (G16 && !CERT) {
-#pragma unroll
-            for (int i = 0; i < HBG_DM; i++) gBi[i] = v.gB[(size_t)(gp0 + min(i, Dg - 1)) * P + t];
-        }
+        int gBi[CERT ? HBG_DM : 1];   // CERT: gB of this thread's markers in the group
+        float sqf[CERT ? HBG_DM : 1]; // CERT: lower bound of sqrt(threshold) of this thread's markers
+        (void)gBi; (void)sqf;
         double thc[HBG_DM];  // candidate thresholds of the group's rounds (candf * filter word, as a double; hot: -1, filtered out: NaN)
         bool staged = false; // (uniform) the next group's records have been requested
         (void)staged;
-        if constexpr (G16) {
-#pragma unroll
-            for (int x = 0; x < HBG_FW; x++) gBf[x] = v.gB[(size_t)min(gp0 + D + x, np - 1) * P + t];
-        }
         {
             double dj[HBG_DM], fc[HBG_DM];
             // (k_fwd writes the corrections the moves of the group before the last owe this one: sentinel-prefilled like the dots)
@@ -229,9 +216,8 @@ __device__ __forceinline__ void chain_group_body(const hb_sweep_in *__restrict__
                 for (unsigned looks = 0;; looks++) {
                     bad = false;
                     if (HB_CHAINDBG && t == 0) st_flag(pv.flags + 45, (unsigned)wall_clock64());
-                    if (FRESH || hb_fresh_look(looks)) { // (uniform; what is still missing is read at the memory side, ld_fresh in hb_handoff.hpp: once in
-                        // HB_FRESH_EVERY looks — or, beside the persistent mat-vec (FRESH: an instantiation of its own — as a run-time switch this branch cost the headline kernel, which sits at 256 registers, six spilled ones and 446 -> 421 sweeps/s), at every look: there no kernel boundary ever drops a line this XCD's L2
-                        // took before its words were published, and a word that HAS arrived is kept — it never changes again)
+                    if (hb_fresh_look(looks)) { // (uniform; what is still missing is read at the memory side, ld_fresh in hb_handoff.hpp: once in
+                        // HB_FRESH_EVERY looks; a word that HAS arrived is kept — it never changes again)
 #pragma unroll
                         for (int i = 0; i < HBG_DM; i++) {
                             const size_t j = (size_t)(gp0 + min(i, Dg - 1)) * P + t;
@@ -410,7 +396,7 @@ __device__ __forceinline__ void chain_group_body(const hb_sweep_in *__restrict__
                         szc[c] = v.sdz[(size_t)c * v.m_pad + j];
                     }
                     int gac = 0, cmc = 0;
-                    if constexpr (G16 || CERT) gac = v.ga[j];
+                    if constexpr (CERT) gac = v.ga[j];
                     if constexpr (CERT) cmc = v.gcmax[j];
                     cs_d[rank] = fma(xx, gold, r0i);
                     cs_d[64 + rank] = gold;
@@ -420,7 +406,7 @@ __device__ __forceinline__ void chain_group_body(const hb_sweep_in *__restrict__
                         cs_d[(2 + K1 + c) * 64 + rank] = ivc[c];
                         cs_d[(2 + 2 * K1 + c) * 64 + rank] = szc[c];
                     }
-                    if constexpr (G16 || CERT) cs_ga[rank] = gac;
+                    if constexpr (CERT) cs_ga[rank] = gac;
                     if constexpr (CERT) cs_cm[rank] = cmc;
                 }
             }
@@ -508,7 +494,6 @@ __device__ __forceinline__ void chain_group_body(const hb_sweep_in *__restrict__
                     const int pos = __popcll(moved & lt);
                     ev_pos[pos] = cp;
                     ev_del[pos] = dmine;
-                    if constexpr (G16) ev_ga[pos] = cs_ga[lane];
                 }
                 res_c[lane] = cls;
                 res_g[lane] = gn;
@@ -615,8 +600,6 @@ __device__ __forceinline__ void chain_group_body(const hb_sweep_in *__restrict__
 #pragma unroll
             for (int x = 0; x < HBG_FW; x++) fw[x] = 0.0;
             // (row addresses are "wave-uniform pointer"[t]: scalar base + one vector offset, no 64-bit vector arithmetic)
-            using gram_t = typename std::conditional<G16, int16_t, int32_t>::type;
-            const gram_t *gbase = G16 ? reinterpret_cast<const gram_t *>(v.gram16) + (size_t)gp0 * (pv.Lg + 1) * PP : reinterpret_cast<const gram_t *>(gblk0);
             if (CERT && !need_full) {
                 // every passed-over marker is proven to stay and the round reaches the group's end: only the next group's panels need the moves
                 // (rows requested together: at most 63 loads per lane; round 6: up to 15 moves per trip where a move has few rows — BayesR's 16 moves per
@@ -650,7 +633,7 @@ __device__ __forceinline__ void chain_group_body(const hb_sweep_in *__restrict__
 #pragma unroll 1
             for (int e0 = 0; e0 < nmoves; e0 += HBG_CH) {
                 int gv[HBG_CH][HBG_DM], gf[HBG_CH][HBG_FW];
-                int pae[HBG_CH], iae[HBG_CH], gaf[HBG_CH], latm[HBG_CH];
+                int pae[HBG_CH], iae[HBG_CH], latm[HBG_CH];
                 double dl[HBG_CH];
 #pragma unroll
                 for (int f = 0; f < HBG_CH; f++) {
@@ -659,7 +642,6 @@ __device__ __forceinline__ void chain_group_body(const hb_sweep_in *__restrict__
                     pae[f] = a >> lgP;
                     iae[f] = a & (P - 1);
                     dl[f] = (e0 + f < nmoves) ? ev_del[e] : 0.0;
-                    gaf[f] = G16 ? __builtin_amdgcn_readfirstlane(ev_ga[e]) : 0;
                     // bit i: marker (i, t) comes after the mover in the order (an integer mask, used through a one-bit signed field extract: as
                     // a chain of && and || the compiler built it from scalar branches and sixteen lane masks per trip)
                     latm[f] = (int)(((0x1feu << pae[f]) & 0xffu) | ((t > iae[f]) ? 1u << pae[f] : 0u));
@@ -670,14 +652,14 @@ __device__ __forceinline__ void chain_group_body(const hb_sweep_in *__restrict__
                     // gblk0 + (i (Lg + 1) + i - pae) PP = (gblk0 - pae PP) + i (Lg + 2) PP; the panels ahead continue the same walk.
                     // Branch-free: a panel before the mover's or past the group's end reads a neighbouring valid row instead (its
                     // value is not used) — behind a branch every load would be waited for on the spot.
-                    const gram_t *row = gbase + (size_t)iae[f] * P + (size_t)pae[f] * (pstep - PP); // i = pae
+                    const int32_t *row = gblk0 + (size_t)iae[f] * P + (size_t)pae[f] * (pstep - PP); // i = pae
 #pragma unroll
                     for (int i = 0; i < HBG_DM; i++) {
                         gv[f][i] = row[t];
                         row += (i >= pae[f] && i + 1 < Dg) ? pstep : 0; // (scalar select)
                     }
                     // (no panel ahead at the end of the sweep: the loads stay, on an address that exists; their values are not used)
-                    row = have_fw ? gbase + (size_t)iae[f] * P + (size_t)D * pstep - (size_t)pae[f] * PP : gbase; // first panel ahead
+                    row = have_fw ? gblk0 + (size_t)iae[f] * P + (size_t)D * pstep - (size_t)pae[f] * PP : gblk0; // first panel ahead
 #pragma unroll
                     for (int x = 0; x < HBG_FW; x++) {
                         gf[f][x] = row[t];
@@ -690,12 +672,11 @@ __device__ __forceinline__ void chain_group_body(const hb_sweep_in *__restrict__
                     for (int i = 0; i < HBG_DM; i++) {
                         // marker (i, t) takes the move of (pae, iae) if it comes later in the order: the others add an exact zero (a panel past
                         // the group's end takes whatever its stand-in row holds — its right-hand side is never looked at)
-                        // (G16: G[k][j] = g16[k][j] + ga[k] gB[j], an exact integer — the fold's arithmetic is the int32 band's, bit for bit)
-                        const int gm = (G16 ? gv[f][i] + gaf[f] * gBi[G16 ? i : 0] : gv[f][i]) & __builtin_amdgcn_sbfe(latm[f], i, 1);
+                        const int gm = gv[f][i] & __builtin_amdgcn_sbfe(latm[f], i, 1);
                         rnew[i] = fma(-(double)gm, dl[f], rnew[i]);
                     }
 #pragma unroll
-                    for (int x = 0; x < HBG_FW; x++) fw[x] = (x < nfw) ? fma((double)(G16 ? gf[f][x] + gaf[f] * gBf[G16 ? x : 0] : gf[f][x]), dl[f], fw[x]) : fw[x];
+                    for (int x = 0; x < HBG_FW; x++) fw[x] = (x < nfw) ? fma((double)gf[f][x], dl[f], fw[x]) : fw[x];
                 }
             }
             }
@@ -846,12 +827,12 @@ __device__ __forceinline__ void chain_group_body(const hb_sweep_in *__restrict__
     }
 }
 
-template <int K1, int HBG_DM, int HBG_FW, int HBG_CH, bool G16 = false, bool CERT = false, bool FRESH = false>
+template <int K1, int HBG_DM, int HBG_FW, int HBG_CH, bool CERT = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_chain_group(const hb_sweep_in *__restrict__ pin, chain_view v,
                                                                                                  persist_view pv)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    chain_group_body<K1, HBG_DM, HBG_FW, HBG_CH, G16, CERT, FRESH>(pin, v, pv, smem);
+    chain_group_body<K1, HBG_DM, HBG_FW, HBG_CH, CERT>(pin, v, pv, smem);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -867,18 +848,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // forward sums: the same chain in exact arithmetic (tests: draw for draw).
 // HBF_D = D panels per group (slot y of fs[] is panel y counted from the first panel of group g + 2), HBF_G = Lv - 1 groups.
 // ---------------------------------------------------------------------------------------------
-// (round 6: the body as a device function on a caller-supplied LDS region, so that it can also run as the SECOND workgroup of the chain's own kernel —
-// k_chain_group_fwd below: one graph branch and one hardware queue instead of two)
-template <int HBF_D, int HBF_G>
-constexpr int hbf_lds_bytes(bool g16) { return HBF_D * 512 * 8 + HBF_D * 512 * 4 + (g16 ? HBF_D * 512 * 4 : 16) + (HBF_D + 1) * 4 + 16; }
-template <int HBF_D, int HBF_G, int HBF_CH, bool G16 = false, bool FRESH = false>
+template <int HBF_D>
+constexpr int hbf_lds_bytes() { return HBF_D * 512 * 8 + HBF_D * 512 * 4 + (HBF_D + 1) * 4 + 16; }
+template <int HBF_D, int HBF_G, int HBF_CH>
 __device__ __forceinline__ void fwd_body(const chain_view &v, const persist_view &pv, char *lds)
 {
     constexpr int NF = HBF_D * HBF_G;
     double *s_del = reinterpret_cast<double *>(lds);                 // [HBF_D * 512] the group's moves: changes of effect
     int *s_pos = reinterpret_cast<int *>(s_del + HBF_D * 512);       // [HBF_D * 512] ... panel * P + marker
-    int *s_ga = s_pos + HBF_D * 512;                                 // [G16 ? HBF_D * 512 : 4] G16: ga[] of the movers
-    int *s_cnt = s_ga + (G16 ? HBF_D * 512 : 4);                     // [HBF_D + 1]
+    int *s_cnt = s_pos + HBF_D * 512;                                // [HBF_D + 1]
     int &s_ok = s_cnt[HBF_D + 1];
     const int P = v.P, t = threadIdx.x, lgP = 31 - __clz(P);
     const int D = pv.D, np = pv.npanels, G = pv.Lv - 1;
@@ -904,7 +882,7 @@ __device__ __forceinline__ void fwd_body(const chain_view &v, const persist_view
                 unsigned looks = 0;
                 while (c < 0 && !ld_flag(pv.flags + HB_FLAG_ABORT) && wall_clock64() - t0 < HB_TIMEOUT_TICKS) {
                     __builtin_amdgcn_s_sleep(2);
-                    c = ld_poll(&v.ev_count[(size_t)(gp0 + i) * HB_EVS], looks++, FRESH ? 4u : 0u);
+                    c = ld_poll(&v.ev_count[(size_t)(gp0 + i) * HB_EVS], looks++);
                 }
                 if (c < 0) { st_flag(pv.flags + HB_FLAG_ABORT, 1u); c = 0; s_ok = 0; }
                 a += c;
@@ -924,28 +902,20 @@ __device__ __forceinline__ void fwd_body(const chain_view &v, const persist_view
                 unsigned looks = 0;
                 while ((ix < 0 || __double_as_longlong(dl) == -1ll) && !ld_flag(pv.flags + HB_FLAG_ABORT) && wall_clock64() - t0 < HB_TIMEOUT_TICKS) {
                     __builtin_amdgcn_s_sleep(2);
-                    ix = ld_poll(&v.ev_idx[src], looks, FRESH ? 4u : 0u);
-                    dl = ld_poll(&v.ev_delta[src], looks, FRESH ? 4u : 0u);
+                    ix = ld_poll(&v.ev_idx[src], looks);
+                    dl = ld_poll(&v.ev_delta[src], looks);
                     looks++;
                 }
                 if (ix < 0 || __double_as_longlong(dl) == -1ll) { st_flag(pv.flags + HB_FLAG_ABORT, 1u); ix = 0; dl = 0.0; }
                 s_pos[b + k] = i * P + ix;
                 s_del[b + k] = dl;
-                if constexpr (G16) s_ga[b + k] = v.ga[(size_t)(gp0 + i) * P + ix];
             }
         }
         __syncthreads();
-        using gram_t = typename std::conditional<G16, int16_t, int32_t>::type;
-        const gram_t *gblk0 = (G16 ? reinterpret_cast<const gram_t *>(v.gram16) : reinterpret_cast<const gram_t *>(v.gram)) + (size_t)gp0 * (pv.Lg + 1) * PP;
-        int gBy[G16 ? NF : 1]; // G16: gB of this thread's marker in each far panel
-        (void)gBy;
-        if constexpr (G16) {
-#pragma unroll
-            for (int y = 0; y < NF; y++) gBy[y] = v.gB[(size_t)min(gp0 + 2 * D + y, np - 1) * P + t];
-        }
+        const int32_t *gblk0 = v.gram + (size_t)gp0 * (pv.Lg + 1) * PP;
 #pragma unroll 1
         for (int e0 = 0; e0 < nev; e0 += HBF_CH) {
-            int gf[HBF_CH][NF], gaf[HBF_CH];
+            int gf[HBF_CH][NF];
             double dl[HBF_CH];
 #pragma unroll
             for (int f = 0; f < HBF_CH; f++) {
@@ -953,9 +923,8 @@ __device__ __forceinline__ void fwd_body(const chain_view &v, const persist_view
                 const int a = __builtin_amdgcn_readfirstlane(s_pos[e]);
                 const int pa = a >> lgP, ia = a & (P - 1);
                 dl[f] = (e0 + f < nev) ? s_del[e] : 0.0;
-                gaf[f] = G16 ? __builtin_amdgcn_readfirstlane(s_ga[G16 ? e : 0]) : 0;
                 // panel y (counted from the first panel of group g + 2) meets the mover in block l = 2 D + y - pa: the chain's walk, 2 D panels on
-                const gram_t *row = gblk0 + (size_t)ia * P + (size_t)(2 * D) * pstep - (size_t)pa * PP;
+                const int32_t *row = gblk0 + (size_t)ia * P + (size_t)(2 * D) * pstep - (size_t)pa * PP;
 #pragma unroll
                 for (int y = 0; y < NF; y++) {
                     gf[f][y] = row[t];
@@ -965,7 +934,7 @@ __device__ __forceinline__ void fwd_body(const chain_view &v, const persist_view
 #pragma unroll
             for (int f = 0; f < HBF_CH; f++)
 #pragma unroll
-                for (int y = 0; y < NF; y++) fs[y] = (y < nfar) ? fma((double)(G16 ? gf[f][y] + gaf[f] * gBy[G16 ? y : 0] : gf[f][y]), dl[f], fs[y]) : fs[y];
+                for (int y = 0; y < NF; y++) fs[y] = (y < nfar) ? fma((double)gf[f][y], dl[f], fs[y]) : fs[y];
         }
         // group g + 2 has now heard from every group that owes it: publish, and shift what the later ones have so far
 #pragma unroll
@@ -981,23 +950,9 @@ __device__ __forceinline__ void fwd_body(const chain_view &v, const persist_view
     }
 }
 
-template <int HBF_D, int HBF_G, int HBF_CH, bool G16 = false, bool FRESH = false>
+template <int HBF_D, int HBF_G, int HBF_CH>
 __global__ __launch_bounds__(512) void k_fwd(chain_view v, persist_view pv)
 {
-    __shared__ __attribute__((aligned(16))) char lds[hbf_lds_bytes<HBF_D, HBF_G>(G16)];
-    fwd_body<HBF_D, HBF_G, HBF_CH, G16, FRESH>(v, pv, lds);
-}
-
-// ---------------------------------------------------------------------------------------------
-// k_chain_group_fwd (round 6): the chain workgroup and k_fwd as the two workgroups of ONE kernel (each takes a compute unit: both ask for the whole LDS) —
-// one graph branch and one hardware queue instead of two, which is what lets the overlapped launch stream (two tile streams + the update kernels) fit the
-// four queues a process gets (profiles/r06_overlap.txt).
-// ---------------------------------------------------------------------------------------------
-template <int K1, int HBG_DM, int HBG_FW, int HBG_CH, bool CERT, int HBF_D, int HBF_G, int HBF_CH>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_chain_group_fwd(const hb_sweep_in *__restrict__ pin, chain_view v,
-                                                                                                     persist_view pv)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    if (blockIdx.x == 0) chain_group_body<K1, HBG_DM, HBG_FW, HBG_CH, false, CERT>(pin, v, pv, smem);
-    else fwd_body<HBF_D, HBF_G, HBF_CH, false>(v, pv, smem);
+    __shared__ __attribute__((aligned(16))) char lds[hbf_lds_bytes<HBF_D>()];
+    fwd_body<HBF_D, HBF_G, HBF_CH>(v, pv, lds);
 }

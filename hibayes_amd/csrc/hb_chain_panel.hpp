@@ -27,8 +27,7 @@ struct chain_view {
     // marker raises it by at most xabs * |D|; the update derives the digits' exponent from it (null: other paths)
     double *mb;
     double xabs;
-    // round 5: the band as rank one + int16 residual (hb_ctx.gram16): G[k][j] = ga[k] * gB[j] + gram16[k][j]; null: not built
-    const int16_t *gram16;
+    // the band's rank-one part (hb_ctx.ga / gB): G[k][j] = ga[k] * gB[j] + c[k][j]; null: no certificate
     const int32_t *ga, *gB;
     const int32_t *gcmax; // the certificate's bound (hb_build_gcert); null: no certificate
 };

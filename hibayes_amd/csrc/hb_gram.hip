@@ -145,7 +145,7 @@ static int gram_launch(hb_ctx *c, const int8_t *Xv, int pa, int pb)
     return HB_OK;
 }
 
-// ---- the compact band (round 5): G = ga (x) gB + int16 residual ----
+// ---- the rank-one part of the band: G = ga (x) gB + residual (the group chain's certificate) ----
 __global__ void k_g16_ab(const double *__restrict__ s1, int m_pad, double n, int32_t *__restrict__ ga, int32_t *__restrict__ gB)
 {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
@@ -154,31 +154,6 @@ __global__ void k_g16_ab(const double *__restrict__ s1, int m_pad, double n, int
     ga[j] = (int32_t)rint(s / 256.0);
     gB[j] = (int32_t)rint(s * 256.0 / n);
 }
-// one thread per four consecutive entries of a row (the band's own order: [panel][block l][row k][column t])
-__global__ __launch_bounds__(256) void k_gram16(const int32_t *__restrict__ gram, int16_t *__restrict__ g16, const int32_t *__restrict__ ga,
-                                                const int32_t *__restrict__ gB, int P, int Lg, size_t nquads, int *__restrict__ flag)
-{
-    const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= nquads) return;
-    const size_t idx = q * 4, PP = (size_t)P * P;
-    const size_t blk = idx / PP, within = idx % PP;
-    const int p = (int)(blk / (size_t)(Lg + 1)), l = (int)(blk % (size_t)(Lg + 1));
-    const int k = (int)(within / P), t = (int)(within % P);
-    const int4 gq = *reinterpret_cast<const int4 *>(gram + idx);
-    int a = 0;
-    if (p - l >= 0) a = ga[(size_t)(p - l) * P + k];
-    const int4 bq = *reinterpret_cast<const int4 *>(gB + (size_t)p * P + t);
-    // (64-bit: the difference of two int32-range numbers; whatever does not fit a short raises the flag and the band stays int32 only)
-    const long long d0 = (long long)gq.x - (long long)a * bq.x, d1 = (long long)gq.y - (long long)a * bq.y, d2 = (long long)gq.z - (long long)a * bq.z,
-                    d3 = (long long)gq.w - (long long)a * bq.w;
-    const long long lo = min(min(d0, d1), min(d2, d3)), hi = max(max(d0, d1), max(d2, d3));
-    if (p - l >= 0 && (lo < -32767 || hi > 32767)) *flag = 1; // (any writer: the band then stays int32 only)
-    const int c0 = (int)d0, c1 = (int)d1, c2 = (int)d2, c3 = (int)d3;
-    short4 o;
-    o.x = (short)c0; o.y = (short)c1; o.z = (short)c2; o.w = (short)c3;
-    *reinterpret_cast<short4 *>(g16 + idx) = o;
-}
-
 // cmax[k] = max over the stored band of |G[k][j] - ga[k] gB[j]|, row marker k (one 128-thread block per row of a block: P / 4 threads x 4 entries)
 __global__ __launch_bounds__(128) void k_gcmax(const int32_t *__restrict__ gram, const int32_t *__restrict__ ga, const int32_t *__restrict__ gB, int P, int Lg,
                                                int32_t *__restrict__ gcmax)
@@ -220,7 +195,6 @@ int hb_build_gcert(hb_ctx *c)
         HB_HIP(hipMalloc(reinterpret_cast<void **>(&c->ga), sizeof(int32_t) * (size_t)c->m_pad));
         HB_HIP(hipMalloc(reinterpret_cast<void **>(&c->gB), sizeof(int32_t) * (size_t)c->m_pad));
         HB_HIP(hipMalloc(reinterpret_cast<void **>(&c->gcmax), sizeof(int32_t) * (size_t)c->m_pad));
-        HB_HIP(hipMalloc(reinterpret_cast<void **>(&c->g16_flag), sizeof(int)));
     }
     hipLaunchKernelGGL(k_g16_ab, dim3((c->m_pad + 255) / 256), dim3(256), 0, c->stream, c->s1, c->m_pad, (double)c->n, c->ga, c->gB);
     HB_HIP(hipMemsetAsync(c->gcmax, 0, sizeof(int32_t) * (size_t)c->m_pad, c->stream));
@@ -228,36 +202,6 @@ int hb_build_gcert(hb_ctx *c)
     hipLaunchKernelGGL(k_gcmax, dim3((unsigned)nrows), dim3(128), 0, c->stream, c->gram, c->ga, c->gB, c->P, c->Lg, c->gcmax);
     HB_HIP(hipGetLastError());
     c->gcert_ok = true;
-    return HB_OK;
-}
-
-// ... and the compact copy, if every residual fits an int16 (non-negative genotype codes only: the column
-// sums are then the scale of every product)
-int hb_build_gram16(hb_ctx *c)
-{
-    c->gram16_ok = false;
-    if (!c->gram16_on || c->xmin < 0 || c->P % 4 != 0 || c->row_reduce) return HB_OK; // (row-sharded mode: the local blocks are partial sums)
-    const size_t need = (size_t)c->m_pad * (size_t)c->P * (size_t)(c->Lg + 1);
-    if (need > c->gram16_cap) {
-        if (c->gram16) { (void)hipFree(c->gram16); c->gram16 = nullptr; }
-        c->gram16_cap = 0;
-        if (hipMalloc(reinterpret_cast<void **>(&c->gram16), need * sizeof(int16_t)) != hipSuccess) { // (no room: the int32 band serves)
-            (void)hipGetLastError();
-            c->gram16 = nullptr;
-            return HB_OK;
-        }
-        c->gram16_cap = need;
-    }
-    if (!c->gcert_ok) return HB_OK; // (ga / gB come from hb_build_gcert)
-    HB_HIP(hipMemsetAsync(c->g16_flag, 0, sizeof(int), c->stream));
-    const size_t nquads = need / 4;
-    hipLaunchKernelGGL(k_gram16, dim3((unsigned)((nquads + 255) / 256)), dim3(256), 0, c->stream, c->gram, c->gram16, c->ga, c->gB, c->P, c->Lg,
-                       nquads, c->g16_flag);
-    HB_HIP(hipGetLastError());
-    int flag = 0;
-    HB_HIP(hipMemcpyAsync(&flag, c->g16_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HB_HIP(hipStreamSynchronize(c->stream));
-    c->gram16_ok = flag == 0;
     return HB_OK;
 }
 

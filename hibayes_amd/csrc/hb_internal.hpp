@@ -48,12 +48,8 @@ struct hb_ctx {
     int D = 1;     // panels per mat-vec launch
     int NB = 1;    // residual versions kept = Lv + D
     int pipeline = 0;              // 0: serial kernels per panel; 1: persistent chain workgroup + flags
-    int chain_kind = 1;            // group-granular chain (k_chain_group): bit 0 BayesB/C, bit 1 the dense models at one panel per group; 0 = k_chain_persist everywhere (HB_CHAIN=panel / all / <bits>)
     int num_cus = 256;             // compute units of the device (hipDeviceProp_t::multiProcessorCount)
-    bool warm_group = false;       // k_warm beside the group chain (HB_WARM_GROUP=1)
-    int warm_g = 0;                // k_warm workgroups per XCD beside the wide group chain with k_fwd (HB_WARM_G)
-    bool dense_chain = true;       // BayesRR / A / L at panel 512: k_chain_dense + k_fold_dense (hb_chain_dense.hpp; HB_DENSE=0: k_chain_persist)
-    bool fwd_group = true;         // k_fwd beside the group chain: a second workgroup folds a move's rows for the group after next (HB_FWD=0: off)
+    bool dense_upd = true;         // the dense update rows beside k_chain_dense on int8 columns (HB_DENSE_UPD set: the plain ones)
     bool concurrent = true;        // kernels on two streams were seen running at the same time (probe at create)
     std::string pipeline_note;     // why the persistent pipeline is off, when it is
     unsigned int *flags = nullptr; // [0] chain_done (panels whose moves are published), [1] abort
@@ -69,15 +65,6 @@ struct hb_ctx {
     hipStream_t s_chain = nullptr;     // serial chain kernels
     hipStream_t s_upd = nullptr;       // residual updates
     hipStream_t s_warm = nullptr;      // k_warm where k_fwd has s_upd (BayesR)
-    // round 6, overlapped launch stream (HB_OVERLAP): the mat-vec launches of a sweep alternate between `stream` and s_t2, the residual updates are kernels of
-    // their own on s_uk and the finalize kernels on s_fk — every dependency a graph edge, two launches in flight (hb_kernels.hip: enqueue_sweep_pipeline)
-    hipStream_t s_t2 = nullptr, s_uk = nullptr, s_fk = nullptr;
-    std::vector<hipEvent_t> ev_ot, ev_ou; // per mat-vec group: its tiles are done / its residual update is done
-    int overlap = 0;                      // 0 off, 1 on (HB_OVERLAP)
-    // round 6: the persistent mat-vec (hb_mvp.hpp; HB_MVP): digit planes and exponents per residual VERSION (rq / vexp grown to rq_slots slots), hand-over counters
-    int mvp = 0;
-    int rq_slots = 8;
-    unsigned *mvp_ho = nullptr;
     std::vector<hipEvent_t> ev_dot, ev_chain, ev_upd; // cross-stream dependencies of one sweep
     hipEvent_t ev_fork = nullptr;
 
@@ -107,16 +94,11 @@ struct hb_ctx {
     long long *accq = nullptr;    // [HB_ND][m_pad] exact digit-plane sums of the current sweep's mat-vecs
     int32_t *gram = nullptr;
     size_t gram_cap = 0; // ints allocated
-    // Round 5: the band once more as "rank one + int16 residual" — G[k][j] = ga[k] * gB[j] + gram16[k][j] exactly, with ga = rint(s1 / 256),
-    // gB = rint(256 s1 / n) (s1: column sums): the product is the part of x_k . x_j that every pair of markers shares (n mean_k mean_j), what is
-    // left is n cov(k, j) plus rounding, a few hundred for unlinked markers and at most n var for a pair in full LD. The group chain and k_fwd
-    // fold a move's rows from it: half the bytes of the phase that is 44 % of their time. Built when every residual fits (else null: the int32 band serves).
-    int16_t *gram16 = nullptr;
-    size_t gram16_cap = 0;
+    // The band as "rank one + residual": G[k][j] = ga[k] * gB[j] + c[k][j] exactly, with ga = rint(s1 / 256), gB = rint(256 s1 / n) (s1: column
+    // sums): the product is the part of x_k . x_j that every pair of markers shares (n mean_k mean_j), what is left is n cov(k, j) plus rounding,
+    // a few hundred for unlinked markers and at most n var for a pair in full LD.
     int32_t *ga = nullptr, *gB = nullptr, *gcmax = nullptr; // G[k][j] = ga[k] gB[j] + c[k][j], |c[k][j]| <= gcmax[k]: the group chain's certificate (hb_build_gcert)
     bool gcert_ok = false, gcert_on = true;                 // (HB_CERT=0: off)
-    int *g16_flag = nullptr;
-    bool gram16_ok = false, gram16_on = false; // (HB_GRAM16=1: on. OFF by default: measured slower than the int32 band both ways it was read)
     bool env_pinned = false;
     int dot_lds = 0;     // dynamic LDS bytes requested by each mat-vec workgroup: caps the workgroups resident per CU
     int q2m_ct = 4, q2m_g = 0, q2m_sc = 1; // k_dotq2m's shape (HB_Q2M_CT / _G / _SC): column tiles of 16 per wave; stages requested together (1, 2) or 512-individual stages of whole-line
@@ -230,7 +212,6 @@ extern "C" int hb_ctx_sweep_begin(hb_ctx *c, const hb_sweep_in *in);
 extern "C" int hb_ctx_sweep_end(hb_ctx *c, hb_sweep_out *out);
 int hb_comm_allreduce_f64(hb_comm *c, double *buf, size_t count, hipStream_t st);
 int hb_build_gram_impl(hb_ctx *c);
-int hb_build_gram16(hb_ctx *c);
 int hb_build_gcert(hb_ctx *c);
 
 // device buffers of one summary-level run (hb_sbayes.hip owns them; the kernels are in hb_sbayes.hpp)

@@ -41,18 +41,8 @@
 #include "hb_update.hpp"
 #include "hb_matvec.hpp"
 #include "hb_dotq2.hpp"
-// The persistent mat-vec is an EXPERIMENT (round 6; DESIGN section 6.0: it does not hold the pace of the launches and stalls at the wide geometry): built only
-// with -DHB_WITH_MVP=1 (tools/build_variant.sh mvp "-DHB_WITH_MVP=1"; then HB_MVP=1 selects it). Its instantiations stay out of the default library on
-// purpose: merely having them in this translation unit changed the inlining around the headline chain kernel, which sits at 256 registers — five spilled
-// registers, 446 -> 421 sweeps/s (tools/kernel_resources.sh shows the spills per kernel).
-#ifndef HB_WITH_MVP
-#define HB_WITH_MVP 0
-#endif
 #ifndef HB_W8_CH
 #define HB_W8_CH 3 /* moves per trip of the eight-panel group chain (4 spills nine registers, 3 four) */
-#endif
-#if HB_WITH_MVP
-#include "hb_mvp.hpp"
 #endif
 
 // Sweep start of the fixed-point path: max |yadj| -> mb[0] and the exponent of slot 0, then slot 0's digit planes.
@@ -173,35 +163,59 @@ static int persist_nslot(int P, int Lb, int K1) { return std::min(P, std::min(25
 static size_t persist_smem(int) { return (size_t)160 * 1024; }
 static size_t chain_smem(int P) { return (size_t)chain_nslot(P) * P * 4 + (size_t)P * 16 + 128 + 128 + 64; }
 
+// The chain kernels that ask for the whole 160 KiB of LDS, picked by the three functions below. They are the one list of these
+// instantiations: hbk_init_attrs raises the LDS limit of every kernel they can return.
+using persist_chain_fn = void (*)(const hb_sweep_in *, chain_view, persist_view, int);
+using group_chain_fn = void (*)(const hb_sweep_in *, chain_view, persist_view);
+using dense_chain_fn = void (*)(const hb_sweep_in *, chain_view, persist_view, double *, const double *);
+
+// k_chain_persist: candidate rows ahead (NPL == Lb) for the band widths of the default geometries; any other band goes without
+static persist_chain_fn persist_chain_kernel(int kp, int Lb, bool fcorr)
+{
+    if (kp == 1) {
+        if (Lb == 20) return k_chain_persist<1, 20>; // (Lv, D) = (2, 7)
+        if (Lb == 17) return k_chain_persist<1, 17>; // (Lv, D) = (2, 6)
+        if (Lb == 1) return k_chain_persist<1, 1>;
+        return k_chain_persist<1, 0>;
+    }
+    const bool npl2 = Lb == 2 && !fcorr; // (with k_fwd beside it the chain requests its fold rows itself, after the rounds)
+    if (kp == 3) return npl2 ? k_chain_persist<3, 2> : k_chain_persist<3, 0>;
+    return npl2 ? k_chain_persist<7, 2> : k_chain_persist<7, 0>;
+}
+
+// k_chain_group: mix = BayesR with up to four classes, else BayesB / BayesC; shape 0 / 1 / 2 (enqueue_sweep_pipeline); fwd: k_fwd beside it,
+// fwd2 / wide8 its (2, 2) BayesR and (2, 8) forms; cert: the certified violation check at panel 512; narrow: three or four panels per launch
+static group_chain_fn group_chain_kernel(bool mix, int shape, bool fwd, bool fwd2, bool wide8, bool cert, bool narrow)
+{
+    if (mix) {
+        if (fwd2) return k_chain_group<3, 2, 2, 15, true>;
+        if (fwd) return cert ? k_chain_group<3, 8, 7, 4, true> : k_chain_group<3, 8, 7, 4>;
+        if (cert && narrow) return k_chain_group<3, 4, 8, 5, true>;
+        if (shape == 0) return k_chain_group<3, 8, 14, 3>;
+        return cert ? k_chain_group<3, 2, 4, 10, true> : k_chain_group<3, 2, 4, 10>; // (shape 1: D = 2)
+    }
+    if (wide8) return k_chain_group<1, 8, 8, HB_W8_CH, true>;
+    if (fwd) return cert ? k_chain_group<1, 8, 7, 4, true> : k_chain_group<1, 8, 7, 4>;
+    if (shape == 0) return k_chain_group<1, 8, 14, 3>;
+    if (shape == 1) return k_chain_group<1, 2, 4, 10>;
+    return k_chain_group<1, 1, 2, 20>;
+}
+
+static dense_chain_fn dense_chain_kernel(bool bayesl) { return bayesl ? k_chain_dense<true> : k_chain_dense<false>; }
+
 int hbk_init_attrs()
 {
-#define HB_PERSIST_ATTR(K1, NPL) HB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_chain_persist<K1, NPL>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024))
-    HB_PERSIST_ATTR(1, 0); HB_PERSIST_ATTR(1, 1); HB_PERSIST_ATTR(1, 17); HB_PERSIST_ATTR(1, 20);
-    HB_PERSIST_ATTR(3, 0); HB_PERSIST_ATTR(3, 2);
-    HB_PERSIST_ATTR(7, 0); HB_PERSIST_ATTR(7, 2);
-#define HB_GROUP_ATTR(K1, DM, FW, CH) HB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_chain_group<K1, DM, FW, CH>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024))
-#define HB_GROUP_ATTR16(K1, DM, FW, CH) HB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_chain_group<K1, DM, FW, CH, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024))
-    HB_GROUP_ATTR(1, 8, 14, 3); HB_GROUP_ATTR(1, 8, 7, 4); HB_GROUP_ATTR(1, 2, 4, 10); HB_GROUP_ATTR(1, 1, 2, 20);
-    HB_GROUP_ATTR(3, 1, 2, 20); HB_GROUP_ATTR(7, 1, 2, 20);
-    HB_GROUP_ATTR(3, 8, 14, 3); HB_GROUP_ATTR(3, 8, 7, 4); HB_GROUP_ATTR(3, 2, 4, 10); // round 6: BayesR (K <= 4 classes) on the group chain at every shape
-    HB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_chain_group<3, 8, 7, 4, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_chain_group<3, 2, 4, 10, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_chain_group<3, 4, 8, 5, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_chain_group<3, 2, 2, 15, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_chain_group_fwd<1, 8, 7, 4, true, 7, 1, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_chain_group_fwd<1, 8, 7, 4, true, 7, 2, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HB_GROUP_ATTR16(1, 8, 7, 4);
-    HB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_chain_group<1, 8, 7, 4, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_chain_group<1, 8, 8, HB_W8_CH, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-#if HB_WITH_MVP
-    HB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_chain_group<1, 8, 7, 4, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_chain_group<1, 2, 4, 10, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-#endif
-    HB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_chain_dense<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_chain_dense<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_chain<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_chain<3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_chain<7>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    auto lds160 = [](const void *k) { return hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); };
+    for (int kp : {1, 3, 7})
+        for (int Lb = 0; Lb <= HB_LBMAX; Lb++)
+            for (bool fc : {false, true}) HB_HIP(lds160(reinterpret_cast<const void *>(persist_chain_kernel(kp, Lb, fc))));
+    for (int bits = 0; bits < 64; bits++)
+        for (int shape = 0; shape < 3; shape++)
+            HB_HIP(lds160(reinterpret_cast<const void *>(group_chain_kernel(bits & 1, shape, bits & 2, bits & 4, bits & 8, bits & 16, bits & 32))));
+    for (bool bayesl : {false, true}) HB_HIP(lds160(reinterpret_cast<const void *>(dense_chain_kernel(bayesl))));
+    HB_HIP(lds160(reinterpret_cast<const void *>(&k_chain<1>)));
+    HB_HIP(lds160(reinterpret_cast<const void *>(&k_chain<3>)));
+    HB_HIP(lds160(reinterpret_cast<const void *>(&k_chain<7>)));
     return HB_OK;
 }
 
@@ -625,35 +639,6 @@ static int enqueue_sweep_kernels(hb_ctx *c, int model, int n_fold, bool timed)
     return HB_OK;
 }
 
-template <int K1, int NPL>
-static hipError_t launch_chain_persist2(hb_ctx *c, const chain_view &cv, const persist_view &pv, hipStream_t st)
-{
-    hipLaunchKernelGGL((k_chain_persist<K1, NPL>), dim3(1), dim3(c->P), persist_smem(c->P), st, c->d_in, cv, pv, persist_nslot(c->P, c->L, K1));
-    return hipGetLastError();
-}
-
-template <int K1>
-static hipError_t launch_chain_persist(hb_ctx *c, const chain_view &cv, const persist_view &pv, hipStream_t st)
-{
-    // candidate rows ahead (NPL == Lb) for the band widths of the default geometries; any other band goes without
-    if (K1 == 1) {
-        if (pv.Lb == 20) return launch_chain_persist2<1, 20>(c, cv, pv, st); // (Lv, D) = (2, 7)
-        if (pv.Lb == 17) return launch_chain_persist2<1, 17>(c, cv, pv, st); // (Lv, D) = (2, 6)
-        if (pv.Lb == 1) return launch_chain_persist2<1, 1>(c, cv, pv, st);
-        return launch_chain_persist2<1, 0>(c, cv, pv, st);
-    }
-    if (pv.Lb == 2 && !pv.fcorr) return launch_chain_persist2<K1 == 1 ? 3 : K1, 2>(c, cv, pv, st); // (with k_fwd beside it the chain requests its fold rows itself, after the rounds)
-    return launch_chain_persist2<K1, 0>(c, cv, pv, st);
-}
-
-// Persistent pipeline: stream A = mat-vec launches (each also carrying an update row and a partial-sum row),
-// stream B = ONE chain workgroup for the whole sweep.  Device-side hand-offs: mat-vec -> chain through dsum[]
-// (NaN-prefilled, written through by the partial-sum row of the next launch); chain -> update through
-// chain_done; update -> mat-vec is a kernel boundary on stream A.
-// The panels [pb, pe) of a sweep (pb a multiple of D): the whole sweep, or one block of a sweep whose shards exchange their
-// residual deltas every few mat-vec groups (hb_ctx_sweep_range). A range is self-contained: the residual holds every earlier
-// move when it starts, so its corrections start from zero and its version ring from slot 0. `first` also prepares the
-// per-sweep data (k_pre, k_hotlist, zeroed sums), `last` closes the sweep (BayesL's variances, the residual's sums).
 // debug hook (hb_ctx_debug_inject_abort): raise the abort flag once the chain has published `panel` panels — what a waiter that
 // timed out does — so that the tests can show a replayed sweep to be the same chain
 __global__ void k_inject_abort(unsigned *flags, unsigned panel)
@@ -664,26 +649,38 @@ __global__ void k_inject_abort(unsigned *flags, unsigned panel)
     st_flag(flags + HB_FLAG_ABORT, 1u);
 }
 
-static int enqueue_sweep_pipeline(hb_ctx *c, int model, int n_fold, int pb, int pe, bool first, bool last)
+// Persistent pipeline: stream A = mat-vec launches (each also carrying an update row and a partial-sum row),
+// stream B = ONE chain workgroup for the whole sweep.  Device-side hand-offs: mat-vec -> chain through dsum[]
+// (NaN-prefilled, written through by the partial-sum row of the next launch); chain -> update through
+// chain_done; update -> mat-vec is a kernel boundary on stream A.
+// The panels [pb, pe) of a sweep (pb a multiple of D): the whole sweep, or one block of a sweep whose shards exchange their
+// residual deltas every few mat-vec groups (hb_ctx_sweep_range). A range is self-contained: the residual holds every earlier
+// move when it starts, so its corrections start from zero and its version ring from slot 0. `first` also prepares the
+// per-sweep data (k_pre, k_hotlist, zeroed sums), `last` closes the sweep (BayesL's variances, the residual's sums).
+// env_alone: HB_CHAIN_ALONE, read once per sweep by hb_sweep_enqueue.
+static int enqueue_sweep_pipeline(hb_ctx *c, int model, int n_fold, int pb, int pe, bool first, bool last, bool env_alone)
 {
     const int kp = kpad_for(model, n_fold);
     const int np = pe, D = c->D, Lv = c->Lv;
     const int g0 = pb / D;                             // absolute index of the range's first mat-vec group
     const int ngroups = (np - pb + D - 1) / D;         // groups in the range
     hipStream_t sA = c->stream, sB = c->s_chain;
+    // HB_CHAIN_ALONE=1 / hb_ctx_set_profiling(c, 4) — a TIMING AND COUNTER DIAGNOSTIC, results are meaningless (it needs no
+    // co-resident kernels, so it is also how k_chain_persist runs under a counter-collecting profiler, tools/chain_counters.py): the mat-vec launches run first against a pre-set
+    // chain_done (their update rows find empty event lists), the chain afterwards with the device to itself; the stamped span
+    // (tools/chain_timeline.py with CT_ALONE=1) is then what the chain costs without the mat-vec's memory traffic beside it.
+    const bool alone = c->chain_alone || env_alone;
     // sweep start: one kernel clears the sweep sums, the flag block, the event counts (quiet panels do not write theirs) and
     // fills dsum[] with "not written yet" (a NaN no sum can produce); the residual's digit planes are then written (k_quant0,
     // one workgroup) beside k_pre / k_hotlist, which need all the other compute units. The chain must be launched BEFORE the
     // first mat-vec launch (it needs a compute unit with all of its LDS free, and back-to-back mat-vec launches never leave
     // one), so both branches start together after the join.
     // the models in which every marker moves (BayesRR / A / L) at panel 512: k_chain_dense + k_fold_dense (hb_chain_dense.hpp)
-    const bool dense = kp == 1 && (model == 1 || model == 2 || model == 5) && c->P == 512 && c->dense_chain && !c->chain_alone &&
-                       getenv("HB_CHAIN_ALONE") == nullptr && c->L <= HB_LBMAX;
-    const bool dense_upd = dense && getenv("HB_DENSE_UPD") == nullptr;
+    const bool dense = kp == 1 && (model == 1 || model == 2 || model == 5) && c->P == 512 && !alone && c->L <= HB_LBMAX;
+    const bool dense_upd = dense && c->dense_upd;
     if (c->ldiag) HB_HIP(hipMemsetAsync(c->ldiag, 0, sizeof(unsigned long long) * 4 * ((size_t)c->npanels + 2), sA));
     hipLaunchKernelGGL(k_sweep_init, dim3(256), dim3(256), 0, sA, first ? c->acc : nullptr, c->flags, c->ev_count, c->npanels,
-                       reinterpret_cast<unsigned long long *>(c->dsum), c->m_pad, pb,
-                       (c->fwd_group || dense) ? reinterpret_cast<unsigned long long *>(c->fcorr) : nullptr,
+                       reinterpret_cast<unsigned long long *>(c->dsum), c->m_pad, pb, reinterpret_cast<unsigned long long *>(c->fcorr),
                        dense ? reinterpret_cast<unsigned long long *>(c->ddense) : nullptr,
                        c->precise == 2 ? reinterpret_cast<unsigned long long *>(c->mb) : nullptr, 1 + pb / c->D, c->npanels + 2,
                        dense ? reinterpret_cast<unsigned long long *>(c->fcorr2) : nullptr, c->ev_idx,
@@ -710,105 +707,53 @@ static int enqueue_sweep_pipeline(hb_ctx *c, int model, int n_fold, int pb, int 
     chain_view cv{c->m_pad, c->P, c->nsplit, Lv, c->Lg, c->xpx, c->vx, c->g, c->tracker, c->nzrate, c->alpha_sum, c->alpha_sq,
                   c->thr, c->invv, c->sdz, c->gram, c->partial, c->dsum, c->ev_count, c->ev_idx, c->ev_delta, c->acc,
                   c->wind, c->wflag, c->dbg, fx ? c->mb : nullptr, xabs};
-    const bool g16 = c->gram16_ok && c->gram16 != nullptr && kp == 1; // (the compact band: only the wide group chain and its k_fwd read it)
-    if (g16) { cv.gram16 = c->gram16; cv.ga = c->ga; cv.gB = c->gB; }
-    const bool cert = !g16 && c->gcert_ok && c->gcmax != nullptr; // (the wide group chain's certified violation check)
+    const bool cert = c->gcert_ok && c->gcmax != nullptr; // (the wide group chain's certified violation check)
     if (cert) { cv.ga = c->ga; cv.gB = c->gB; cv.gcmax = c->gcmax; }
     const int last_panels = np - (g0 + ngroups - 1) * D;
     persist_view pv{np, D, Lv, c->L, c->Lg, pb, c->flags,
                     c->hot_slot, c->hot_list, c->thr0f, c->candf, nullptr, nullptr};
     if (cert) pv.opn = c->opn; // (k_hotlist wrote it: gcert_ok)
-    // HB_CHAIN_ALONE=1 / hb_ctx_set_profiling(c, 4) — a TIMING AND COUNTER DIAGNOSTIC, results are meaningless (it needs no
-    // co-resident kernels, so it is also how k_chain_persist runs under a counter-collecting profiler, tools/chain_counters.py): the mat-vec launches run first against a pre-set
-    // chain_done (their update rows find empty event lists), the chain afterwards with the device to itself; the stamped span
-    // (tools/chain_timeline.py with CT_ALONE=1) is then what the chain costs without the mat-vec's memory traffic beside it.
-    const bool alone = c->chain_alone || getenv("HB_CHAIN_ALONE") != nullptr;
-    // the point-mass models run the group-granular chain (hb_chain_group.hpp); HB_CHAIN=panel keeps the per-panel one
-    // (chain_kind bit 0: BayesB / BayesC; bit 1: the dense models too — BayesR and RR / A / L at one panel per group)
-    const int shape = (D <= 1 && Lv * D <= 2) ? 2 : (D <= 2 && Lv * D <= 4) ? 1 : (D <= 8 && Lv * D <= 14) ? 0 : (c->fwd_group && c->P == 512 && ((Lv == 3 && D == 7) || (Lv == 2 && D == 8))) ? 0 : -1;
+    // the point-mass models (and BayesR below) run the group-granular chain (hb_chain_group.hpp); the other models k_chain_persist
+    const int shape = (D <= 1 && Lv * D <= 2) ? 2 : (D <= 2 && Lv * D <= 4) ? 1 : (D <= 8 && Lv * D <= 14) ? 0 : (c->P == 512 && ((Lv == 3 && D == 7) || (Lv == 2 && D == 8))) ? 0 : -1;
     const bool sparse_model = kp == 1 && (model == 3 || model == 4);
-    // round 6: BayesR with up to four classes (kp == 3) runs the group chain too wherever a launch covers more than one panel (chain_kind bit 2
-    // clear; HB_CHAIN=panel keeps k_chain_persist). K1 nested thresholds per candidate instead of one; everything else — candidates, certificate
-    // (it bounds the right-hand side, not the class), fold, k_fwd — is the point-mass models' path.
+    // round 6: BayesR with up to four classes (kp == 3) runs the group chain too wherever a launch covers more than one panel. K1 nested
+    // thresholds per candidate instead of one; everything else — candidates, certificate (it bounds the right-hand side, not the class),
+    // fold, k_fwd — is the point-mass models' path.
     const bool mix_model = kp == 3 && model == 6 && D >= 2;
-    const bool group_chain = !dense && shape >= 0 && !c->chain_alone && (sparse_model ? (c->chain_kind & 1) != 0 : mix_model ? c->chain_kind != 0 : ((c->chain_kind & 2) != 0 && shape == 2));
+    const bool group_chain = !dense && shape >= 0 && !c->chain_alone && (sparse_model || mix_model);
     // k_fwd beside the wide group chain: the chain folds a move into its own group and the next (15 rows, four moves per trip),
-    // a second workgroup into the group after that (HB_FWD=0: the chain does all 22 rows itself, three moves per trip)
+    // a second workgroup into the group after that
     // round 6: also beside BayesR's two-panel groups ((2, 2): the chain folds a move into the next group's two panels, k_fwd into the two after — half of the
     // chain's fold rows leave its compute unit, and a group's ~16 moves fit ONE trip of 62 loads per lane instead of two of 60)
-    const bool fwd2 = group_chain && mix_model && Lv == 2 && D == 2 && c->P == 512 && c->fwd_group && !alone && cert && !getenv("HB_FWD2_OFF");
+    const bool fwd2 = group_chain && mix_model && Lv == 2 && D == 2 && c->P == 512 && !alone && cert;
     // round 6: eight panels per launch (Lv = 2 only, point-mass models, certified): k_chain_group<1, 8, 8, CH, CERT> + k_fwd<8, 1, 8>
-    const bool wide8 = group_chain && kp == 1 && Lv == 2 && D == 8 && c->P == 512 && c->fwd_group && !alone && cert;
-    const bool fwd = (group_chain && (kp == 1 || mix_model) && (Lv == 2 || Lv == 3) && D == 7 && c->P == 512 && c->fwd_group && !alone) || fwd2 || wide8;
-    const bool warm_r_env_off = !(getenv("HB_WARM_G") && atoi(getenv("HB_WARM_G")) > 0);
-    // (only where chain and k_fwd run as ONE kernel — the wide certified shape of BayesB / BayesC: four branches in all, what a process has queues for)
-    const bool overlap = c->overlap && fx && !dense && !alone && !c->lstamp && ngroups > Lv + 2 && Lv + 1 <= 8 && c->s_fk != nullptr &&
-                         fwd && !fwd2 && cert && kp == 1 && !g16 && warm_r_env_off;
-    const bool merged = overlap;
-    // round 6: the persistent mat-vec (hb_mvp.hpp, HB_MVP=1): 2-bit genotypes, matrix-core tiles on 512-individual stages, whole sweeps
-    const bool mvp = HB_WITH_MVP && c->mvp && fx && c->layout == 2 && c->X2 && c->dotq2_kind == 2 && (c->q2m_g == 0) && c->ld % 512 == 0 && !dense && !alone && !overlap &&
-                     pb == 0 && ngroups > Lv + 2 && c->rq_slots >= ngroups + 1 && c->mvp_ho != nullptr &&
-                     kp == 1 && group_chain && !g16 && ((fwd && cert) || (!fwd && shape == 1)); // (the two chain shapes instantiated with memory-side looks)
+    const bool wide8 = group_chain && kp == 1 && Lv == 2 && D == 8 && c->P == 512 && !alone && cert;
+    const bool fwd = (group_chain && (Lv == 2 || Lv == 3) && D == 7 && c->P == 512 && !alone) || fwd2 || wide8;
     if (fwd) pv.fcorr = c->fcorr;
     if (c->L > HB_LBMAX && !fwd)
         return hb_fail(HB_ERR_UNSUPPORTED, "three groups of seven panels of look-ahead need the group chain with k_fwd (BayesB / BayesC, panel 512)");
     if (dense) pv.fcorr = c->fcorr;
     // BayesR on the per-panel chain (round 4): k_fwd folds a panel's moves into the panels two (and, at Lv = 3, three) ahead, the chain
-    // itself only into the next one — half (two thirds) of the band rows of a dense sweep leave the chain's compute unit (HB_FWD=0: off)
-    const bool fwd_persist = !dense && !group_chain && kp == 3 && c->P == 512 && D == 1 && (Lv == 2 || Lv == 3) && c->fwd_group && !alone &&
-                             np - pb > 2 && getenv("HB_FWD_R") == nullptr;
+    // itself only into the next one — half (two thirds) of the band rows of a dense sweep leave the chain's compute unit
+    const bool fwd_persist = !dense && !group_chain && kp == 3 && c->P == 512 && D == 1 && (Lv == 2 || Lv == 3) && !alone && np - pb > 2;
     if (fwd_persist) pv.fcorr = c->fcorr;
     auto launch_the_chain = [&](hipStream_t st) -> int {
+        const char *what = "k_chain_persist";
         if (dense) {
-            if (model == 5) hipLaunchKernelGGL((k_chain_dense<true>), dim3(1), dim3(512), persist_smem(c->P), st, c->d_in, cv, pv, c->ddense, c->fcorr2);
-            else hipLaunchKernelGGL((k_chain_dense<false>), dim3(1), dim3(512), persist_smem(c->P), st, c->d_in, cv, pv, c->ddense, c->fcorr2);
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return hb_fail(HB_ERR_HIP, std::string("k_chain_dense launch: ") + hipGetErrorString(e));
-            return HB_OK;
-        }
-        if (group_chain) {
-            const size_t sm = persist_smem(c->P);
-            if (merged) { // chain + k_fwd as the two workgroups of one kernel (the overlapped launch stream)
-                if (Lv == 2) hipLaunchKernelGGL((k_chain_group_fwd<1, 8, 7, 4, true, 7, 1, 8>), dim3(2), dim3(c->P), sm, st, c->d_in, cv, pv);
-                else hipLaunchKernelGGL((k_chain_group_fwd<1, 8, 7, 4, true, 7, 2, 4>), dim3(2), dim3(c->P), sm, st, c->d_in, cv, pv);
-                hipError_t e = hipGetLastError();
-                if (e != hipSuccess) return hb_fail(HB_ERR_HIP, std::string("k_chain_group_fwd launch: ") + hipGetErrorString(e));
-                return HB_OK;
-            }
-            if (mix_model) {
-                if (fwd2) hipLaunchKernelGGL((k_chain_group<3, 2, 2, 15, false, true>), dim3(1), dim3(c->P), sm, st, c->d_in, cv, pv);
-                else if (fwd && cert) hipLaunchKernelGGL((k_chain_group<3, 8, 7, 4, false, true>), dim3(1), dim3(c->P), sm, st, c->d_in, cv, pv);
-                else if (fwd) hipLaunchKernelGGL((k_chain_group<3, 8, 7, 4>), dim3(1), dim3(c->P), sm, st, c->d_in, cv, pv);
-                else if (cert && c->P == 512 && D <= 4 && Lv * D <= 8 && !(D <= 2 && Lv * D <= 4) && !getenv("HB_CERT_NARROW_OFF"))
-                    hipLaunchKernelGGL((k_chain_group<3, 4, 8, 5, false, true>), dim3(1), dim3(c->P), sm, st, c->d_in, cv, pv); // (three or four panels per launch, certified)
-                else if (shape == 0) hipLaunchKernelGGL((k_chain_group<3, 8, 14, 3>), dim3(1), dim3(c->P), sm, st, c->d_in, cv, pv);
-                else if (cert && c->P == 512 && !getenv("HB_CERT_NARROW_OFF")) hipLaunchKernelGGL((k_chain_group<3, 2, 4, 10, false, true>), dim3(1), dim3(c->P), sm, st, c->d_in, cv, pv); // (shape 1: D = 2, certified)
-                else hipLaunchKernelGGL((k_chain_group<3, 2, 4, 10>), dim3(1), dim3(c->P), sm, st, c->d_in, cv, pv); // (shape 1: D = 2; shape 2 needs D <= 1)
-            }
-#if HB_WITH_MVP
-            else if (mvp && fwd) hipLaunchKernelGGL((k_chain_group<1, 8, 7, 4, false, true, true>), dim3(1), dim3(c->P), sm, st, c->d_in, cv, pv);
-            else if (mvp) hipLaunchKernelGGL((k_chain_group<1, 2, 4, 10, false, false, true>), dim3(1), dim3(c->P), sm, st, c->d_in, cv, pv);
-#endif
-            else if (wide8) hipLaunchKernelGGL((k_chain_group<1, 8, 8, HB_W8_CH, false, true>), dim3(1), dim3(c->P), sm, st, c->d_in, cv, pv);
-            else if (fwd && g16) hipLaunchKernelGGL((k_chain_group<1, 8, 7, 4, true>), dim3(1), dim3(c->P), sm, st, c->d_in, cv, pv);
-            else if (fwd && cert) hipLaunchKernelGGL((k_chain_group<1, 8, 7, 4, false, true>), dim3(1), dim3(c->P), sm, st, c->d_in, cv, pv);
-            else if (fwd) hipLaunchKernelGGL((k_chain_group<1, 8, 7, 4>), dim3(1), dim3(c->P), sm, st, c->d_in, cv, pv);
-            else if (kp == 1 && shape == 0) hipLaunchKernelGGL((k_chain_group<1, 8, 14, 3>), dim3(1), dim3(c->P), sm, st, c->d_in, cv, pv);
-            else if (kp == 1 && shape == 1) hipLaunchKernelGGL((k_chain_group<1, 2, 4, 10>), dim3(1), dim3(c->P), sm, st, c->d_in, cv, pv);
-            else if (kp == 1) hipLaunchKernelGGL((k_chain_group<1, 1, 2, 20>), dim3(1), dim3(c->P), sm, st, c->d_in, cv, pv);
-            else if (kp == 3) hipLaunchKernelGGL((k_chain_group<3, 1, 2, 20>), dim3(1), dim3(c->P), sm, st, c->d_in, cv, pv);
-            else hipLaunchKernelGGL((k_chain_group<7, 1, 2, 20>), dim3(1), dim3(c->P), sm, st, c->d_in, cv, pv);
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return hb_fail(HB_ERR_HIP, std::string("k_chain_group launch: ") + hipGetErrorString(e));
-            return HB_OK;
-        }
-        hipError_t e = kp == 1 ? launch_chain_persist<1>(c, cv, pv, st) : kp == 3 ? launch_chain_persist<3>(c, cv, pv, st)
-                                                                                 : launch_chain_persist<7>(c, cv, pv, st);
-        if (e != hipSuccess) return hb_fail(HB_ERR_HIP, std::string("k_chain_persist launch: ") + hipGetErrorString(e));
+            what = "k_chain_dense";
+            hipLaunchKernelGGL(dense_chain_kernel(model == 5), dim3(1), dim3(512), persist_smem(c->P), st, c->d_in, cv, pv, c->ddense, c->fcorr2);
+        } else if (group_chain) {
+            what = "k_chain_group";
+            const bool narrow = D <= 4 && Lv * D <= 8 && !(D <= 2 && Lv * D <= 4);
+            hipLaunchKernelGGL(group_chain_kernel(mix_model, shape, fwd, fwd2, wide8, cert && c->P == 512, narrow), dim3(1), dim3(c->P),
+                               persist_smem(c->P), st, c->d_in, cv, pv);
+        } else
+            hipLaunchKernelGGL(persist_chain_kernel(kp, pv.Lb, pv.fcorr != nullptr), dim3(1), dim3(c->P), persist_smem(c->P), st, c->d_in, cv, pv,
+                               persist_nslot(c->P, c->L, kp));
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return hb_fail(HB_ERR_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
         return HB_OK;
     };
-    bool fold_first = false;
-    const bool side_first = !alone && getenv("HB_SIDE_FIRST") && atoi(getenv("HB_SIDE_FIRST")) != 0; // (A/B: k_fwd and the warmers enqueued before the chain, as k_fold_dense is)
     if (alone) { // (the update rows poll the move counts themselves: "no moves" for every panel)
         HB_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->flags + HB_FLAG_CHAIN_DONE), 0x7ffffff0, 1, sA));
         HB_HIP(hipMemsetAsync(c->ev_count, 0, sizeof(int32_t) * (size_t)c->npanels * HB_EVS, sA));
@@ -817,69 +762,32 @@ static int enqueue_sweep_pipeline(hb_ctx *c, int model, int n_fold, int pb, int 
     else {
         // round 6: k_fold_dense is enqueued BEFORE the chain and the gate. Captured after them, the graph started it ~1 ms late — the dense chain waits for its
         // first far sums at sub-block 4 of the sweep's first panel, launch 2's update rows wait for the chain: 1 ms of every 18 ms sweep
-        // (tools/r6_long_launch.py, tools/r6_dense_start.py; HB_GATE=0 or HB_GRAPH=0 alone also removed it; HB_FOLD_FIRST=0: the old order)
-        fold_first = dense && !(getenv("HB_FOLD_FIRST") && atoi(getenv("HB_FOLD_FIRST")) == 0);
-        if (fold_first) {
+        // (tools/r6_long_launch.py, tools/r6_dense_start.py)
+        // (Lb + 1 target panels are open at any time: Lb ahead for their band, the chain's own for its far sub-blocks)
+        if (dense) {
             HB_HIP(hipStreamWaitEvent(c->s_upd, c->ev_fork, 0));
             hipLaunchKernelGGL(k_fold_dense, dim3(8 * (c->L + 1)), dim3(256), 0, c->s_upd, cv, pv, c->ddense, c->fcorr2, c->L + 1);
             HB_HIP(hipGetLastError());
         }
-        if (!side_first) {
-            if (int rc = launch_the_chain(sB)) return rc;
-            // (the first mat-vec launch starts when the chain is resident; HB_GATE=0 / 1 overrides: by default only where a launch's
-            // update blocks can sit on every compute unit)
-            bool gate = dense || overlap || mvp; // (overlap / persistent mat-vec: tiles from the first microsecond on, no compute unit left free for the chain's 160 KB of LDS)
-            if (const char *e = getenv("HB_GATE")) gate = atoi(e) != 0;
-            if (gate) hipLaunchKernelGGL(k_gate, dim3(1), dim3(64), 0, sA, c->flags);
-        }
+        if (int rc = launch_the_chain(sB)) return rc;
+        // (the first mat-vec launch starts when the chain is resident — where a launch's update blocks can sit on every compute unit)
+        if (dense) hipLaunchKernelGGL(k_gate, dim3(1), dim3(64), 0, sA, c->flags);
     }
-    // the L2 warmers (k_warm): a third branch of the graph, 4 workgroups per XCD of which only the chain's XCD's stay
-    int warm = 4;
-    if (const char *e = getenv("HB_WARM")) warm = std::max(0, std::min(16, atoi(e)));
-    if (alone || (group_chain && !c->warm_group) || fwd || dense || fwd_persist) warm = 0; // (k_fwd has the third stream)
-    // BayesR with k_fwd beside the chain: the warmers on a stream of their own (HB_WARM_R: workgroups per XCD, 0 = off). They read
-    // the Gram rows of EVERY marker on a panel's hot list, with or without a slot in the chain's row cache, and the rows their
-    // moves fold into the next panel (the chain's share of the band)
-    int warm_r = 0;
-    if (fwd_persist && c->s_warm) {
-        warm_r = 4;
-        if (const char *e = getenv("HB_WARM_R")) warm_r = std::max(0, std::min(16, atoi(e)));
-    }
-    // the wide group chain with k_fwd beside it (BayesB / BayesC, the headline): warmers on the same fourth stream — the listed markers' Gram rows
-    // for the chain's share of the band (its own group and the next: 2 D - 1 blocks) and the panels' exact per-marker data (HB_WARM_G: workgroups
-    // per XCD, 0 = off)
-    if (fwd && c->s_warm && warm_r == 0) {
-        warm_r = fwd2 ? 4 : c->warm_g; // (BayesR's two-panel groups, round 6: 92.1 sweeps/s without, 95.9 / 97.5 / 96.5 with 2 / 4 / 8 workgroups per XCD, profiles/r06_bayesr_conv_warm.txt; the wide BayesCpi shape: no effect, round 5)
-        if (const char *e = getenv("HB_WARM_G")) warm_r = std::max(0, std::min(16, atoi(e)));
-    }
-    if (dense && !fold_first) { // (Lb + 1 target panels are open at any time: Lb ahead for their band, the chain's own for its far sub-blocks)
-        HB_HIP(hipStreamWaitEvent(c->s_upd, c->ev_fork, 0));
-        hipLaunchKernelGGL(k_fold_dense, dim3(8 * (c->L + 1)), dim3(256), 0, c->s_upd, cv, pv, c->ddense, c->fcorr2, c->L + 1);
-        HB_HIP(hipGetLastError());
-    }
-    bool warm_dense = false;
-    if (dense) { // the chain's own Gram reads, into its XCD's L2 ahead of it (HB_WARM_DENSE=0: off; = workgroups per XCD)
-        int wd = 0; // (measured at n = 50k: 4.45-4.52 ms per 200 panels with 0, 2, 4, 8 or 16 workgroups per XCD, 2 or 4 panels ahead: no gain, off by default)
-        if (const char *e = getenv("HB_WARM_DENSE")) wd = std::max(0, std::min(16, atoi(e)));
-        if (wd > 0) {
-            int ahead = D + 1;
-            if (const char *e = getenv("HB_WARM_AHEAD")) ahead = std::max(1, atoi(e));
-            hipLaunchKernelGGL(k_warm_dense, dim3(8 * wd), dim3(256), 0, c->s_upd, cv, pv, wd, ahead, reinterpret_cast<int *>(c->flags + 48));
-            HB_HIP(hipGetLastError());
-            warm_dense = true;
-        }
-    }
-    if (fwd && !merged) {
+    // the L2 warmers (k_warm): a third branch of the graph, warm_per_xcd workgroups per XCD of which only the chain's XCD's stay; not beside
+    // the group chain and k_fwd, which has the third stream
+    constexpr int warm_per_xcd = 4;
+    const int warm = (alone || group_chain || dense || fwd_persist) ? 0 : warm_per_xcd;
+    // BayesR with k_fwd beside the chain: the warmers on a stream of their own. They read the Gram rows of EVERY marker on a
+    // panel's hot list, with or without a slot in the chain's row cache, and the rows their moves fold into the next panel (the chain's share of the band).
+    // The same beside BayesR's two-panel group chain with k_fwd: the listed markers' Gram rows for the chain's share of the band (its own group and the
+    // next: 2 D - 1 blocks) and the panels' exact per-marker data (round 6: 92.1 sweeps/s without, 95.9 / 97.5 / 96.5 with 2 / 4 / 8 workgroups per XCD,
+    // profiles/r06_bayesr_conv_warm.txt; beside the wide BayesCpi shape: no effect, round 5)
+    const int warm_r = ((fwd_persist || fwd2) && c->s_warm) ? warm_per_xcd : 0;
+    if (fwd) {
         HB_HIP(hipStreamWaitEvent(c->s_upd, c->ev_fork, 0));
         if (fwd2) hipLaunchKernelGGL((k_fwd<2, 1, 16>), dim3(1), dim3(c->P), 0, c->s_upd, cv, pv);
-#if HB_WITH_MVP
-        else if (mvp && Lv == 2) hipLaunchKernelGGL((k_fwd<7, 1, 8, false, true>), dim3(1), dim3(c->P), 0, c->s_upd, cv, pv);
-        else if (mvp) hipLaunchKernelGGL((k_fwd<7, 2, 4, false, true>), dim3(1), dim3(c->P), 0, c->s_upd, cv, pv);
-#endif
         else if (wide8) hipLaunchKernelGGL((k_fwd<8, 1, 8>), dim3(1), dim3(c->P), 0, c->s_upd, cv, pv);
-        else if (Lv == 2 && g16) hipLaunchKernelGGL((k_fwd<7, 1, 8, true>), dim3(1), dim3(c->P), 0, c->s_upd, cv, pv);
         else if (Lv == 2) hipLaunchKernelGGL((k_fwd<7, 1, 8>), dim3(1), dim3(c->P), 0, c->s_upd, cv, pv);
-        else if (g16) hipLaunchKernelGGL((k_fwd<7, 2, 4, true>), dim3(1), dim3(c->P), 0, c->s_upd, cv, pv);
         else hipLaunchKernelGGL((k_fwd<7, 2, 4>), dim3(1), dim3(c->P), 0, c->s_upd, cv, pv);
         HB_HIP(hipGetLastError());
     }
@@ -891,25 +799,17 @@ static int enqueue_sweep_pipeline(hb_ctx *c, int model, int n_fold, int pb, int 
     }
     if (warm) {
         HB_HIP(hipStreamWaitEvent(c->s_upd, c->ev_fork, 0));
-        int ahead = D + 4;
-        if (const char *e = getenv("HB_WARM_AHEAD")) ahead = std::max(1, atoi(e));
+        const int ahead = D + 4; // (panels ahead of chain_done)
         hipLaunchKernelGGL(k_warm, dim3(8 * warm), dim3(256), 0, c->s_upd, pv, cv, kp, c->gram, c->P, ahead, warm, reinterpret_cast<int *>(c->flags + 48));
         HB_HIP(hipGetLastError());
     }
     if (warm_r) {
         HB_HIP(hipStreamWaitEvent(c->s_warm, c->ev_fork, 0));
-        int ahead = fwd ? 2 * D : 2; // (measured, BayesR at n = 50k, m = 500k: off 48.3 sweeps/s, 2 panels ahead 51.2, 4 ahead 50.5, 8 ahead 50.0)
-        if (const char *e = getenv("HB_WARM_AHEAD")) ahead = std::max(1, atoi(e));
+        const int ahead = fwd ? 2 * D : 2; // (measured, BayesR at n = 50k, m = 500k: off 48.3 sweeps/s, 2 panels ahead 51.2, 4 ahead 50.5, 8 ahead 50.0)
         persist_view pw = pv;
         pw.Lb = fwd ? 2 * D - 1 : 1; // (BayesR: the chain folds into the next panel only; the group chain: into its own group's later panels and the next group's)
         hipLaunchKernelGGL(k_warm, dim3(8 * warm_r), dim3(256), 0, c->s_warm, pw, cv, kp, c->gram, c->P, ahead, warm_r, reinterpret_cast<int *>(c->flags + 48));
         HB_HIP(hipGetLastError());
-    }
-    if (side_first) {
-        if (int rc = launch_the_chain(sB)) return rc;
-        bool gate = dense || overlap || mvp;
-        if (const char *e = getenv("HB_GATE")) gate = atoi(e) != 0;
-        if (gate) hipLaunchKernelGGL(k_gate, dim3(1), dim3(64), 0, sA, c->flags);
     }
     const bool inject = c->inject_abort_panel >= 0 && c->s_dbg && !alone;
     if (inject) { // (debug hook: a fourth branch that aborts the sweep in mid-flight)
@@ -918,96 +818,12 @@ static int enqueue_sweep_pipeline(hb_ctx *c, int model, int n_fold, int pb, int 
         HB_HIP(hipGetLastError());
     }
     const int upd_blocks = (int)((c->ld / 4 + 255) / 256);
-    // ---- Round 6: the OVERLAPPED launch stream (HB_OVERLAP=1). A 3 584-column launch lives 12 us of which its tiles run 9: the rest is the ramp of a
-    // kernel that is too small for the chip, plus 1.6 us of dependent-dispatch gap — and two such launches in flight stream 21 % more
-    // (9.6 against 12.2 us per launch isolated, tools/matvec_only.py with HB_TM_STREAMS=2; the int8 launches reach the measured read ceiling, 6.1 TB/s).
-    // What ties launch g to launch g - 1 is only what RIDES in it — the update rows that write the residual version the next launch reads, and the finalize
-    // rows of the previous launch's sums. Here both are kernels of their own: the mat-vec launches (tiles only) alternate between two streams, the residual
-    // updates u(h) follow each other on a third (each still polls the chain's counts for its group on the device), the finalize kernels f(g) on a
-    // fourth; t(g) waits for u(g - Lv - 1) — the version it reads — and f(g) for t(g): graph edges, no new device-side hand-off, no coherence question.
-    // The residual versions live in a ring of Lv + 1 slots: while t(g) reads version g - Lv - 1 the chain has closed group g - 1 at most, so the
-    // youngest version written is g - 1; u(g), which overwrites the slot t(g) reads, needs chain_done(g), i.e. the sums of t(g). Same integers, same
-    // chain: the band, the correction ring and k_fwd see the geometry they always saw. ----
-    if (overlap) {
-        const int NBr = Lv + 1;
-        auto slotn = [&](int v) { return v < 0 ? 0 : (v + 1) % NBr; };
-        // (the second tile stream starts behind the gate / the sweep's start like the first: an event on sA here)
-        HB_HIP(hipEventRecord(c->ev_chain[2 % c->npanels], sA));
-        HB_HIP(hipStreamWaitEvent(c->s_t2, c->ev_chain[2 % c->npanels], 0));
-        HB_HIP(hipStreamWaitEvent(c->s_uk, c->ev_fork, 0));
-        for (int g = 0; g < ngroups; g++) {
-            const int ga = g0 + g, p0 = ga * D, p1 = std::min(np, p0 + D);
-            hipStream_t st = (g & 1) ? c->s_t2 : sA;
-            const int v = g - Lv - 1; // the residual version the tiles read
-            if (v >= 0) HB_HIP(hipStreamWaitEvent(st, c->ev_ou[v], 0));
-            launch_dot(c, p0 * c->P, (p1 - p0) * c->P, slotn(v), st, true, nullptr, 0, 0, ga);
-            // (the finalize kernel follows its tiles in their stream: one edge per group — u(v) -> t(v + Lv + 1) — is all the graph holds besides its three
-            // chains; with an event per tile launch, finalize and update the executor's traversal of the captured graph did not return)
-            launch_dotq_fin(c, p0 * c->P, (p1 - p0) * c->P, ga, c->dsum + (size_t)p0 * c->P, st);
-            upd_view uq = make_upd(c, p0, p1, slotn(g - 1), slotn(g), c->flags, ga);
-            hipLaunchKernelGGL(k_update, dim3(upd_blocks), dim3(256), 0, c->s_uk, c->ld, uq);
-            HB_HIP(hipEventRecord(c->ev_ou[g], c->s_uk));
-        }
-        // join: everything back into sA
-        HB_HIP(hipEventRecord(c->ev_ot[0], c->s_t2));
-        HB_HIP(hipStreamWaitEvent(sA, c->ev_ot[0], 0));
-        HB_HIP(hipStreamWaitEvent(sA, c->ev_ou[ngroups - 1], 0));
-    }
-#if HB_WITH_MVP
-    if (mvp) {
-        const int ncols = D * c->P, nst = (int)(c->ld / 512), ncg = ncols / 64, nupd_blk = (int)(c->ld / 256);
-        // tiles per group: as a k_dotq2m launch sizes them (launch_dotq2) — all workgroups of the kernel resident at once
-        int ns = std::max(1, std::min(std::max(1, nst / 4), (int)(900.0 / ncg + 0.5)));
-        const int ns_min = std::max(1, (int)(((int64_t)nst * 512 + 131071) / 131072));
-        ns = std::max(ns, ns_min);
-        {
-            const int lds = q2m512_lds<false>(), per_cu = std::max(1, std::min(8, (160 * 1024) / std::max(1, lds))), cus_per_xcd = std::max(1, c->num_cus / 8);
-            const int budget = 8 * (cus_per_xcd * per_cu - (per_cu + 3));
-            auto total = [&](int k) { const int NSk = (nst + k - 1) / k; return nupd_blk + ncg * ((nst + NSk - 1) / NSk); };
-            while (ns > ns_min && total(ns) > budget) ns--;
-        }
-        const int NS = (nst + ns - 1) / ns, nsplit = (nst + NS - 1) / NS;
-        mvp_view mv{};
-        mv.v0.X = nullptr;
-        mv.v0.X2 = reinterpret_cast<const uint8_t *>(c->X2) + (int64_t)(g0 * D) * c->P * c->ld2;
-        mv.v0.ld2 = c->ld2;
-        mv.v0.ld = c->ld;
-        mv.v0.gexp_out = c->gexp + g0;
-        mv.v0.accq = c->accq + (int64_t)(g0 * D) * c->P;
-        mv.v0.accstride = c->m_pad;
-        mv.v0.nstages = nst;
-        mv.v0.NS = NS;
-        mv.v0.ncg = ncg;
-        mv.u0 = make_upd(c, 0, 0, 0, 0, c->flags, 0);
-        auto envi = [](const char *k, int d) { const char *e = getenv(k); return e ? atoi(e) : d; };
-        mv.ufresh = std::max(1, envi("HB_MVP_UFRESH", 4));
-        mv.usleep = std::max(0, envi("HB_MVP_USLEEP", 0));
-        mv.tfresh = std::max(1, envi("HB_MVP_TFRESH", 4));
-        mv.tsleep = std::max(0, envi("HB_MVP_TSLEEP", 0));
-        mv.ngroups = ngroups; mv.D = D; mv.np = np; mv.g0 = g0; mv.Lv = Lv;
-        mv.ntile = ncg * nsplit; mv.nupd = nupd_blk; mv.nsplit = nsplit;
-        mv.rqv = c->rq; mv.vexpv = c->vexp; mv.r = c->r; mv.mb = c->mb; mv.r32 = c->r32; mv.dsum = c->dsum;
-        mv.ho = c->mvp_ho; mv.flags = c->flags;
-        mv.rel = c->mvp_ho + ((size_t)(c->npanels + 2) * 65); // (behind the counters: 64 lines)
-        mv.stamp = nullptr;
-        const int nblk = mv.nupd + mv.ntile;
-        if (c->lstamp && nblk <= HB_LSTAMP_BLOCKS) {
-            mv.stamp = c->lstamp;
-            for (int g = 0; g < ngroups; g++) { c->lstamp_nblk[g0 + g] = nblk; c->lstamp_cols[g0 + g] = (std::min(np, (g0 + g + 1) * D) - (g0 + g) * D) * c->P; }
-        }
-        HB_HIP(hipMemsetAsync(c->mvp_ho, 0, sizeof(unsigned) * ((size_t)(ngroups + 1) + (size_t)ngroups * 64), sA));
-        HB_HIP(hipMemsetAsync(mv.rel, 0, sizeof(unsigned) * 64 * 32, sA));
-        if (c->q2m_sc) hipLaunchKernelGGL((k_mvp2<true>), dim3(nblk), dim3(64), q2m512_lds<false>(), sA, mv);
-        else hipLaunchKernelGGL((k_mvp2<false>), dim3(nblk), dim3(64), q2m512_lds<false>(), sA, mv);
-        HB_HIP(hipGetLastError());
-    }
-#endif
     // Residual versions advance per mat-vec group: version h = every panel of groups <= h applied. Mat-vec launch g
     // reads version g - Lv - 1 and, in one extra grid row, carries update(h = g - Lv): version h-1 -> h, which the
     // NEXT launch reads. Two buffers ping-pong (slot = (version + 1) & 1). No third stream, no cross-stream events.
     auto slot2 = [](int v) { return v < 0 ? 0 : ((v + 1) & 1); };
     // (g, h: group indices within the range — they drive the version slots; ga, ha: the absolute ones — they address panels)
-    for (int g = 0; g < ngroups && !overlap && !mvp; g++) {
+    for (int g = 0; g < ngroups; g++) {
         const int ga = g0 + g;
         const int p0 = ga * D, p1 = std::min(np, p0 + D);
         const int h = g - Lv, ha = g0 + h;
@@ -1026,10 +842,10 @@ static int enqueue_sweep_pipeline(hb_ctx *c, int model, int n_fold, int pb, int 
         launch_dot(c, p0 * c->P, (p1 - p0) * c->P, slot2(g - Lv - 1), sA, true, ride ? &uq : nullptr,
                    g > 0 ? (ga - 1) * D * c->P : 0, g > 0 ? D * c->P : 0, ga);
     }
-    if (!overlap && !mvp) launch_reduce(c, (g0 + ngroups - 1) * D * c->P, last_panels * c->P, sA, g0 + ngroups - 1);
+    launch_reduce(c, (g0 + ngroups - 1) * D * c->P, last_panels * c->P, sA, g0 + ngroups - 1);
     if (alone)
         if (int rc = launch_the_chain(sA)) return rc;
-    for (int h = std::max(0, ngroups - Lv); h < ngroups && !overlap && !mvp; h++) { // the updates that had no later mat-vec to ride on
+    for (int h = std::max(0, ngroups - Lv); h < ngroups; h++) { // the updates that had no later mat-vec to ride on
         upd_view uq = make_upd(c, (g0 + h) * D, std::min(np, (g0 + h) * D + D), slot2(h - 1), slot2(h), c->flags, g0 + h);
         if (dense_upd && c->layout == 8 && D <= 2) {
             uq.dense = 1;
@@ -1038,7 +854,7 @@ static int enqueue_sweep_pipeline(hb_ctx *c, int model, int n_fold, int pb, int 
     }
     HB_HIP(hipEventRecord(c->ev_chain[0], sB));
     HB_HIP(hipStreamWaitEvent(sA, c->ev_chain[0], 0));
-    if (warm || (fwd && !merged) || dense || warm_dense || fwd_persist) {
+    if (warm || fwd || dense || fwd_persist) {
         HB_HIP(hipEventRecord(c->ev_upd[0], c->s_upd));
         HB_HIP(hipStreamWaitEvent(sA, c->ev_upd[0], 0));
     }
@@ -1050,7 +866,7 @@ static int enqueue_sweep_pipeline(hb_ctx *c, int model, int n_fold, int pb, int 
         HB_HIP(hipEventRecord(c->ev_dot[0], c->s_dbg));
         HB_HIP(hipStreamWaitEvent(sA, c->ev_dot[0], 0));
     }
-    const int sfin = overlap ? ((ngroups - 1 + 1) % (Lv + 1)) : slot2(ngroups - 1);
+    const int sfin = slot2(ngroups - 1);
     if (sfin != 0) {
         HB_HIP(hipMemcpyAsync(c->r, c->r + (size_t)sfin * c->ld, sizeof(double) * c->ld, hipMemcpyDeviceToDevice, sA));
         HB_HIP(hipMemcpyAsync(c->r32, c->r32 + (size_t)sfin * c->ld, sizeof(float) * c->ld, hipMemcpyDeviceToDevice, sA));
@@ -1065,56 +881,17 @@ static int enqueue_sweep_pipeline(hb_ctx *c, int model, int n_fold, int pb, int 
     return HB_OK;
 }
 
-// streams and events of the overlapped launch stream: created OUTSIDE any capture
-static int overlap_resources(hb_ctx *c)
-{
-    auto mk = [&](hipStream_t *st) { return *st ? hipSuccess : hipStreamCreateWithFlags(st, hipStreamNonBlocking); };
-    HB_HIP(mk(&c->s_t2));
-    HB_HIP(mk(&c->s_uk));
-    HB_HIP(mk(&c->s_fk));
-    const int need = c->npanels + 1;
-    while ((int)c->ev_ot.size() < need) { hipEvent_t e; HB_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); c->ev_ot.push_back(e); }
-    while ((int)c->ev_ou.size() < need) { hipEvent_t e; HB_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); c->ev_ou.push_back(e); }
-    return HB_OK;
-}
-
-// the persistent mat-vec's buffers (outside any capture): digit planes and exponents for every residual version of a sweep, the hand-over counters
-static int mvp_resources(hb_ctx *c)
-{
-    const int need = c->npanels + 2;
-    if (c->rq_slots < need) {
-        HB_HIP(hipStreamSynchronize(c->stream));
-        int8_t *rq = nullptr;
-        int *vexp = nullptr;
-        HB_HIP(hipMalloc(reinterpret_cast<void **>(&rq), (size_t)c->ld * HB_ND * need));
-        HB_HIP(hipMalloc(reinterpret_cast<void **>(&vexp), sizeof(int) * need));
-        HB_HIP(hipMemset(rq, 0, (size_t)c->ld * HB_ND * need));
-        HB_HIP(hipMemset(vexp, 0, sizeof(int) * need));
-        (void)hipFree(c->rq);
-        (void)hipFree(c->vexp);
-        c->rq = rq;
-        c->vexp = vexp;
-        c->rq_slots = need;
-        c->graph_model = -1; // (the captured sweeps hold the old pointers)
-    }
-    if (!c->mvp_ho) HB_HIP(hipMalloc(reinterpret_cast<void **>(&c->mvp_ho), sizeof(unsigned) * ((size_t)(c->npanels + 2) * 65 + 64 * 32)));
-    return HB_OK;
-}
-
 int hb_sweep_enqueue(hb_ctx *c, const hb_sweep_in *in, bool timed)
 {
     if (int rc = hbk_set_timeout(c)) return rc;
-    if (c->mvp && c->pipeline && c->precise == 2 && c->layout == 2 && (c->rq_slots < c->npanels + 2 || !c->mvp_ho))
-        if (int rc = mvp_resources(c)) return rc;
-    if (c->overlap && c->pipeline && !c->s_fk)
-        if (int rc = overlap_resources(c)) return rc;
     *c->h_in = *in;
     HB_HIP(hipMemcpyAsync(c->d_in, c->h_in, sizeof(hb_sweep_in), hipMemcpyHostToDevice, c->stream));
     if (timed || c->row_reduce) return enqueue_sweep_kernels(c, in->model_index, in->n_fold, true); // (row-sharded mode: host round trips inside the sweep)
     const int pb = c->rng_pe ? c->rng_pb : 0, pe = c->rng_pe ? c->rng_pe : c->npanels;
     const bool first = c->rng_pe ? c->rng_first : true, last = c->rng_pe ? c->rng_last : true;
+    const bool env_alone = getenv("HB_CHAIN_ALONE") != nullptr; // (tools/chain_timeline.py sets it in the middle of a run)
     auto enqueue = [&]() {
-        return c->pipeline ? enqueue_sweep_pipeline(c, in->model_index, in->n_fold, pb, pe, first, last)
+        return c->pipeline ? enqueue_sweep_pipeline(c, in->model_index, in->n_fold, pb, pe, first, last, env_alone)
                            : enqueue_sweep_kernels(c, in->model_index, in->n_fold, false);
     };
     if (c->inject_abort_panel >= 0 && c->pipeline) { // (debug hook: such a sweep is launched directly, never from a cached graph)
@@ -1444,21 +1221,10 @@ int hbk_time_matvec(hb_ctx *c, int D, int reps, int as_pipeline, double *avg_us,
     hipGraph_t g = nullptr;
     hipGraphExec_t ge = nullptr;
     HB_HIP(hipStreamBeginCapture(c->stream, hipStreamCaptureModeRelaxed));
-    // (round 6, timing experiment only — HB_TM_STREAMS=2: the launches alternate between two streams with nothing between them, i.e. two launches in flight:
-    // what an overlapped launch stream could reach; the sums are not meaningful then)
-    const int nstreams = getenv("HB_TM_STREAMS") ? std::max(1, std::min(2, atoi(getenv("HB_TM_STREAMS")))) : 1;
-    if (nstreams == 2) {
-        HB_HIP(hipEventRecord(c->ev_fork, c->stream));
-        HB_HIP(hipStreamWaitEvent(c->s_upd, c->ev_fork, 0));
-    }
     for (int gi = 0; gi < ngroups; gi++) {
         const int p0 = gi * D, p1 = std::min(c->npanels, p0 + D);
-        launch_dot(c, p0 * c->P, (p1 - p0) * c->P, 0, (nstreams == 2 && (gi & 1)) ? c->s_upd : c->stream, as_pipeline != 0, nullptr,
+        launch_dot(c, p0 * c->P, (p1 - p0) * c->P, 0, c->stream, as_pipeline != 0, nullptr,
                    gi > 0 ? (gi - 1) * D * c->P : 0, gi > 0 ? D * c->P : 0, gi);
-    }
-    if (nstreams == 2) {
-        HB_HIP(hipEventRecord(c->ev_upd[0], c->s_upd));
-        HB_HIP(hipStreamWaitEvent(c->stream, c->ev_upd[0], 0));
     }
     if (as_pipeline) launch_reduce(c, (ngroups - 1) * D * c->P, (c->npanels - (ngroups - 1) * D) * c->P, c->stream, ngroups - 1);
     HB_HIP(hipStreamEndCapture(c->stream, &g));

@@ -445,21 +445,18 @@ def test_continued_chain_is_the_oracles_continued_chain(big, model, Pi, fold):
         assert abs(int((r2["MCMCsamples"]["alpha"][:, 0] != 0).sum()) - nnz1) < max(20, nnz1)
 
 
-@pytest.mark.parametrize("knob,values", [("HB_CERT", ("0", "1")), ("HB_GRAM16", ("0", "1"))])
+@pytest.mark.parametrize("knob,values", [("HB_CERT", ("0", "1"))])
 def test_certified_check_and_compact_band_are_the_plain_group_chain(big, monkeypatch, knob, values):
-    """Two round-5 variants of k_chain_group at (3, 7) must change NOTHING in the results:
+    """A round-5 variant of k_chain_group at (3, 7) must change NOTHING in the results:
     HB_CERT (on by default): the violation check of a round from the rank-one part of the moves, G[k][j] = ga[k] gB[j] + c[k][j], and the bound
     |c[k][j]| <= gcmax[k] — passed-over markers proven to stay cost no Gram rows, proven crossers join the candidates before anything is fetched,
-    the undecided ones send the round through the full fold and the exact check; HB_GRAM16 (off by default): a move's rows fetched from the band
-    stored as int16 residuals and rebuilt exactly. A cold start with the geometry switch, and a dense start (5 % of the markers in the model:
+    the undecided ones send the round through the full fold and the exact check. A cold start with the geometry switch, and a dense start (5 % of the markers in the model:
     rounds that do not reach the group's end, roll-backs); and the oracle's draw for draw."""
     X, y = big["X"], big["y"]
     m = X.shape[1]
     rng = np.random.default_rng(12)
     g0 = np.where(rng.random(m) < 0.05, rng.normal(0, 0.03, m), 0.0)
     out = []
-    if knob == "HB_GRAM16":
-        monkeypatch.setenv("HB_CERT", "0")   # (the compact band is read by the plain path: compare like with like)
     for on in values:
         monkeypatch.setenv(knob, on)
         res = []
