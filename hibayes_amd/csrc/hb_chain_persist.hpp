@@ -24,7 +24,7 @@ struct persist_view {
     const int4 *opn;                     // k_chain_group, certified shape: the staged opening's records (hb_ctx.opn); null: the opening loads and computes its own
 };
 
-#define HB_LBMAX 20
+// (HB_LBMAX, the band this chain folds into: hb_plan.hpp)
 #ifndef HB_APPLY_PREFIX
 #define HB_APPLY_PREFIX 1 /* a wave applies only the prefix of a round's moves that can touch it */
 #endif

@@ -1,5 +1,6 @@
 // hb_ctx.hip — device context of one genotype shard and the fine-grained C ABI on top of it.
 #include "hb_internal.hpp"
+#include "hb_plan.hpp"
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -78,9 +79,7 @@ static void hb_pipeline_geometry(hb_ctx *c)
     c->Lv = std::max(0, std::min(6, c->Lv));
     c->D = c->pipeline ? std::max(1, std::min(8, c->D)) : 1;
     // Lv counts mat-vec GROUPS of look-ahead; the Gram band then spans (Lv + 1) * D - 1 earlier panels
-    // (20 = HB_LBMAX in hb_kernels.hip, what k_chain_persist folds; 27 with k_fwd beside the group chain — three groups of seven
-    // panels of look-ahead — which the sweep refuses for the models that run k_chain_persist)
-    const int lbmax = (c->P == 512 && ((c->Lv == 3 && c->D == 7) || (c->Lv == 2 && c->D == 8))) ? 27 : 20; // ((2, 8): 23, round 6)
+    const int lbmax = plan_band_limit(c->P, c->Lv, c->D);
     while ((c->Lv + 1) * c->D - 1 > lbmax) {
         if (c->Lv > 1) c->Lv--; else c->D--;
     }
@@ -168,7 +167,8 @@ int hb_ctx_create(const hb_ctx_params *p, hb_ctx **out)
     if (const char *e = getenv("HB_DOTGROUP")) c->D = atoi(e);
     if (const char *e = getenv("HB_GRAPH")) c->use_graph = atoi(e) != 0;
     if (const char *e = getenv("HB_DOTQ2_CPL")) c->dotq2_cpl = atoi(e) == 1 ? 1 : 2;
-    if (const char *e = getenv("HB_DOTQ2_TILES")) c->dotq2_tiles = std::max(1, atoi(e));
+    if (const char *e = getenv("HB_DOTQ_TILES")) c->dotq_tiles = std::max(1, atoi(e));
+    if (const char *e = getenv("HB_DOTQ2_TILES")) { c->dotq2_tiles = std::max(1, atoi(e)); c->dotq2_tiles_set = true; }
     if (const char *e = getenv("HB_DOTQ2_KIND")) c->dotq2_kind = std::max(0, std::min(2, atoi(e)));
     if (const char *e = getenv("HB_CERT")) c->gcert_on = atoi(e) != 0;
     if (const char *e = getenv("HB_Q2M_CT")) c->q2m_ct = atoi(e) >= 16 ? 16 : atoi(e) >= 8 ? 8 : 4;

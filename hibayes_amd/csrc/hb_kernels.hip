@@ -25,8 +25,10 @@
 //                    hb_reduce.hpp         var(u), yadj.yadj, BayesL's variances, GWAS windows
 //   ingest / egress  hb_stats.hpp          xpx, vx                              hb_ingest.hpp  f64 check, .bed decode, X alpha, GEBV, generator
 //   summary level    hb_sbayes.hpp         SBayesD on a dense LD matrix
-//   this file        sweep start (k_sweep_init, k_quant0), the launchers, graph capture, probes, thin wrappers for hb_ctx.hip
+//   host plan        hb_plan.hpp           which chain, k_fwd and warmers a sweep runs (plan_sweep: no HIP, tested on the CPU)
+//   this file        sweep start (k_sweep_init, k_quant0), the launch tables, the launchers, graph capture, probes, thin wrappers for hb_ctx.hip
 #include "hb_internal.hpp"
+#include "hb_plan.hpp"
 #include "hb_rng.hpp"
 #include <type_traits>
 #include <algorithm>
@@ -41,9 +43,6 @@
 #include "hb_update.hpp"
 #include "hb_matvec.hpp"
 #include "hb_dotq2.hpp"
-#ifndef HB_W8_CH
-#define HB_W8_CH 3 /* moves per trip of the eight-panel group chain (4 spills nine registers, 3 four) */
-#endif
 
 // Sweep start of the fixed-point path: max |yadj| -> mb[0] and the exponent of slot 0, then slot 0's digit planes.
 // One workgroup (n is a few hundred KB).
@@ -145,13 +144,6 @@ __global__ __launch_bounds__(256) void k_update(int64_t ld, upd_view q)
 // =============================================================================================
 // host side: launchers
 // =============================================================================================
-static inline int kpad_for(int model, int n_fold)
-{
-    if (model != 6) return 1;
-    const int k1 = n_fold - 1;
-    return k1 <= 1 ? 1 : (k1 <= 3 ? 3 : 7);
-}
-
 // LDS budget of k_chain: as many Gram rows as fit beside the event lists
 static int chain_nslot(int P) { return (int)((158 * 1024 - ((size_t)P * 16 + 128 + 128 + 64)) / ((size_t)P * 4)); }
 #define HB_PERSIST_RING(P) ((size_t)4 * ((((size_t)12 * (P) + 1023) >> 10 << 10) + 1024)) /* HB_RD slots of the opening ring */
@@ -163,56 +155,39 @@ static int persist_nslot(int P, int Lb, int K1) { return std::min(P, std::min(25
 static size_t persist_smem(int) { return (size_t)160 * 1024; }
 static size_t chain_smem(int P) { return (size_t)chain_nslot(P) * P * 4 + (size_t)P * 16 + 128 + 128 + 64; }
 
-// The chain kernels that ask for the whole 160 KiB of LDS, picked by the three functions below. They are the one list of these
-// instantiations: hbk_init_attrs raises the LDS limit of every kernel they can return.
-using persist_chain_fn = void (*)(const hb_sweep_in *, chain_view, persist_view, int);
-using group_chain_fn = void (*)(const hb_sweep_in *, chain_view, persist_view);
-using dense_chain_fn = void (*)(const hb_sweep_in *, chain_view, persist_view, double *, const double *);
+// The launch tables: a sweep plan's template arguments (plan_sweep, hb_plan.hpp) -> the instantiation, one table per kernel family, expanded
+// from the plan's own lists. The three chain tables are also the list of the kernels that ask for the whole 160 KiB of LDS (hbk_init_attrs).
+template <int N, class... Params>
+struct kernel_entry {
+    int arg[N];             // template arguments
+    void (*fn)(Params...);  // the kernel
+    int lds;                // (the mat-vec table: dynamic LDS of the shape)
+};
+#define HB_GROUP_ENTRY(K1, DM, FW, CH, CERT) {{K1, DM, FW, CH, CERT}, k_chain_group<K1, DM, FW, CH, (CERT) != 0>},
+#define HB_PERSIST_ENTRY(K1, NPL) {{K1, NPL}, k_chain_persist<K1, NPL>},
+#define HB_DENSE_ENTRY(LASSO) {{LASSO}, k_chain_dense<(LASSO) != 0>},
+#define HB_FWD_ENTRY(D, G, CH) {{D, G, CH}, k_fwd<D, G, CH>},
+static const kernel_entry<5, const hb_sweep_in *, chain_view, persist_view> group_chains[] = {HB_GROUP_KERNELS(HB_GROUP_ENTRY)};
+static const kernel_entry<2, const hb_sweep_in *, chain_view, persist_view, int> persist_chains[] = {HB_PERSIST_KERNELS(HB_PERSIST_ENTRY)};
+static const kernel_entry<1, const hb_sweep_in *, chain_view, persist_view, double *, const double *> dense_chains[] = {HB_DENSE_KERNELS(HB_DENSE_ENTRY)};
+static const kernel_entry<3, chain_view, persist_view> fwd_kernels[] = {HB_FWD_KERNELS(HB_FWD_ENTRY)};
 
-// k_chain_persist: candidate rows ahead (NPL == Lb) for the band widths of the default geometries; any other band goes without
-static persist_chain_fn persist_chain_kernel(int kp, int Lb, bool fcorr)
+// null, and the error recorded: the caller names a kernel that was never built — a programming error, never a reason to run another instantiation
+template <class E, size_t M>
+static const E *find_kernel(const E (&tab)[M], const int *arg, const char *what)
 {
-    if (kp == 1) {
-        if (Lb == 20) return k_chain_persist<1, 20>; // (Lv, D) = (2, 7)
-        if (Lb == 17) return k_chain_persist<1, 17>; // (Lv, D) = (2, 6)
-        if (Lb == 1) return k_chain_persist<1, 1>;
-        return k_chain_persist<1, 0>;
-    }
-    const bool npl2 = Lb == 2 && !fcorr; // (with k_fwd beside it the chain requests its fold rows itself, after the rounds)
-    if (kp == 3) return npl2 ? k_chain_persist<3, 2> : k_chain_persist<3, 0>;
-    return npl2 ? k_chain_persist<7, 2> : k_chain_persist<7, 0>;
+    for (const E &e : tab)
+        if (std::equal(std::begin(e.arg), std::end(e.arg), arg)) return &e;
+    hb_fail(HB_ERR_INVALID, std::string(what) + ": template arguments that are in no launch table");
+    return nullptr;
 }
-
-// k_chain_group: mix = BayesR with up to four classes, else BayesB / BayesC; shape 0 / 1 / 2 (enqueue_sweep_pipeline); fwd: k_fwd beside it,
-// fwd2 / wide8 its (2, 2) BayesR and (2, 8) forms; cert: the certified violation check at panel 512; narrow: three or four panels per launch
-static group_chain_fn group_chain_kernel(bool mix, int shape, bool fwd, bool fwd2, bool wide8, bool cert, bool narrow)
-{
-    if (mix) {
-        if (fwd2) return k_chain_group<3, 2, 2, 15, true>;
-        if (fwd) return cert ? k_chain_group<3, 8, 7, 4, true> : k_chain_group<3, 8, 7, 4>;
-        if (cert && narrow) return k_chain_group<3, 4, 8, 5, true>;
-        if (shape == 0) return k_chain_group<3, 8, 14, 3>;
-        return cert ? k_chain_group<3, 2, 4, 10, true> : k_chain_group<3, 2, 4, 10>; // (shape 1: D = 2)
-    }
-    if (wide8) return k_chain_group<1, 8, 8, HB_W8_CH, true>;
-    if (fwd) return cert ? k_chain_group<1, 8, 7, 4, true> : k_chain_group<1, 8, 7, 4>;
-    if (shape == 0) return k_chain_group<1, 8, 14, 3>;
-    if (shape == 1) return k_chain_group<1, 2, 4, 10>;
-    return k_chain_group<1, 1, 2, 20>;
-}
-
-static dense_chain_fn dense_chain_kernel(bool bayesl) { return bayesl ? k_chain_dense<true> : k_chain_dense<false>; }
 
 int hbk_init_attrs()
 {
     auto lds160 = [](const void *k) { return hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); };
-    for (int kp : {1, 3, 7})
-        for (int Lb = 0; Lb <= HB_LBMAX; Lb++)
-            for (bool fc : {false, true}) HB_HIP(lds160(reinterpret_cast<const void *>(persist_chain_kernel(kp, Lb, fc))));
-    for (int bits = 0; bits < 64; bits++)
-        for (int shape = 0; shape < 3; shape++)
-            HB_HIP(lds160(reinterpret_cast<const void *>(group_chain_kernel(bits & 1, shape, bits & 2, bits & 4, bits & 8, bits & 16, bits & 32))));
-    for (bool bayesl : {false, true}) HB_HIP(lds160(reinterpret_cast<const void *>(dense_chain_kernel(bayesl))));
+    for (auto &e : persist_chains) HB_HIP(lds160(reinterpret_cast<const void *>(e.fn)));
+    for (auto &e : group_chains) HB_HIP(lds160(reinterpret_cast<const void *>(e.fn)));
+    for (auto &e : dense_chains) HB_HIP(lds160(reinterpret_cast<const void *>(e.fn)));
     HB_HIP(lds160(reinterpret_cast<const void *>(&k_chain<1>)));
     HB_HIP(lds160(reinterpret_cast<const void *>(&k_chain<3>)));
     HB_HIP(lds160(reinterpret_cast<const void *>(&k_chain<7>)));
@@ -230,59 +205,67 @@ static hipError_t launch_chain(hb_ctx *c, const chain_view &cv, int p, hipStream
 // residual version v (moves of panels <= v applied; v = -1: start of the sweep) lives in slot (v+1) mod NB
 static inline int ver_slot(const hb_ctx *c, int v) { return (v + 1) % c->NB; }
 
-// tiles of one k_dotq launch: about three waves per compute unit, each a long run of stages (measured: fewer, longer
-// waves stream better than many short ones; tools/dotq_bench.hip)
-static void dotq_geometry(const hb_ctx *c, int ncols, int *ncg, int *NS, int *nsplit)
+// What every launch of the fixed-point mat-vec (k_dotq, k_dotq2, k_dotq2m, k_dotq2r) shares: the residual slot's digits and exponent, the plane sums,
+// the update and finalize rows that ride in the launch, the finalize window. The launcher adds X or X2, nstages, NS and ncg ...
+static dq_view dq_common(hb_ctx *c, int col0, int slot, int gidx, const upd_view &uq, int fin_col0, int fin_ncols, int fin_gidx)
 {
-    const int nst = (int)(c->ld / HBQ_RS);
-    *ncg = ncols / 64;
-    int target = 768;
-    if (const char *e = getenv("HB_DOTQ_TILES")) target = std::max(1, atoi(e));
-    int ns = std::max(1, std::min(nst, (int)((double)target / *ncg + 0.5)));
-    *NS = std::min(1024, (nst + ns - 1) / ns); // (int32 accumulators: NS * 128 rows * 127 * 128 < 2^31)
-    *nsplit = (nst + *NS - 1) / *NS;
+    dq_view v{};
+    v.ld = c->ld;
+    v.rq = c->rq + (size_t)slot * HB_ND * c->ld;
+    v.vexp_in = c->vexp + slot;
+    v.gexp_out = c->gexp + gidx;
+    v.accq = c->accq + col0;
+    v.accstride = c->m_pad;
+    v.nupd = (uq.p1 > uq.p0) ? (int)(c->ld / (uq.dense ? 64 : 256)) : 0;
+    v.nfin = fin_ncols > 0 ? (fin_ncols + 63) / 64 : 0;
+    v.fin_acc = c->accq + fin_col0;
+    v.fin_out = c->dsum + fin_col0;
+    v.fin_exp = c->gexp + fin_gidx;
+    v.fin_ncols = fin_ncols;
+    return v;
 }
 
-// the same launch on the 2-bit resident layout (hb_dotq2.hpp): about two long-lived waves per compute unit
-static void launch_dotq2(hb_ctx *c, int col0, int ncols, int slot, hipStream_t st, int gidx, const upd_view *upd, int fin_col0,
+// ... and, once it knows its tiles, has the launch registered for the block stamps and the time-out diagnostics. Returns the launch's blocks.
+static int dq_register(hb_ctx *c, dq_view *v, int gidx, int ncols, int ntiles)
+{
+    const int nblk = v->nupd + v->nfin + ntiles;
+    v->ldiag = (c->ldiag && gidx >= 0 && gidx <= c->npanels) ? c->ldiag + 4 * (size_t)gidx : nullptr;
+    if (v->ldiag) c->ldiag_nblk[gidx] = nblk;
+    if (c->lstamp && gidx >= 0 && gidx <= c->npanels && nblk <= HB_LSTAMP_BLOCKS) {
+        v->stamp = c->lstamp + (size_t)gidx * HB_LSTAMP_BLOCKS * 2;
+        c->lstamp_nblk[gidx] = nblk;
+        c->lstamp_cols[gidx] = ncols;
+    }
+    return nblk;
+}
+
+// the shapes of the 2-bit mat-vec (hb_dotq2.hpp) with their LDS: {1, CT, G, SC} k_dotq2m on the matrix cores (G = 0 / 3: the 512-individual stages),
+// {0, CPL, RS, 0} k_dotq2 (RS = 128: 6208 bytes of LDS per wave, twice the waves per compute unit)
+#define HB_Q2M_ENTRY(CT, G, LDS) {{1, CT, G, 0}, k_dotq2m<CT, G, false>, LDS}, {{1, CT, G, 1}, k_dotq2m<CT, G, true>, LDS},
+#define HB_Q2_ENTRY(CPL, RS) {{0, CPL, RS, 0}, k_dotq2<CPL, RS>, q2_lds(CPL, RS)},
+static const kernel_entry<4, dq_view, upd_view> dotq2_kernels[] = {
+    HB_Q2M_ENTRY(4, 0, q2m512_lds<false>()) HB_Q2M_ENTRY(4, 3, q2m512_lds<true>()) HB_Q2M_ENTRY(16, 1, (q2m_lds<16, 1>())) HB_Q2M_ENTRY(8, 2, (q2m_lds<8, 2>()))
+    HB_Q2M_ENTRY(8, 1, (q2m_lds<8, 1>())) HB_Q2M_ENTRY(4, 2, (q2m_lds<4, 2>())) HB_Q2M_ENTRY(4, 1, (q2m_lds<4, 1>()))
+    HB_Q2_ENTRY(2, 512) HB_Q2_ENTRY(2, 256) HB_Q2_ENTRY(1, 512) HB_Q2_ENTRY(1, 128) HB_Q2_ENTRY(1, 256)};
+
+// the mat-vec launch on the 2-bit resident layout (hb_dotq2.hpp): about two long-lived waves per compute unit
+static int launch_dotq2(hb_ctx *c, int col0, int ncols, int slot, hipStream_t st, int gidx, const upd_view *upd, int fin_col0,
                          int fin_ncols, int fin_gidx)
 {
+    const upd_view uq = upd ? *upd : upd_view{};
+    dq_view v = dq_common(c, col0, slot, gidx, uq, fin_col0, fin_ncols, fin_gidx);
+    v.X2 = reinterpret_cast<const uint8_t *>(c->X2) + (int64_t)col0 * c->ld2;
+    v.ld2 = c->ld2;
     if (c->dotq2_kind == 1) { // rows across the lanes, no LDS (k_dotq2r): tiles = row blocks x groups of NC columns
         int NC = c->dotq2_nc;
         while (NC > Q2R_CB && ncols % NC) NC -= Q2R_CB;
         if (ncols % NC == 0 && NC % Q2R_CB == 0 && c->ld >= 64) {
-            upd_view uq{};
-            if (upd) uq = *upd;
-            dq_view v{};
-            v.X = nullptr;
-            v.X2 = reinterpret_cast<const uint8_t *>(c->X2) + (int64_t)col0 * c->ld2;
-            v.ld2 = c->ld2;
-            v.ld = c->ld;
-            v.rq = c->rq + (size_t)slot * HB_ND * c->ld;
-            v.vexp_in = c->vexp + slot;
-            v.gexp_out = c->gexp + gidx;
-            v.accq = c->accq + col0;
-            v.accstride = c->m_pad;
             v.NS = NC;
             v.ncg = ncols / NC;
             v.nstages = (int)((c->ld2 * 4 + Q2R_RB - 1) / Q2R_RB);
-            v.nupd = (uq.p1 > uq.p0) ? (int)(c->ld / (uq.dense ? 64 : 256)) : 0;
-            v.nfin = fin_ncols > 0 ? (fin_ncols + 63) / 64 : 0;
-            v.fin_acc = c->accq + fin_col0;
-            v.fin_out = c->dsum + fin_col0;
-            v.fin_exp = c->gexp + fin_gidx;
-            v.fin_ncols = fin_ncols;
-            const int nblk = v.nupd + v.nfin + v.ncg * v.nstages;
-            v.stamp = nullptr;
-            v.ldiag = (c->ldiag && gidx >= 0 && gidx <= c->npanels) ? c->ldiag + 4 * (size_t)gidx : nullptr;
-            if (v.ldiag) c->ldiag_nblk[gidx] = nblk;
-            if (c->lstamp && gidx >= 0 && gidx <= c->npanels && nblk <= HB_LSTAMP_BLOCKS) {
-                v.stamp = c->lstamp + (size_t)gidx * HB_LSTAMP_BLOCKS * 2;
-                c->lstamp_nblk[gidx] = nblk;
-                c->lstamp_cols[gidx] = ncols;
-            }
+            const int nblk = dq_register(c, &v, gidx, ncols, v.ncg * v.nstages);
             hipLaunchKernelGGL(k_dotq2r, dim3(nblk), dim3(64), 0, st, v, uq);
-            return;
+            return HB_OK;
         }
     }
     const bool mfma = c->dotq2_kind == 2; // (A/B: the digit-plane product on the matrix cores, k_dotq2m; 256-individual stages, 64 columns per wave)
@@ -299,13 +282,10 @@ static void launch_dotq2(hb_ctx *c, int col0, int ncols, int slot, hipStream_t s
     // (a tile is at least four stages: its first stage's load latency and its closing atomics are paid per tile)
     // (the matrix-core kernel streams best with few, long tiles — its per-stage work is an eighth of the v_dot4 kernel's, so a tile's fixed
     // costs weigh more: ~800 tiles per 3584-column launch)
-    int ns = std::max(1, std::min(std::max(1, nst / 4), (int)((double)(mfma && !getenv("HB_DOTQ2_TILES") ? ((q2m_g == 0 || q2m_g == 3) ? 900 : 800) : c->dotq2_tiles) / ncg + 0.5)));
+    int ns = std::max(1, std::min(std::max(1, nst / 4), (int)((double)(mfma && !c->dotq2_tiles_set ? ((q2m_g == 0 || q2m_g == 3) ? 900 : 800) : c->dotq2_tiles) / ncg + 0.5)));
     // (int32 accumulators of genotypes scaled by up to 32 — Q2_SCALED, k_dotq2m: rows x 96 x 128 < 2^31 bounds a tile at 174 000 individuals)
     ns = std::max(ns, (int)(((int64_t)nst * RS + 131071) / 131072));
-    upd_view uq{};
-    if (upd) uq = *upd;
-    const int nupd_blk = (uq.p1 > uq.p0) ? (int)(c->ld / (uq.dense ? 64 : 256)) : 0, nfin_blk = fin_ncols > 0 ? (fin_ncols + 63) / 64 : 0;
-    if (mfma && (q2m_g == 0 || q2m_g == 3) && !getenv("HB_DOTQ2_TILES")) {
+    if (mfma && (q2m_g == 0 || q2m_g == 3) && !c->dotq2_tiles_set) {
         // ALL blocks of the launch resident at once (round 5, the last measurement of the round). A block of this kernel holds 37 KB of LDS: four per
         // compute unit, 128 per XCD — less the chain workgroup's compute unit and k_fwd's share of another, which sit on ONE XCD — and the
         // dispatcher deals the blocks round-robin over the eight XCDs whatever they have free. 784 tiles + 196 update + 56 finalize blocks = 1 036
@@ -315,114 +295,49 @@ static void launch_dotq2(hb_ctx *c, int col0, int ncols, int slot, hipStream_t s
         const int per_cu = std::max(1, std::min(8, (160 * 1024) / std::max(1, lds)));
         const int cus_per_xcd = std::max(1, c->num_cus / 8);
         const int budget = 8 * (cus_per_xcd * per_cu - (per_cu + 3)); // (the fullest XCD gets ceil(blocks / 8))
-        auto total = [&](int k) { const int NSk = (nst + k - 1) / k; return nupd_blk + nfin_blk + ncg * ((nst + NSk - 1) / NSk); };
+        auto total = [&](int k) { const int NSk = (nst + k - 1) / k; return v.nupd + v.nfin + ncg * ((nst + NSk - 1) / NSk); };
         const int ns_min = std::max(1, (int)(((int64_t)nst * RS + 131071) / 131072));
         while (ns > ns_min && total(ns) > budget) ns--;
     }
-    const int NS = (nst + ns - 1) / ns, nsplit = (nst + NS - 1) / NS;
-    dq_view v{};
-    v.X = nullptr;
-    v.X2 = reinterpret_cast<const uint8_t *>(c->X2) + (int64_t)col0 * c->ld2;
-    v.ld2 = c->ld2;
-    v.ld = c->ld;
-    v.rq = c->rq + (size_t)slot * HB_ND * c->ld;
-    v.vexp_in = c->vexp + slot;
-    v.gexp_out = c->gexp + gidx;
-    v.accq = c->accq + col0;
-    v.accstride = c->m_pad;
     v.nstages = nst;
-    v.NS = NS;
+    v.NS = (nst + ns - 1) / ns;
     v.ncg = ncg;
-    v.nupd = nupd_blk;
-    v.nfin = nfin_blk;
-    v.fin_acc = c->accq + fin_col0;
-    v.fin_out = c->dsum + fin_col0;
-    v.fin_exp = c->gexp + fin_gidx;
-    v.fin_ncols = fin_ncols;
-    const int nblk = v.nupd + v.nfin + ncg * nsplit;
-    v.stamp = nullptr;
-    v.ldiag = (c->ldiag && gidx >= 0 && gidx <= c->npanels) ? c->ldiag + 4 * (size_t)gidx : nullptr;
-    if (v.ldiag) c->ldiag_nblk[gidx] = nblk;
-    if (c->lstamp && gidx >= 0 && gidx <= c->npanels && nblk <= HB_LSTAMP_BLOCKS) {
-        v.stamp = c->lstamp + (size_t)gidx * HB_LSTAMP_BLOCKS * 2;
-        c->lstamp_nblk[gidx] = nblk;
-        c->lstamp_cols[gidx] = ncols;
-    }
+    const int nblk = dq_register(c, &v, gidx, ncols, ncg * ((nst + v.NS - 1) / v.NS));
     // (the update rows stage their lists in the tile buffers: 6152 bytes, below the smallest shape's 12416)
-    if (mfma) {
-#define HB_Q2M_LAUNCH(CT, G, SC) hipLaunchKernelGGL((k_dotq2m<CT, G, SC>), dim3(nblk), dim3(64), (q2m_lds<CT, G>()), st, v, uq)
-        const bool sc = c->q2m_sc != 0;
-        if (q2m_g == 0) {
-            if (sc) hipLaunchKernelGGL((k_dotq2m<4, 0, true>), dim3(nblk), dim3(64), q2m512_lds<false>(), st, v, uq);
-            else hipLaunchKernelGGL((k_dotq2m<4, 0, false>), dim3(nblk), dim3(64), q2m512_lds<false>(), st, v, uq);
-        } else if (q2m_g == 3) {
-            if (sc) hipLaunchKernelGGL((k_dotq2m<4, 3, true>), dim3(nblk), dim3(64), q2m512_lds<true>(), st, v, uq);
-            else hipLaunchKernelGGL((k_dotq2m<4, 3, false>), dim3(nblk), dim3(64), q2m512_lds<true>(), st, v, uq);
-        } else if (q2m_ct == 16) { if (sc) HB_Q2M_LAUNCH(16, 1, true); else HB_Q2M_LAUNCH(16, 1, false); }
-        else if (q2m_ct == 8 && q2m_g == 2) { if (sc) HB_Q2M_LAUNCH(8, 2, true); else HB_Q2M_LAUNCH(8, 2, false); }
-        else if (q2m_ct == 8) { if (sc) HB_Q2M_LAUNCH(8, 1, true); else HB_Q2M_LAUNCH(8, 1, false); }
-        else if (q2m_g == 2) { if (sc) HB_Q2M_LAUNCH(4, 2, true); else HB_Q2M_LAUNCH(4, 2, false); }
-        else { if (sc) HB_Q2M_LAUNCH(4, 1, true); else HB_Q2M_LAUNCH(4, 1, false); }
-#undef HB_Q2M_LAUNCH
-    }
-    else if (cpl == 2 && RS == 512) hipLaunchKernelGGL((k_dotq2<2, 512>), dim3(nblk), dim3(64), q2_lds(2, 512), st, v, uq);
-    else if (cpl == 2) hipLaunchKernelGGL((k_dotq2<2, 256>), dim3(nblk), dim3(64), q2_lds(2, 256), st, v, uq);
-    else if (RS == 512) hipLaunchKernelGGL((k_dotq2<1, 512>), dim3(nblk), dim3(64), q2_lds(1, 512), st, v, uq);
-    else if (RS == 128) hipLaunchKernelGGL((k_dotq2<1, 128>), dim3(nblk), dim3(64), q2_lds(1, 128), st, v, uq); // (6208 bytes of LDS per wave: twice the waves per compute unit)
-    else hipLaunchKernelGGL((k_dotq2<1, 256>), dim3(nblk), dim3(64), q2_lds(1, 256), st, v, uq);
+    const int shape[4] = {mfma, mfma ? q2m_ct : cpl, mfma ? q2m_g : RS, mfma && c->q2m_sc};
+    const auto *k = find_kernel(dotq2_kernels, shape, mfma ? "k_dotq2m" : "k_dotq2");
+    if (!k) return HB_ERR_INVALID;
+    hipLaunchKernelGGL(k->fn, dim3(nblk), dim3(64), k->lds, st, v, uq);
+    return HB_OK;
 }
 
-static void launch_dotq(hb_ctx *c, int col0, int ncols, int slot, hipStream_t st, int gidx, const upd_view *upd, int fin_col0,
+static int launch_dotq(hb_ctx *c, int col0, int ncols, int slot, hipStream_t st, int gidx, const upd_view *upd, int fin_col0,
                         int fin_ncols, int fin_gidx)
 {
-    if (c->layout == 2) {
-        launch_dotq2(c, col0, ncols, slot, st, gidx, upd, fin_col0, fin_ncols, fin_gidx);
-        return;
-    }
-    int ncg, NS, nsplit;
-    dotq_geometry(c, ncols, &ncg, &NS, &nsplit);
-    upd_view uq{};
-    if (upd) uq = *upd;
-    dq_view v{};
+    if (c->layout == 2) return launch_dotq2(c, col0, ncols, slot, st, gidx, upd, fin_col0, fin_ncols, fin_gidx);
+    // tiles of one k_dotq launch: about three waves per compute unit, each a long run of stages (measured: fewer, longer
+    // waves stream better than many short ones; tools/dotq_bench.hip)
+    const int nst = (int)(c->ld / HBQ_RS), ncg = ncols / 64;
+    const int ns = std::max(1, std::min(nst, (int)((double)c->dotq_tiles / ncg + 0.5)));
+    const upd_view uq = upd ? *upd : upd_view{};
+    dq_view v = dq_common(c, col0, slot, gidx, uq, fin_col0, fin_ncols, fin_gidx);
     v.X = c->X + (int64_t)col0 * c->ld;
-    v.ld = c->ld;
-    v.rq = c->rq + (size_t)slot * HB_ND * c->ld;
-    v.vexp_in = c->vexp + slot;
-    v.gexp_out = c->gexp + gidx;
-    v.accq = c->accq + col0;
-    v.accstride = c->m_pad;
-    v.nstages = (int)(c->ld / HBQ_RS);
-    v.NS = NS;
+    v.nstages = nst;
+    v.NS = std::min(1024, (nst + ns - 1) / ns); // (int32 accumulators: NS * 128 rows * 127 * 128 < 2^31)
     v.ncg = ncg;
-    v.nupd = (uq.p1 > uq.p0) ? (int)(c->ld / (uq.dense ? 64 : 256)) : 0;
-    v.nfin = fin_ncols > 0 ? (fin_ncols + 63) / 64 : 0;
-    v.fin_acc = c->accq + fin_col0;
-    v.fin_out = c->dsum + fin_col0;
-    v.fin_exp = c->gexp + fin_gidx;
-    v.fin_ncols = fin_ncols;
-    const int nblk = v.nupd + v.nfin + ncg * nsplit;
-    v.stamp = nullptr;
-    v.ldiag = (c->ldiag && gidx >= 0 && gidx <= c->npanels) ? c->ldiag + 4 * (size_t)gidx : nullptr;
-    if (v.ldiag) c->ldiag_nblk[gidx] = nblk;
-    if (c->lstamp && gidx >= 0 && gidx <= c->npanels && nblk <= HB_LSTAMP_BLOCKS) {
-        v.stamp = c->lstamp + (size_t)gidx * HB_LSTAMP_BLOCKS * 2;
-        c->lstamp_nblk[gidx] = nblk;
-        c->lstamp_cols[gidx] = ncols;
-    }
+    const int nblk = dq_register(c, &v, gidx, ncols, ncg * ((nst + v.NS - 1) / v.NS));
     hipLaunchKernelGGL(k_dotq, dim3(nblk), dim3(64), uq.dense ? HBU_LDS : HBQ_LDS, st, v, uq);
+    return HB_OK;
 }
 
-static void launch_dot(hb_ctx *c, int col0, int ncols, int slot = 0, hipStream_t st = nullptr, bool pipeline = false,
+static int launch_dot(hb_ctx *c, int col0, int ncols, int slot = 0, hipStream_t st = nullptr, bool pipeline = false,
                        const upd_view *upd = nullptr, int red_col0 = 0, int red_ncols = 0, int gidx = 0)
 {
     if (!st) st = c->stream;
     upd_view uq{};
     if (upd) uq = *upd;
     if (!pipeline) red_ncols = 0;
-    if (c->precise == 2) {
-        launch_dotq(c, col0, ncols, slot, st, gidx, upd, red_col0, red_ncols, gidx - 1);
-        return;
-    }
+    if (c->precise == 2) return launch_dotq(c, col0, ncols, slot, st, gidx, upd, red_col0, red_ncols, gidx - 1);
     const dim3 grid(ncols / 8, c->nsplit + (uq.p1 > uq.p0 ? 1 : 0) + (red_ncols > 0 ? 1 : 0)), block(256);
     const int8_t *Xp = c->X + (int64_t)col0 * c->ld;
     double *part = c->partial + col0;
@@ -437,6 +352,7 @@ static void launch_dot(hb_ctx *c, int col0, int ncols, int slot = 0, hipStream_t
         if (sgn) hipLaunchKernelGGL((k_dot<false, true>), grid, block, c->dot_lds, st, Xp, c->ld, r32, r64, c->nchunks, 1, part, c->m_pad, sy, uq);
         else     hipLaunchKernelGGL((k_dot<false, false>), grid, block, c->dot_lds, st, Xp, c->ld, r32, r64, c->nchunks, 1, part, c->m_pad, sy, uq);
     }
+    return HB_OK;
 }
 
 // digit-plane sums of [col0, col0 + ncols) -> doubles at out (the finalize that has no later launch to ride on)
@@ -577,7 +493,7 @@ static int enqueue_sweep_kernels(hb_ctx *c, int model, int n_fold, bool timed)
             hipEvent_t b = tm.begin();
             const int vread = pd - L - 1;
             if (!timed && vread >= 0) HB_HIP(hipStreamWaitEvent(sA, c->ev_upd[vread], 0));
-            launch_dot(c, pd * c->P, c->P, ver_slot(c, vread < -1 ? -1 : vread), sA, false, nullptr, 0, 0, pd);
+            if (int rc = launch_dot(c, pd * c->P, c->P, ver_slot(c, vread < -1 ? -1 : vread), sA, false, nullptr, 0, 0, pd)) return rc;
             if (fx && c->row_reduce)
                 if (int rcr = row_reduce_accq(c, pd * c->P, c->P, sA)) return rcr;
             if (fx) launch_dotq_fin(c, pd * c->P, c->P, pd, c->partial + (size_t)pd * c->P, sA); // the chain sums one "split"
@@ -670,13 +586,18 @@ static int enqueue_sweep_pipeline(hb_ctx *c, int model, int n_fold, int pb, int 
     // chain_done (their update rows find empty event lists), the chain afterwards with the device to itself; the stamped span
     // (tools/chain_timeline.py with CT_ALONE=1) is then what the chain costs without the mat-vec's memory traffic beside it.
     const bool alone = c->chain_alone || env_alone;
+    const bool cert = c->gcert_ok && c->gcmax != nullptr; // (the group chain's certified violation check)
+    // WHAT runs — the chain's instantiation, k_fwd and the warmers beside it — is the plan's; from here on only WHEN
+    const hb_sweep_plan plan = plan_sweep({model, n_fold, c->P, Lv, D, c->L, cert, c->chain_alone, env_alone, np - pb > 2, c->s_warm != nullptr});
+    if (!plan.ok)
+        return hb_fail(HB_ERR_UNSUPPORTED, "three groups of seven panels of look-ahead, or two of eight, need the group chain with k_fwd (panel 512; seven: BayesB / BayesC "
+                                           "and BayesR with up to four classes; eight: BayesB / BayesC with the certificate)");
+    const bool dense = plan.chain == HB_CHAIN_DENSE; // k_chain_dense + k_fold_dense (hb_chain_dense.hpp)
     // sweep start: one kernel clears the sweep sums, the flag block, the event counts (quiet panels do not write theirs) and
     // fills dsum[] with "not written yet" (a NaN no sum can produce); the residual's digit planes are then written (k_quant0,
     // one workgroup) beside k_pre / k_hotlist, which need all the other compute units. The chain must be launched BEFORE the
     // first mat-vec launch (it needs a compute unit with all of its LDS free, and back-to-back mat-vec launches never leave
     // one), so both branches start together after the join.
-    // the models in which every marker moves (BayesRR / A / L) at panel 512: k_chain_dense + k_fold_dense (hb_chain_dense.hpp)
-    const bool dense = kp == 1 && (model == 1 || model == 2 || model == 5) && c->P == 512 && !alone && c->L <= HB_LBMAX;
     const bool dense_upd = dense && c->dense_upd;
     if (c->ldiag) HB_HIP(hipMemsetAsync(c->ldiag, 0, sizeof(unsigned long long) * 4 * ((size_t)c->npanels + 2), sA));
     hipLaunchKernelGGL(k_sweep_init, dim3(256), dim3(256), 0, sA, first ? c->acc : nullptr, c->flags, c->ev_count, c->npanels,
@@ -707,52 +628,24 @@ static int enqueue_sweep_pipeline(hb_ctx *c, int model, int n_fold, int pb, int 
     chain_view cv{c->m_pad, c->P, c->nsplit, Lv, c->Lg, c->xpx, c->vx, c->g, c->tracker, c->nzrate, c->alpha_sum, c->alpha_sq,
                   c->thr, c->invv, c->sdz, c->gram, c->partial, c->dsum, c->ev_count, c->ev_idx, c->ev_delta, c->acc,
                   c->wind, c->wflag, c->dbg, fx ? c->mb : nullptr, xabs};
-    const bool cert = c->gcert_ok && c->gcmax != nullptr; // (the wide group chain's certified violation check)
     if (cert) { cv.ga = c->ga; cv.gB = c->gB; cv.gcmax = c->gcmax; }
     const int last_panels = np - (g0 + ngroups - 1) * D;
     persist_view pv{np, D, Lv, c->L, c->Lg, pb, c->flags,
                     c->hot_slot, c->hot_list, c->thr0f, c->candf, nullptr, nullptr};
     if (cert) pv.opn = c->opn; // (k_hotlist wrote it: gcert_ok)
-    // the point-mass models (and BayesR below) run the group-granular chain (hb_chain_group.hpp); the other models k_chain_persist
-    const int shape = (D <= 1 && Lv * D <= 2) ? 2 : (D <= 2 && Lv * D <= 4) ? 1 : (D <= 8 && Lv * D <= 14) ? 0 : (c->P == 512 && ((Lv == 3 && D == 7) || (Lv == 2 && D == 8))) ? 0 : -1;
-    const bool sparse_model = kp == 1 && (model == 3 || model == 4);
-    // round 6: BayesR with up to four classes (kp == 3) runs the group chain too wherever a launch covers more than one panel. K1 nested
-    // thresholds per candidate instead of one; everything else — candidates, certificate (it bounds the right-hand side, not the class),
-    // fold, k_fwd — is the point-mass models' path.
-    const bool mix_model = kp == 3 && model == 6 && D >= 2;
-    const bool group_chain = !dense && shape >= 0 && !c->chain_alone && (sparse_model || mix_model);
-    // k_fwd beside the wide group chain: the chain folds a move into its own group and the next (15 rows, four moves per trip),
-    // a second workgroup into the group after that
-    // round 6: also beside BayesR's two-panel groups ((2, 2): the chain folds a move into the next group's two panels, k_fwd into the two after — half of the
-    // chain's fold rows leave its compute unit, and a group's ~16 moves fit ONE trip of 62 loads per lane instead of two of 60)
-    const bool fwd2 = group_chain && mix_model && Lv == 2 && D == 2 && c->P == 512 && !alone && cert;
-    // round 6: eight panels per launch (Lv = 2 only, point-mass models, certified): k_chain_group<1, 8, 8, CH, CERT> + k_fwd<8, 1, 8>
-    const bool wide8 = group_chain && kp == 1 && Lv == 2 && D == 8 && c->P == 512 && !alone && cert;
-    const bool fwd = (group_chain && (Lv == 2 || Lv == 3) && D == 7 && c->P == 512 && !alone) || fwd2 || wide8;
-    if (fwd) pv.fcorr = c->fcorr;
-    if (c->L > HB_LBMAX && !fwd)
-        return hb_fail(HB_ERR_UNSUPPORTED, "three groups of seven panels of look-ahead need the group chain with k_fwd (BayesB / BayesC, panel 512)");
-    if (dense) pv.fcorr = c->fcorr;
-    // BayesR on the per-panel chain (round 4): k_fwd folds a panel's moves into the panels two (and, at Lv = 3, three) ahead, the chain
-    // itself only into the next one — half (two thirds) of the band rows of a dense sweep leave the chain's compute unit
-    const bool fwd_persist = !dense && !group_chain && kp == 3 && c->P == 512 && D == 1 && (Lv == 2 || Lv == 3) && !alone && np - pb > 2;
-    if (fwd_persist) pv.fcorr = c->fcorr;
+    if (plan.fcorr) pv.fcorr = c->fcorr;
     auto launch_the_chain = [&](hipStream_t st) -> int {
-        const char *what = "k_chain_persist";
-        if (dense) {
-            what = "k_chain_dense";
-            hipLaunchKernelGGL(dense_chain_kernel(model == 5), dim3(1), dim3(512), persist_smem(c->P), st, c->d_in, cv, pv, c->ddense, c->fcorr2);
-        } else if (group_chain) {
-            what = "k_chain_group";
-            const bool narrow = D <= 4 && Lv * D <= 8 && !(D <= 2 && Lv * D <= 4);
-            hipLaunchKernelGGL(group_chain_kernel(mix_model, shape, fwd, fwd2, wide8, cert && c->P == 512, narrow), dim3(1), dim3(c->P),
-                               persist_smem(c->P), st, c->d_in, cv, pv);
-        } else
-            hipLaunchKernelGGL(persist_chain_kernel(kp, pv.Lb, pv.fcorr != nullptr), dim3(1), dim3(c->P), persist_smem(c->P), st, c->d_in, cv, pv,
-                               persist_nslot(c->P, c->L, kp));
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return hb_fail(HB_ERR_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
-        return HB_OK;
+        const char *what = dense ? "k_chain_dense" : plan.chain == HB_CHAIN_GROUP ? "k_chain_group" : "k_chain_persist";
+        auto launch = [&](const auto &table, int threads, auto... more) -> int { // (the plan's instantiation, with the arguments its family adds)
+            const auto *k = find_kernel(table, plan.ct, what);
+            if (!k) return HB_ERR_INVALID;
+            hipLaunchKernelGGL(k->fn, dim3(1), dim3(threads), persist_smem(c->P), st, c->d_in, cv, pv, more...);
+            hipError_t e = hipGetLastError();
+            return e == hipSuccess ? HB_OK : hb_fail(HB_ERR_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
+        };
+        if (dense) return launch(dense_chains, 512, c->ddense, c->fcorr2);
+        if (plan.chain == HB_CHAIN_GROUP) return launch(group_chains, c->P);
+        return launch(persist_chains, c->P, persist_nslot(c->P, c->L, kp));
     };
     if (alone) { // (the update rows poll the move counts themselves: "no moves" for every panel)
         HB_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->flags + HB_FLAG_CHAIN_DONE), 0x7ffffff0, 1, sA));
@@ -773,42 +666,23 @@ static int enqueue_sweep_pipeline(hb_ctx *c, int model, int n_fold, int pb, int 
         // (the first mat-vec launch starts when the chain is resident — where a launch's update blocks can sit on every compute unit)
         if (dense) hipLaunchKernelGGL(k_gate, dim3(1), dim3(64), 0, sA, c->flags);
     }
-    // the L2 warmers (k_warm): a third branch of the graph, warm_per_xcd workgroups per XCD of which only the chain's XCD's stay; not beside
-    // the group chain and k_fwd, which has the third stream
-    constexpr int warm_per_xcd = 4;
-    const int warm = (alone || group_chain || dense || fwd_persist) ? 0 : warm_per_xcd;
-    // BayesR with k_fwd beside the chain: the warmers on a stream of their own. They read the Gram rows of EVERY marker on a
-    // panel's hot list, with or without a slot in the chain's row cache, and the rows their moves fold into the next panel (the chain's share of the band).
-    // The same beside BayesR's two-panel group chain with k_fwd: the listed markers' Gram rows for the chain's share of the band (its own group and the
-    // next: 2 D - 1 blocks) and the panels' exact per-marker data (round 6: 92.1 sweeps/s without, 95.9 / 97.5 / 96.5 with 2 / 4 / 8 workgroups per XCD,
-    // profiles/r06_bayesr_conv_warm.txt; beside the wide BayesCpi shape: no effect, round 5)
-    const int warm_r = ((fwd_persist || fwd2) && c->s_warm) ? warm_per_xcd : 0;
-    if (fwd) {
+    if (plan.fwd[0]) { // k_fwd: a second persistent workgroup, on the update stream
+        auto *k = find_kernel(fwd_kernels, plan.fwd, "k_fwd");
+        if (!k) return HB_ERR_INVALID;
         HB_HIP(hipStreamWaitEvent(c->s_upd, c->ev_fork, 0));
-        if (fwd2) hipLaunchKernelGGL((k_fwd<2, 1, 16>), dim3(1), dim3(c->P), 0, c->s_upd, cv, pv);
-        else if (wide8) hipLaunchKernelGGL((k_fwd<8, 1, 8>), dim3(1), dim3(c->P), 0, c->s_upd, cv, pv);
-        else if (Lv == 2) hipLaunchKernelGGL((k_fwd<7, 1, 8>), dim3(1), dim3(c->P), 0, c->s_upd, cv, pv);
-        else hipLaunchKernelGGL((k_fwd<7, 2, 4>), dim3(1), dim3(c->P), 0, c->s_upd, cv, pv);
+        hipLaunchKernelGGL(k->fn, dim3(1), dim3(c->P), 0, c->s_upd, cv, pv);
         HB_HIP(hipGetLastError());
     }
-    if (fwd_persist) {
+    if (plan.warm) { // the L2 warmers (k_warm, hb_warm.hpp): a third branch of the graph
         HB_HIP(hipStreamWaitEvent(c->s_upd, c->ev_fork, 0));
-        if (Lv == 2) hipLaunchKernelGGL((k_fwd<1, 1, 16>), dim3(1), dim3(c->P), 0, c->s_upd, cv, pv);
-        else hipLaunchKernelGGL((k_fwd<1, 2, 8>), dim3(1), dim3(c->P), 0, c->s_upd, cv, pv);
+        hipLaunchKernelGGL(k_warm, dim3(8 * plan.warm), dim3(256), 0, c->s_upd, pv, cv, kp, c->gram, c->P, plan.warm_ahead, plan.warm, reinterpret_cast<int *>(c->flags + 48));
         HB_HIP(hipGetLastError());
     }
-    if (warm) {
-        HB_HIP(hipStreamWaitEvent(c->s_upd, c->ev_fork, 0));
-        const int ahead = D + 4; // (panels ahead of chain_done)
-        hipLaunchKernelGGL(k_warm, dim3(8 * warm), dim3(256), 0, c->s_upd, pv, cv, kp, c->gram, c->P, ahead, warm, reinterpret_cast<int *>(c->flags + 48));
-        HB_HIP(hipGetLastError());
-    }
-    if (warm_r) {
+    if (plan.warm_r) { // ... or a fourth, where k_fwd has the third
         HB_HIP(hipStreamWaitEvent(c->s_warm, c->ev_fork, 0));
-        const int ahead = fwd ? 2 * D : 2; // (measured, BayesR at n = 50k, m = 500k: off 48.3 sweeps/s, 2 panels ahead 51.2, 4 ahead 50.5, 8 ahead 50.0)
         persist_view pw = pv;
-        pw.Lb = fwd ? 2 * D - 1 : 1; // (BayesR: the chain folds into the next panel only; the group chain: into its own group's later panels and the next group's)
-        hipLaunchKernelGGL(k_warm, dim3(8 * warm_r), dim3(256), 0, c->s_warm, pw, cv, kp, c->gram, c->P, ahead, warm_r, reinterpret_cast<int *>(c->flags + 48));
+        pw.Lb = plan.warm_r_Lb;
+        hipLaunchKernelGGL(k_warm, dim3(8 * plan.warm_r), dim3(256), 0, c->s_warm, pw, cv, kp, c->gram, c->P, plan.warm_r_ahead, plan.warm_r, reinterpret_cast<int *>(c->flags + 48));
         HB_HIP(hipGetLastError());
     }
     const bool inject = c->inject_abort_panel >= 0 && c->s_dbg && !alone;
@@ -839,8 +713,8 @@ static int enqueue_sweep_pipeline(hb_ctx *c, int model, int n_fold, int pb, int 
             hipLaunchKernelGGL(k_update_dense, dim3((unsigned)(c->ld / 64)), dim3(64), 0, sA, c->ld, uq);
             ride = false;
         }
-        launch_dot(c, p0 * c->P, (p1 - p0) * c->P, slot2(g - Lv - 1), sA, true, ride ? &uq : nullptr,
-                   g > 0 ? (ga - 1) * D * c->P : 0, g > 0 ? D * c->P : 0, ga);
+        if (int rc = launch_dot(c, p0 * c->P, (p1 - p0) * c->P, slot2(g - Lv - 1), sA, true, ride ? &uq : nullptr,
+                                g > 0 ? (ga - 1) * D * c->P : 0, g > 0 ? D * c->P : 0, ga)) return rc;
     }
     launch_reduce(c, (g0 + ngroups - 1) * D * c->P, last_panels * c->P, sA, g0 + ngroups - 1);
     if (alone)
@@ -854,11 +728,11 @@ static int enqueue_sweep_pipeline(hb_ctx *c, int model, int n_fold, int pb, int 
     }
     HB_HIP(hipEventRecord(c->ev_chain[0], sB));
     HB_HIP(hipStreamWaitEvent(sA, c->ev_chain[0], 0));
-    if (warm || fwd || dense || fwd_persist) {
+    if (plan.warm || plan.fwd[0] || dense) {
         HB_HIP(hipEventRecord(c->ev_upd[0], c->s_upd));
         HB_HIP(hipStreamWaitEvent(sA, c->ev_upd[0], 0));
     }
-    if (warm_r) {
+    if (plan.warm_r) {
         HB_HIP(hipEventRecord(c->ev_chain[1 % c->npanels], c->s_warm));
         HB_HIP(hipStreamWaitEvent(sA, c->ev_chain[1 % c->npanels], 0));
     }
@@ -987,12 +861,12 @@ int hbk_dot_all(hb_ctx *c)
 {
     if (c->precise == 2) {
         launch_quant0(c, c->stream);
-        for (int p = 0; p < c->npanels; p++) launch_dot(c, p * c->P, c->P);
+        for (int p = 0; p < c->npanels; p++) if (int rc = launch_dot(c, p * c->P, c->P)) return rc;
         launch_dotq_fin(c, 0, c->m_pad, 0, c->dots, c->stream);
         HB_HIP(hipGetLastError());
         return HB_OK;
     }
-    for (int p = 0; p < c->npanels; p++) launch_dot(c, p * c->P, c->P);
+    for (int p = 0; p < c->npanels; p++) if (int rc = launch_dot(c, p * c->P, c->P)) return rc;
     hipLaunchKernelGGL(k_sum_partials, dim3((c->m_pad + 255) / 256), dim3(256), 0, c->stream, c->partial, c->m_pad,
                        c->nsplit, c->m_pad, c->dots);
     HB_HIP(hipGetLastError());
@@ -1002,7 +876,7 @@ int hbk_dot_all(hb_ctx *c)
 int hbk_dot_panels(hb_ctx *c, int reps)
 {
     for (int r = 0; r < reps; r++)
-        for (int p = 0; p < c->npanels; p++) launch_dot(c, p * c->P, c->P);
+        for (int p = 0; p < c->npanels; p++) if (int rc = launch_dot(c, p * c->P, c->P)) return rc;
     HB_HIP(hipGetLastError());
     return HB_OK;
 }
@@ -1221,13 +1095,15 @@ int hbk_time_matvec(hb_ctx *c, int D, int reps, int as_pipeline, double *avg_us,
     hipGraph_t g = nullptr;
     hipGraphExec_t ge = nullptr;
     HB_HIP(hipStreamBeginCapture(c->stream, hipStreamCaptureModeRelaxed));
-    for (int gi = 0; gi < ngroups; gi++) {
+    int rc = HB_OK;
+    for (int gi = 0; gi < ngroups && !rc; gi++) {
         const int p0 = gi * D, p1 = std::min(c->npanels, p0 + D);
-        launch_dot(c, p0 * c->P, (p1 - p0) * c->P, 0, c->stream, as_pipeline != 0, nullptr,
-                   gi > 0 ? (gi - 1) * D * c->P : 0, gi > 0 ? D * c->P : 0, gi);
+        rc = launch_dot(c, p0 * c->P, (p1 - p0) * c->P, 0, c->stream, as_pipeline != 0, nullptr,
+                        gi > 0 ? (gi - 1) * D * c->P : 0, gi > 0 ? D * c->P : 0, gi);
     }
     if (as_pipeline) launch_reduce(c, (ngroups - 1) * D * c->P, (c->npanels - (ngroups - 1) * D) * c->P, c->stream, ngroups - 1);
     HB_HIP(hipStreamEndCapture(c->stream, &g));
+    if (rc) return rc;
     HB_HIP(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
     HB_HIP(hipGraphLaunch(ge, c->stream));
     HB_HIP(hipEventRecord(e0, c->stream));

@@ -325,3 +325,74 @@ def test_hot_kernels_are_built_without_register_spills():
         assert found, "kernel missing from the report: %s (%s)" % (what, prefix)
         for k in found:
             assert rows[k].get("ScratchSize", 0) == 0 and rows[k].get("VGPRsSpill", 0) == 0, "%s spills: %s %s" % (what, k, rows[k])
+
+
+_PLAN_PROGRAM = r"""
+#include "hb_plan.hpp"
+#include <cstdio>
+#define G(a, b, c, d, e) printf("table group<%d,%d,%d,%d,%d>\n", a, b, c, d, e);
+#define P(a, b) printf("table persist<%d,%d>\n", a, b);
+#define D(a) printf("table dense<%d>\n", a);
+#define F(a, b, c) printf("table fwd<%d,%d,%d>\n", a, b, c);
+int main()
+{
+    HB_GROUP_KERNELS(G) HB_PERSIST_KERNELS(P) HB_DENSE_KERNELS(D) HB_FWD_KERNELS(F)
+    for (int model = 1; model <= 6; model++)
+    for (int nf = 2; nf <= (model == 6 ? 8 : 2); nf++)
+    for (int P : {64, 128, 256, 512}) for (int Lv = 0; Lv <= 6; Lv++) for (int D = 1; D <= 8; D++) {
+        if ((Lv + 1) * D - 1 > plan_band_limit(P, Lv, D)) continue; // (what hb_pipeline_geometry lets through)
+        for (int bits = 0; bits < 16; bits++) {
+            const bool cert = bits & 8, ca = bits & 4, ea = bits & 2, lg = bits & 1;
+            const hb_sweep_plan p = plan_sweep(hb_sweep_shape{model, nf, P, Lv, D, std::max((Lv + 1) * D - 1, Lv), cert, ca, ea, lg, true});
+            printf("%d %d %d %d %d %d %d %d %d | ", model, nf, P, Lv, D, cert, ca, ea, lg);
+            if (!p.ok) { puts("unsupported"); continue; }
+            if (p.chain == HB_CHAIN_GROUP) printf("group<%d,%d,%d,%d,%d> ", p.ct[0], p.ct[1], p.ct[2], p.ct[3], p.ct[4]);
+            else if (p.chain == HB_CHAIN_PERSIST) printf("persist<%d,%d> ", p.ct[0], p.ct[1]);
+            else printf("dense<%d> ", p.ct[0]);
+            if (p.fwd[0]) printf("fwd<%d,%d,%d> ", p.fwd[0], p.fwd[1], p.fwd[2]); else printf("- ");
+            printf("warm=%d/%d warm_r=%d/%d/%d fcorr=%d\n", p.warm, p.warm_ahead, p.warm_r, p.warm_r_ahead, p.warm_r_Lb, (int)p.fcorr);
+        }
+    }
+}
+"""
+
+
+def test_every_sweep_plan_equals_the_recorded_dispatch_and_names_a_built_kernel(tmp_path):
+    """plan_sweep (hibayes_amd/csrc/hb_plan.hpp: plain C++, compiled here with g++) decides which chain kernel a sweep of the persistent pipeline
+    runs and what runs beside it. Every input of the domain — model 1..6 (n_fold 2..8 for BayesR), panel 64..512, every geometry the band limit
+    lets through, certificate, the two "alone" switches, short / long range — against tests/golden/sweep_plan_table.json, which was recorded from
+    the dispatch as it stood inside enqueue_sweep_pipeline before it became this function. And both ways between the plans and the lists of
+    instantiations hb_kernels.hip builds its launch tables from (HB_*_KERNELS, the same header): a plan names only listed kernels, and every
+    listed kernel is some input's plan."""
+    import json
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    src, exe = tmp_path / "plan.cpp", tmp_path / "plan"
+    src.write_text(_PLAN_PROGRAM)
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(root, "hibayes_amd", "csrc"), str(src), "-o", str(exe)])
+    listed, got = set(), {}
+    for line in subprocess.check_output([str(exe)]).decode().splitlines():
+        if line.startswith("table "):
+            listed.add(line[6:])
+        else:
+            k, v = line.split(" | ")
+            got[tuple(int(x) for x in k.split())] = v
+    assert len(listed) == 13 + 8 + 2 + 6
+    table = json.load(open(os.path.join(root, "tests", "golden", "sweep_plan_table.json")))
+    want = {}
+    for key, gi in table["rows"].items():
+        for Lv, row in enumerate(table["grids"][gi]):
+            for D, ch in enumerate(row, start=1):
+                if ch != ".":
+                    model, nf, P, cert, ca, ea, lg = (int(x) for x in key.split())
+                    want[(model, nf, P, Lv, D, cert, ca, ea, lg)] = "unsupported" if ch == "!" else table["outcomes"][ch]
+    assert len(want) == 29568 and sum(v == "unsupported" for v in want.values()) == 364
+    assert set(got) == set(want), "the domains differ (plan_band_limit?)"
+    wrong = ["%s: %s, recorded %s" % (k, got[k], want[k]) for k in sorted(want) if got[k] != want[k]]
+    assert not wrong, "%d plans differ from the record (model n_fold P Lv D cert chain_alone env_alone long_range), the first:\n%s" % (len(wrong), "\n".join(wrong[:20]))
+    named = set()
+    for v in got.values():
+        if v != "unsupported":
+            named.update(x for x in v.split()[:2] if x != "-")
+    assert named <= listed, "plans name kernels that are in no launch table: %s" % sorted(named - listed)
+    assert listed <= named, "listed kernels that no input of the domain runs: %s" % sorted(listed - named)
