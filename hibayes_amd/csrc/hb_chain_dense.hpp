@@ -372,9 +372,8 @@ __global__ __launch_bounds__(256) void k_fold_dense(chain_view v, persist_view p
             if (__any(HBD_SENT(d))) {
                 const double *dp = dptr(st);
                 const unsigned long long t0 = wall_clock64();
-                unsigned looks = 0;
                 for (;;) {
-                    d = (hb_fresh_look(looks) && HBD_SENT(d)) ? ld_fresh(dp) : ld_sc1(dp);
+                    d = ld_sc1(dp);
                     if (!__any(HBD_SENT(d))) break;
                     const bool own = wall_clock64() - t0 > HB_TIMEOUT_TICKS;
                     if (ld_flag(pv.flags + HB_FLAG_ABORT) || own) {
@@ -385,9 +384,7 @@ __global__ __launch_bounds__(256) void k_fold_dense(chain_view v, persist_view p
                         dead = true;
                         break;
                     }
-                    hb_poll_pause(looks, 1);
-                    hb_long_wait(looks);
-                    looks++;
+                    hb_poll_pause(1);
                 }
                 if (st + 1 < nsteps) dn = ld_sc1(dptr(st + 1)); // (looked at before this step was there: likely stale)
             }

@@ -63,11 +63,6 @@
 #ifndef HBG_CH2MAX
 #define HBG_CH2MAX 31
 #endif
-#ifndef HB_CHAINDBG
-#define HB_CHAINDBG 0 /* development aid: progress markers of the chain workgroup in flags[20..22] (group, phase, rounds) */
-#endif
-#define HBG_DBGW(code) do { if (HB_CHAINDBG && lane == 0) st_flag(pv.flags + 24 + wave, (unsigned)(code)); } while (0)
-#define HBG_DBG(code) do { if (HB_CHAINDBG && t == 0) { st_flag(pv.flags + 20, (unsigned)gcount); st_flag(pv.flags + 21, (unsigned)(code)); } } while (0)
 #ifndef HBG_CERT_MARGIN
 #define HBG_CERT_MARGIN 1.0
 #endif
@@ -152,8 +147,6 @@ __device__ __forceinline__ void chain_group_body(const hb_sweep_in *__restrict__
         __syncthreads();
     }
     int gslot = 0; // ring slot of the group's first panel
-    HBG_DBG(100); // staged, about to open the first group
-    if (HB_CHAINDBG && t == 0) st_flag(pv.flags + 43, (unsigned)wall_clock64());
     for (int gp0 = pv.p0; ok && gp0 < np; gp0 += D) {
         const int Dg = min(D, np - gp0);
         HBG_BEGIN();
@@ -212,12 +205,9 @@ __device__ __forceinline__ void chain_group_body(const hb_sweep_in *__restrict__
             HBG_MARK(19); // (the opening's values are in registers)
             if (__any(bad)) { // the mat-vec (or k_fwd) has not delivered (all of) this group yet: look again
                 const unsigned long long t0 = wall_clock64();
-                if (HB_CHAINDBG && t == 0) st_flag(pv.flags + 44, (unsigned)t0);
                 for (unsigned looks = 0;; looks++) {
                     bad = false;
-                    if (HB_CHAINDBG && t == 0) st_flag(pv.flags + 45, (unsigned)wall_clock64());
-                    if (hb_fresh_look(looks)) { // (uniform; what is still missing is read at the memory side, ld_fresh in hb_handoff.hpp: once in
-                        // HB_FRESH_EVERY looks; a word that HAS arrived is kept — it never changes again)
+                    if (hb_fresh_look(looks)) { // (never, see hb_handoff.hpp: what is still missing read at the memory side; a word that HAS arrived is kept)
 #pragma unroll
                         for (int i = 0; i < HBG_DM; i++) {
                             const size_t j = (size_t)(gp0 + min(i, Dg - 1)) * P + t;
@@ -240,11 +230,6 @@ __device__ __forceinline__ void chain_group_body(const hb_sweep_in *__restrict__
                         bad = sdf != sdf;
                     }
                     if (!__any(bad)) break;
-                    if (HB_CHAINDBG) { // what is missing, as the chain sees it: lanes with a NaN sum per wave, and thread 0's first words
-                        const unsigned long long bm = __ballot(bad);
-                        if (lane == 0) st_flag(pv.flags + 32 + wave, (unsigned)__popcll(bm));
-                        if (t == 0) { st_flag(pv.flags + 22, looks); st_flag(pv.flags + 40, (unsigned)(__double_as_longlong(dj[0]) >> 32)); st_flag(pv.flags + 41, (unsigned)(__double_as_longlong(fc[0]) >> 32)); st_flag(pv.flags + 42, far_in ? 1u : 0u); }
-                    }
                     {   // (advisor finding, round 5) "not delivered" is the sentinel's BIT PATTERN; a delivered word that is a NaN or an infinity (an upstream
                         // overflow) makes the sum a NaN too and would be polled until the time-out, replayed three times and reported as a time-out. If
                         // every word of a lane with a NaN sum is there, the fault is numerical: stop now and say so (fetch_acc: h_flags[15])
@@ -261,7 +246,6 @@ __device__ __forceinline__ void chain_group_body(const hb_sweep_in *__restrict__
                         break;
                     }
                     __builtin_amdgcn_s_sleep(2);
-                    hb_long_wait(looks);
                 }
             }
             HBG_MARK(20);
@@ -279,7 +263,6 @@ __device__ __forceinline__ void chain_group_body(const hb_sweep_in *__restrict__
             }
         }
         HBG_ACC(0);
-        HBG_DBG(1); // the group's dots are in hand
         const int32_t *gblk0 = v.gram + (size_t)gp0 * (pv.Lg + 1) * PP; // block l = 0 of the group's first panel
         const size_t pstep = (size_t)(pv.Lg + 2) * PP;                   // block l of panel p -> block l + 1 of panel p + 1
         // panels ahead that are owed the corrections by THIS workgroup (with k_fwd beside it: the next group's only)
@@ -317,7 +300,6 @@ __device__ __forceinline__ void chain_group_body(const hb_sweep_in *__restrict__
             if (lane < HBG_DM) wcnt[lane * 8 + wave] = cntv; // (one write per wave)
             if (t == 0) misc[1] = Dg * P;
             __syncthreads(); // B1
-            HBG_DBG(2);
             if (misc[2]) { ok = false; break; }
             int total, myscan;
             {   // exclusive scan of the (panel, wave) counts in every wave: lane = panel * 8 + wave
@@ -346,9 +328,7 @@ __device__ __forceinline__ void chain_group_body(const hb_sweep_in *__restrict__
                     inrm |= 1u << i;
                 }
             }
-            HBG_DBGW(21);
             __syncthreads(); // B2
-            HBG_DBGW(22);
             HBG_ACC(2);
             const int pos_hi = misc[1];
             // (2b) + (3) ONE round trip for both (round 5: they used to be two, the gather's loads issued only after the exact data had come back —
@@ -374,7 +354,6 @@ __device__ __forceinline__ void chain_group_body(const hb_sweep_in *__restrict__
                 for (int q = 1; q < 8; q++)
                     if (q < nq) gq[q] = gather_one(q); // (round 6: seven unconditional batches above eight candidates cost BayesR's 17-candidate rounds five batches of index arithmetic for nothing)
             }
-            HBG_DBGW(23);
             for (unsigned left = inrm; __any(left != 0u);) {
                 const bool mine = left != 0u;
                 const int i = mine ? __ffs((int)left) - 1 : 0;
@@ -431,9 +410,7 @@ __device__ __forceinline__ void chain_group_body(const hb_sweep_in *__restrict__
                     cg[idx] = gval;
                 }
             }
-            HBG_DBGW(25);
             __syncthreads(); // B3
-            HBG_DBG(3);
             HBG_ACC(3);
             bool stage_wait = false; // (per wave) this wave has pieces in flight
             if constexpr (CERT) {    // (the next group's records: by the waves that would otherwise stand at B4 while wave 0 walks the serial chain)
@@ -532,7 +509,6 @@ __device__ __forceinline__ void chain_group_body(const hb_sweep_in *__restrict__
                 if (stage_wait) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // (the pieces have landed: these waves had nothing else to do)
             }
             __syncthreads(); // B4
-            HBG_DBG(4);
             HBG_ACC(4);
             const int nmoves = misc[0];
             // ---- (4b) CERT: decide the passed-over markers from the rank-one part of the moves and the bound on the rest ----
@@ -793,7 +769,6 @@ __device__ __forceinline__ void chain_group_body(const hb_sweep_in *__restrict__
             // the next group's first barrier the whole workgroup, ~25 000 cycles per group: profiles/r04_group_timeline_*.txt)
             if (lane == 0) st_flag(pv.flags + HB_FLAG_CHAIN_DONE, (unsigned)(gp0 + Dg));
         }
-        HBG_DBG(9);
         HBG_ACC(8);
         HBG_CNT(10, nmv_grp);
         HBG_CNT(13, nround);
@@ -879,10 +854,9 @@ __device__ __forceinline__ void fwd_body(const chain_view &v, const persist_view
             for (int i = 0; i < t && i < Dg; i++) {
                 int c = ld_sc1(&v.ev_count[(size_t)(gp0 + i) * HB_EVS]);
                 const unsigned long long t0 = wall_clock64();
-                unsigned looks = 0;
                 while (c < 0 && !ld_flag(pv.flags + HB_FLAG_ABORT) && wall_clock64() - t0 < HB_TIMEOUT_TICKS) {
                     __builtin_amdgcn_s_sleep(2);
-                    c = ld_poll(&v.ev_count[(size_t)(gp0 + i) * HB_EVS], looks++);
+                    c = ld_sc1(&v.ev_count[(size_t)(gp0 + i) * HB_EVS]);
                 }
                 if (c < 0) { st_flag(pv.flags + HB_FLAG_ABORT, 1u); c = 0; s_ok = 0; }
                 a += c;
@@ -899,12 +873,10 @@ __device__ __forceinline__ void fwd_body(const chain_view &v, const persist_view
                 int ix = ld_sc1(&v.ev_idx[src]);
                 double dl = ld_sc1(&v.ev_delta[src]);
                 const unsigned long long t0 = wall_clock64();
-                unsigned looks = 0;
                 while ((ix < 0 || __double_as_longlong(dl) == -1ll) && !ld_flag(pv.flags + HB_FLAG_ABORT) && wall_clock64() - t0 < HB_TIMEOUT_TICKS) {
                     __builtin_amdgcn_s_sleep(2);
-                    ix = ld_poll(&v.ev_idx[src], looks);
-                    dl = ld_poll(&v.ev_delta[src], looks);
-                    looks++;
+                    ix = ld_sc1(&v.ev_idx[src]);
+                    dl = ld_sc1(&v.ev_delta[src]);
                 }
                 if (ix < 0 || __double_as_longlong(dl) == -1ll) { st_flag(pv.flags + HB_FLAG_ABORT, 1u); ix = 0; dl = 0.0; }
                 s_pos[b + k] = i * P + ix;

@@ -25,54 +25,12 @@ struct persist_view {
 };
 
 // (HB_LBMAX, the band this chain folds into: hb_plan.hpp)
-#ifndef HB_APPLY_PREFIX
-#define HB_APPLY_PREFIX 1 /* a wave applies only the prefix of a round's moves that can touch it */
-#endif
-#ifndef HB_FOLD_GATHER
-#define HB_FOLD_GATHER 1 /* the fold's moves gathered with one LDS pass + v_readlane */
-#endif
-#ifndef HB_DECIDE_PAR
-#define HB_DECIDE_PAR 1
-#endif
-#ifndef HB_FAST1
-#define HB_FAST1 1 /* single-candidate panels skip the rounds */
-#endif
-#ifndef HB_NPF
-#define HB_NPF 1 /* candidates per panel whose band rows are requested ahead (1 or 2) */
-#endif
 #define HB_CROWD 8 /* candidates in a round from which their Gram entries are gathered up front */
-#ifndef HB_R_EARLY
-#define HB_R_EARLY 1 /* with k_fwd beside the chain: the next panel's dots and k_fwd's sums are (re-)requested right after a panel's rounds */
-#endif
-#ifndef HB_R_FOLDPRE
-#define HB_R_FOLDPRE 1 /* ... and the band rows of its first 32 moves before the publish, used after the results */
-#endif
-#ifndef HB_ROW_TRI
-#define HB_ROW_TRI 1 /* panel 512: the row cache keeps a row of the panel's second half as its second 1-KiB piece alone (k_hotlist) */
-#endif
-#ifndef HB_RING_NODOTS
-#define HB_RING_NODOTS 1 /* with k_fwd beside the chain the ring does not fetch the dots three panels ahead: they are never there yet, and the line it read stayed in the XCD's L2 as the copy the early request one panel ahead then got (sentinel at 80 % of the panels; 0 % without) */
-#endif
 #ifndef HB_FPRE_N
 #define HB_FPRE_N 64 /* band rows (moves) requested before the publish: 16, 32, 48 or 64 */
 #endif
-#ifndef HB_FILL_ALL
-#define HB_FILL_ALL 1 /* the ring waves issue their share of the row cache's pieces too (0: the four non-ring waves alone) */
-#endif
-#ifndef HB_APPLY_PROG
-#define HB_APPLY_PROG 0 /* (A/B, off) ... and while the serial pass is still running: every verified block of it publishes its moves' records and the waves at the barrier apply them. Measured: apply + violation barrier 6 500 -> 950 cycles, but the serial pass 7 800 -> 13 000 (the publishing, and SGPR spills in its loop at 254 VGPRs): 52.7 sweeps/s against 52.8 */
-#endif
-#ifndef HB_APPLY_LEAN
-#define HB_APPLY_LEAN 1 /* a crowded round's moves are applied from 16-byte records read with one broadcast LDS load (0: the round-3 loop) */
-#endif
 #ifndef HB_SPEC_B
 #define HB_SPEC_B 16 /* steps per speculated block */
-#endif
-#ifndef HB_R_SPEC
-#define HB_R_SPEC 1 /* crowded rounds of a mixture model: the serial pass in blocks of eight steps on speculated classes */
-#endif
-#ifndef HB_SERIAL_BRANCHLESS
-#define HB_SERIAL_BRANCHLESS 1
 #endif
 
 // Row-cache list of every panel, in marker order, capped at nslot rows: the markers that are certain to move
@@ -127,11 +85,11 @@ __global__ __launch_bounds__(512) void k_hotlist(const hb_sweep_in *__restrict__
     const int raw = sbase + __popcll(hmask & ((1ull << lane) - 1ull));
     // Where a listed row sits in the chain's row cache, in units of 64 ints: base64 * 64 + column. Row k is only ever used at
     // columns > k (a move touches later markers), so at panel 512 — two 1-KiB pieces per row — a row of the panel's second half is
-    // kept as its second piece alone: the cache holds a third more rows in the same LDS (HB_ROW_TRI). The list is in marker order,
+    // kept as its second piece alone: the cache holds a third more rows in the same LDS. The list is in marker order,
     // so the whole rows (n2 of them) come first; a half row's base points 256 columns before its piece (shifted by one piece when
     // there is no whole row before it, so that no base is negative). [0] = rows that fit, [1] = rows listed, [2] = whole rows among
     // those that fit, [3] = that shift, in pieces.
-    const bool tri = HB_ROW_TRI && P == 512;
+    const bool tri = P == 512;
     int n2 = tot;
     if (tri) {
         n2 = 0;
@@ -172,7 +130,7 @@ __device__ __forceinline__ void fold_forward(double *corrL, int R, const int32_t
         int gv[LB][FW];
         int kk[FW];
         double dl[FW];
-        if (HB_FOLD_GATHER && FW >= 8) { // (the wide batches of the narrow bands: dense sweeps; two moves at a time gain nothing)
+        if (FW >= 8) { // (the wide batches of the narrow bands: dense sweeps; two moves at a time gain nothing)
             // the batch's moves in ONE pass over LDS: lane f reads move e0 + f, every lane then takes them lane by lane
             // (v_readlane: wave-uniform row addresses without a read-and-wait per move); a lane past the list holds row 0, delta 0
             const int lane_ = t & 63, e = e0 + lane_;
@@ -274,7 +232,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // chain itself folds a panel's moves into the NEXT panel only (half of the band rows of a dense sweep leave its compute unit)
     const bool fwd = pv.fcorr != nullptr;
     double *fcring = reinterpret_cast<double *>(oring + (size_t)4 * (((((size_t)12 * P + 1023) >> 10) << 10) + 1024));
-    // one crowded round's moves as the apply reads them (HB_APPLY_LEAN): {byte offset of the row in the row cache, marker, change}
+    // one crowded round's moves as the apply reads them: {byte offset of the row in the row cache, marker, change}
     // for the moves whose row is cached — 64 + 8 records, the list is padded with changes of zero — and {-, marker, change} for the others
     int4 *ap_rec = reinterpret_cast<int4 *>(fcring + (size_t)2 * P);
     int4 *ms_rec = ap_rec + 72;
@@ -339,7 +297,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 const int off = i << 10; // whole piece inside one segment
                 // (with k_fwd beside the chain the dots come with the early request one panel ahead: three panels ahead they are
                 // never there yet, and the line read now would be the copy the early request then finds in this XCD's L2)
-                if (HB_RING_NODOTS && HB_R_EARLY && fwd && off < 8 * P && x > pv.p0) continue;
+                if (fwd && off < 8 * P && x > pv.p0) continue;
                 dma_piece_s(off < 8 * P ? dsrc + off : fsrc + (off - 8 * P), dst + (unsigned)off, true);
             } else {
                 const int off = (i << 10) + lane * 16;
@@ -355,7 +313,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         }
     };
     int my_pieces = __builtin_amdgcn_readfirstlane(wave < RW ? (NPC - wave + RW - 1) / RW : 0); // ring pieces this wave issues per group
-    if (HB_RING_NODOTS && HB_R_EARLY && fwd && P >= 128 && wave < RW) { // (without the dots' pieces)
+    if (fwd && P >= 128 && wave < RW) { // (without the dots' pieces)
         int c = 0;
         for (int i = __builtin_amdgcn_readfirstlane(wave); i < NPC; i += RW) c += (i == NPC - 1 || (i << 10) >= 8 * P) ? 1 : 0;
         my_pieces = c;
@@ -378,7 +336,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         const int *hl0 = pv.hotpack + (size_t)pv.p0 * HB_HS;
         n_nhot = hl0[0];
         const int32_t *gp0 = v.gram + (size_t)pv.p0 * (pv.Lg + 1) * P * P;
-        if (HB_ROW_TRI && P == 512) { // (the layout k_hotlist describes: whole rows first, then second pieces alone)
+        if (P == 512) { // (the layout k_hotlist describes: whole rows first, then second pieces alone)
             const int n2s = hl0[2], sh = hl0[3], items = n_nhot + n2s;
             for (int it = wave; it < items; it += S) {
                 const int r = it < 2 * n2s ? it >> 1 : it - n2s, pc = it < 2 * n2s ? (it & 1) << 8 : 256;
@@ -415,7 +373,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         // the barrier below hands it to everybody before the next panel's take
         if (wave < RW) {
             // (what may stay in flight: the youngest ring group — none was issued behind the previous panel near the end of the range —
-            // and, HB_FILL_ALL, the row-cache pieces this wave issued behind it: the counter wants an immediate, hence the ladder)
+            // and the row-cache pieces this wave issued behind it: the counter wants an immediate, hence the ladder)
             const int keep = (S == 1) ? 0 : ((p + HB_RD - 2 < np || p == pv.p0) ? my_pieces : 0) + my_rowp;
             switch (min(keep, 31)) {
 #define HB_VMC(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
@@ -427,14 +385,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         }
         // ---- take over the panel: LDS only ----
         const bool use_fc = fwd && p >= pv.p0 + 2; // (the first two panels of a range have nobody two panels before them)
-        // (k_fwd's sums — and, HB_R_EARLY, a second copy of the panel's dots — were brought in by the ring waves during the previous
+        // (k_fwd's sums — and a second copy of the panel's dots — were brought in by the ring waves during the previous
         // panel, after its barrier — their producers need the panels before — so unlike the ring groups no earlier barrier has handed
         // them to the other waves yet: one extra barrier per panel, a few hundred cycles)
         HB_STAMP(20);
 #if HB_STAMPS
         if (v.dbg && lane == 0 && wave < 8) v.dbg[(size_t)p * 32 + 22 + wave] = clock64(); // (each wave's arrival at the barrier)
 #endif
-        if (HB_R_EARLY ? fwd : use_fc) __syncthreads();
+        if (fwd) __syncthreads();
         HB_STAMP(21);
         double dj = reinterpret_cast<const double *>(oslotp)[t];
         const float fthr = reinterpret_cast<const float *>(oslotp + 8 * P)[t];
@@ -445,9 +403,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             HB_STAMP_VAL(11, bad ? 1 : 0);
             if (__any(bad || badf)) { // this wave's dots (or k_fwd's sums) had not been written when the ring slot was filled: re-read until they are
                 const unsigned long long t0 = wall_clock64();
-                unsigned looks = 0;
                 for (;;) {
-                    const bool fresh = hb_fresh_look(looks);
+                    const bool fresh = hb_fresh_look(0u); // (never, see hb_handoff.hpp)
                     if (bad) {
                         dj = fresh ? ld_fresh(&v.dsum[j]) : ld_sc1(&v.dsum[j]);
                         bad = __double_as_longlong(dj) == HB_SENT;
@@ -465,9 +422,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                         aborted = true;
                         break;
                     }
-                    hb_poll_pause(looks, 1);
-                    hb_long_wait(looks);
-                    looks++;
+                    hb_poll_pause(1);
                 }
             }
         }
@@ -497,7 +452,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         }
         HB_STAMP(1);
         __syncthreads(); // the panel's one fixed barrier: wcnt[] staged, ring group of panel p + 1 published; everybody is done with panel p-1
-        int tot0 = 0, c1 = -1, c2 = -1; // candidates in the panel; its first two (thread = marker index in the panel)
+        int tot0 = 0, c1 = -1, c2 = -1; // candidates in the panel; its first two (thread = marker index in the panel; the second is not used, see k2)
         {
             int w8[8];
             hb_read8(wcnt, w8);
@@ -536,7 +491,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         int nrerun = 0, nround = 0;
         HB_STAMP_VAL(15, tot0);
 #endif
-        int pre[2][NPL > 0 ? NPL : 1];
+        int pre[NPL > 0 ? NPL : 1];
         if (tot0 > 0) {
             // the exact per-marker data, for the candidates only (one CU pulls ~18 bytes per clock from memory — measured,
             // tools/rowfetch_bench.hip — and every thread's copy of six arrays was a quarter of a move-panel's traffic). A marker
@@ -556,21 +511,23 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 }
             }
             const double thr_lo = (double)fthr; // <= thr[0]; NaN for a monomorphic marker (every comparison false)
-            // (3) ... and, requested right behind it, the band-Gram rows that the panel's first two candidates would fold forward if
-            // they move (in the sparse regime a candidate almost always does, and a panel rarely has more than two): by the time the
-            // rounds are through they have landed, and the fold at the end of the panel costs no round trip. Always 2 * NPL loads, so
+            // (3) ... and, requested right behind it, the band-Gram rows that the panel's first candidate would fold forward if
+            // it moves (in the sparse regime a candidate almost always does): by the time the
+            // rounds are through they have landed, and the fold at the end of the panel costs no round trip. Always NPL loads, so
             // that the counted waits below are exact; rows of panels that do not exist are read from the panel's own block.
             if (NPL > 0) {
                 __builtin_amdgcn_sched_barrier(0); // (the order of issue is the point: hipcc must not move these ahead of the data above)
                 const int lmax = np - 1 - p;
                 const size_t PP = (size_t)P * P, step = (size_t)(pv.Lg + 2) * PP;
+                // (k2: the second candidate, whose rows were requested too when the look-ahead covered two. Nothing reads it, but without it and
+                // c2's decode hipcc numbers this kernel's registers differently: they go with the next change to this kernel)
                 const int k1 = __builtin_amdgcn_readfirstlane(c1), k2 = __builtin_amdgcn_readfirstlane(c2 < 0 ? c1 : c2);
+                (void)k2;
                 const int32_t *blk = v.gram + ((size_t)(p + 1) * (pv.Lg + 1) + 1) * PP;
 #pragma unroll
                 for (int l = 1; l <= NPL; l++) {
                     const int32_t *b = l <= lmax ? blk : gp;
-                    pre[0][l - 1] = (b + (size_t)k1 * P)[t];
-                    if (HB_NPF > 1) pre[1][l - 1] = (b + (size_t)k2 * P)[t];
+                    pre[l - 1] = (b + (size_t)k1 * P)[t];
                     blk += step;
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -588,7 +545,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             // five. A marker pushed over its threshold sends the panel through the general rounds below, exactly as a
             // rolled-back round would.
             bool fast_done = false;
-            if (HB_FAST1 && tot0 == 1) {
+            if (tot0 == 1) {
                 if (t == c1) {
                     cs_d[0] = rhs;
                     cs_d[64] = gold;
@@ -600,7 +557,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     }
                     cs_slot[0] = myslot;
                 }
-                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(HB_NPF * NPL) : "memory"); // (the row cache's DMA pieces, as in the rounds)
+                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPL) : "memory"); // (the row cache's DMA pieces, as in the rounds)
                 __syncthreads();
                 const double crhs = cs_d[0], cgold = cs_d[64];
                 const int cslot = cs_slot[0];
@@ -704,8 +661,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     cs_slot[rank] = myslot;
                 }
                 // the row cache was filled by LDS-DMA a panel ago: every wave drains its own pieces before the barrier — everything
-                // older than the 2 * npl candidate rows requested above, which may stay in flight (the queue completes in order)
-                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(HB_NPF * NPL) : "memory");
+                // older than the NPL candidate rows requested above, which may stay in flight (the queue completes in order)
+                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPL) : "memory");
                 __syncthreads();
                 if (t_lo == 0 && nev0 == 0 && !forced) HB_STAMP(12);
                 const int t_hi = tot > 64 ? *s_thi : P;
@@ -757,7 +714,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                         const double q = rhsv * rhsv;
                         cls = 0;
                         // (thresholds ascend, and below thr[0] the result is zeroed anyway: class 1's coefficients need no select)
-#if HB_DECIDE_PAR
                         // every class's conditional mean at once (independent fused multiply-adds), then ONE select per class on the
                         // result instead of two on its coefficients: the same number, a shorter dependent chain per serial step
                         double gsel = fma(rhsv, cinvv[0], csdz[0]);
@@ -769,18 +725,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                             gsel = ge ? fma(rhsv, cinvv[c], csdz[c]) : gsel;
                         }
                         gn = (q >= cthr[0]) ? gsel : 0.0; // (class > 0 <=> q >= thr[0])
-#else
-                        double iv = cinvv[0], sz = csdz[0];
-                        cls = q >= cthr[0] ? 1 : 0;
-#pragma unroll
-                        for (int c = 1; c < K1; c++) {
-                            const bool ge = q >= cthr[c];
-                            cls += ge ? 1 : 0;
-                            iv = ge ? cinvv[c] : iv;
-                            sz = ge ? csdz[c] : sz;
-                        }
-                        gn = (q >= cthr[0]) ? fma(rhsv, iv, sz) : 0.0; // (class > 0 <=> q >= thr[0])
-#endif
                         if (K1 == 1 && model == 5 && fabs(gn) < 1e-6) gn = 1e-6; // (BayesL is a one-class model)
                     };
                     if (crowded) {
@@ -804,7 +748,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                                 gnx = (double)r1;
                                 r1 = r2;
                             }
-                        } else if (HB_R_SPEC && K1 > 1) {
+                        } else if (K1 > 1) {
                             // A mixture model (BayesR: ~60 candidates in a panel, half of them certain movers): a step of the exact
                             // loop below is ~25 dependent instructions, because the class of lane k has to be decided from the rhs
                             // the step before it left. But within a class the new effect is LINEAR in rhs, and a lane's class
@@ -827,7 +771,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                                     b = ge ? csdz[c] : b;
                                 }
                             };
-                            int cls_s, nsp = 0, nmp = 0; // (records published so far: cached rows, others)
+                            int cls_s;
                             double a_s, b_s;
                             classify(crhs, cls_s, a_s, b_s);
                             constexpr int SB = K1 > 3 ? 8 : HB_SPEC_B; // (steps per block)
@@ -857,31 +801,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #endif
                                     crhs = save;
                                 }
-                                if (HB_APPLY_LEAN && HB_APPLY_PROG) {
-                                    // the block is final: its moves go out now, as the records the other waves' apply reads — they
-                                    // are standing at the round's barrier otherwise (the same records, at the same places, as the
-                                    // listing after the pass writes once more)
-                                    const double dmb = fma(crhs, a_s, b_s) - cgold;
-                                    const bool mvl = inblk && dmb != 0.0;
-                                    const unsigned long long mvb = __ballot(mvl), mvs = mvb & ~noslot, mvm = mvb & noslot, below = (1ull << lane) - 1ull;
-                                    if (mvl) {
-                                        const long long db = __double_as_longlong(dmb);
-                                        if (cslot >= 0) ap_rec[nsp + __popcll(mvs & below)] = make_int4(cslot << 8, ct, (int)db, (int)(db >> 32));
-                                        else ms_rec[nmp + __popcll(mvm & below)] = make_int4(0, ct, (int)db, (int)(db >> 32));
-                                    }
-                                    nsp += __popcll(mvs);
-                                    nmp += __popcll(mvm);
-                                    if (lane == 0) {
-                                        __hip_atomic_store(&cnts[3], nmp, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-                                        __hip_atomic_store(&cnts[2], nsp, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-                                    }
-                                }
                             }
                         } else
                         for (int k = 0; k < ncr; k++) {
                             const double gcur = gnx;
                             r2 = cg[min(k + 2, ncr - 1) * 64 + lane];
-#if HB_SERIAL_BRANCHLESS
                             // (no test for "lane k stays at zero": its change is then an exact zero, and a ballot, a scalar test and a
                             // branch per step cost more than the decide they skip)
                             {
@@ -891,20 +815,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                                 const double dk = readlane_f64(gn - cgold, k);
                                 crhs = fma(-gcur, dk, crhs);
                             }
-#else
-                            bool stays = false;
-                            if (!((hotm >> k) & 1ull)) { // (uniform) a marker at zero moves only if it crosses its entry threshold
-                                const unsigned long long mv = __ballot(crhs * crhs >= cthr[0]) & vmask;
-                                stays = !((mv >> k) & 1ull);
-                            }
-                            if (!stays) {
-                                int cls;
-                                double gn;
-                                decide(crhs, cls, gn);
-                                const double dk = readlane_f64(gn - cgold, k);
-                                crhs = fma(-gcur, dk, crhs);
-                            }
-#endif
                             gnx = (double)r1; // (landed an iteration ago)
                             r1 = r2;
                         }
@@ -956,7 +866,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                         res_c[lane] = rc;
                         res_g[lane] = rg;
                         if (lane == 0) cnts[0] = nev0 + __popcll(moved);
-                        if (HB_APPLY_LEAN && crowded) { // (the same moves once more, as the other waves' apply wants them)
+                        if (crowded) { // (the same moves once more, as the other waves' apply wants them)
                             const unsigned long long mvs = moved & ~noslot, mvm = moved & noslot, below = (1ull << lane) - 1ull;
                             const long long db = __double_as_longlong(dmine);
                             if (lv && dmine != 0.0) {
@@ -973,73 +883,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                         }
                     }
                 }
-                // ---- the apply of a crowded round, WHILE the serial pass runs (HB_APPLY_PROG): the other waves take the records of every
-                // block the pass has finished (the count is released after them) instead of standing at the barrier below until the
-                // whole pass is through; wave 0 does its own non-candidates afterwards. Cached rows in marker order, whatever the
-                // blocks' timing (a block's records are appended in marker order and applied in list order), the others after the
-                // pass — the same sums bit for bit as the apply behind the barrier.
-                double acc_prog = rhs;
-                if (HB_APPLY_LEAN && HB_APPLY_PROG && crowded) {
-                    const bool doap0 = undec && !inr;
-                    const bool anyap = __any(doap0);
-                    int lo = 0;
-                    // (the wave that shares wave 0's SIMD — four SIMDs, waves dealt round-robin — stays asleep until the pass is through:
-                    // every instruction it issues is an issue slot the serial pass does not get: 7 800 -> 13 000 cycles measured)
-                    if (S == 8 && wave == 4)
-                        while (!__hip_atomic_load(&cnts[4], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)) __builtin_amdgcn_s_sleep(8);
-                    for (;;) {
-                        const int fin = __hip_atomic_load(&cnts[4], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        const int hi = __builtin_amdgcn_readfirstlane(__hip_atomic_load(&cnts[2], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP));
-                        if (anyap && hi > lo) {
-                            const int kl = lo + lane < hi ? ap_rec[lo + lane].y : 0x7fffffff; // (a round has at most 64 moves)
-                            const int n_in = __popcll(__ballot(kl < (t | 63)));
-                            const int n_un = __popcll(__ballot(kl < (t & ~63))) & ~7;
-                            for (int e0 = lo; e0 < lo + n_un; e0 += 8) { // moves of markers before the wave's first: no select
-                                int4 rc[8];
-                                int gv[8];
-#pragma unroll
-                                for (int q = 0; q < 8; q++) rc[q] = ap_rec[e0 + q];
-#pragma unroll
-                                for (int q = 0; q < 8; q++) gv[q] = reinterpret_cast<const int *>(smem + rc[q].x)[t];
-#pragma unroll
-                                for (int q = 0; q < 8; q++)
-                                    acc_prog = fma(-(double)gv[q], __longlong_as_double(((long long)rc[q].w << 32) | (unsigned)rc[q].z), acc_prog);
-                            }
-                            for (int e0 = lo + n_un; e0 < lo + n_in; e0 += 8) { // the wave's own stretch (records past `hi` may be half written: never used)
-                                int4 rc[8];
-                                int gv[8];
-#pragma unroll
-                                for (int q = 0; q < 8; q++) rc[q] = ap_rec[e0 + q];
-#pragma unroll
-                                for (int q = 0; q < 8; q++) gv[q] = reinterpret_cast<const int *>(smem + (rc[q].x & 0x3fffc))[t];
-#pragma unroll
-                                for (int q = 0; q < 8; q++) {
-                                    const double nw = fma(-(double)gv[q], __longlong_as_double(((long long)rc[q].w << 32) | (unsigned)rc[q].z), acc_prog);
-                                    acc_prog = (e0 + q < hi && rc[q].y < t) ? nw : acc_prog;
-                                }
-                            }
-                        }
-                        lo = max(lo, hi);
-                        if (fin) break;
-                        __builtin_amdgcn_s_sleep(2);
-                    }
-                    const int nmr = cnts[3];
-                    if (anyap) {
-                        for (int e0 = 0; e0 < nmr; e0 += 8) { // moves whose row is not in the cache
-                            int4 rc[8];
-                            int gv[8];
-#pragma unroll
-                            for (int q = 0; q < 8; q++) rc[q] = ms_rec[min(e0 + q, nmr - 1)];
-#pragma unroll
-                            for (int q = 0; q < 8; q++) gv[q] = gp[(size_t)__builtin_amdgcn_readfirstlane(rc[q].y) * P + t];
-#pragma unroll
-                            for (int q = 0; q < 8; q++) {
-                                const double nw = fma(-(double)gv[q], __longlong_as_double(((long long)rc[q].w << 32) | (unsigned)rc[q].z), acc_prog);
-                                acc_prog = (e0 + q < nmr && rc[q].y < t) ? nw : acc_prog;
-                            }
-                        }
-                    }
-                }
                 if (t_lo == 0 && nev0 == 0 && !forced) HB_STAMP(13);
                 __syncthreads();
                 const int nev1 = cnts[0];
@@ -1048,17 +891,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 // (the round's moves are listed in marker order, and a move only touches later markers: a wave needs the moves of
                 // the markers before its last one — a prefix of the list, on average half of it)
                 int nap = nev1;
-#if HB_APPLY_PREFIX
                 {
                     const int nr = nev1 - nev0; // <= 64: one lane per move
                     const int kl = lane < nr ? (ev_ix[nev0 + lane] & 0xffff) : 0x7fffffff;
                     nap = nev0 + __popcll(__ballot(kl < ((t | 63))));
                 }
-#endif
                 const bool doap = undec && !inr;
-                if (HB_APPLY_LEAN && HB_APPLY_PROG && crowded) {
-                    if (doap) rhs_new = acc_prog; // (applied before the barrier, while the serial pass ran)
-                } else if (HB_APPLY_LEAN && crowded) {
+                if (crowded) {
                     // A crowded round (BayesR: ~50 moves): the apply used to be the longest phase of the panel — eight waves, two
                     // per SIMD, each issuing ~15 instructions per move (the move's record handed round by v_readlane, a scalar row
                     // address, the test for a row outside the cache, the select for "this marker comes later") at ~13 cycles an
@@ -1068,7 +907,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     // costs five instructions (record, address, Gram entry, conversion, fused multiply-add). The few moves whose
                     // row is not cached come afterwards, their global loads in flight together. (The moves are summed in a
                     // different order than the per-panel kernel sums them: the same chain up to the rounding of rhs, which
-                    // every comparison in tests/ already allows for.)
+                    // every comparison in tests/ already allows for.) Applying a block's moves WHILE the serial pass still runs was tried
+                    // and left out: apply + violation barrier 6 500 -> 950 cycles, but the serial pass 7 800 -> 13 000 (profiles/history.md).
                     const int nsr = cnts[2], nmr = cnts[3];
                     if (__any(doap)) {
                         const int kl = lane < nsr ? ap_rec[lane].y : 0x7fffffff;
@@ -1175,8 +1015,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             for (int c = 0; c < K1; c++) asm volatile("" ::"v"(thr[c]), "v"(invv[c]), "v"(sdz[c]));
 #pragma unroll
             for (int l = 0; l < (NPL > 0 ? NPL : 1); l++) {
-                if (NPL > 0) asm volatile("" ::"v"(pre[0][l]));
-                if (NPL > 0 && HB_NPF > 1) asm volatile("" ::"v"(pre[1][l]));
+                if (NPL > 0) asm volatile("" ::"v"(pre[l]));
             }
         }
         HB_STAMP(2);
@@ -1191,7 +1030,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         // re-read was a second round trip). One 1-KiB piece of each per ring wave (P = 512); a word not written yet shows the
         // sentinel the sweep filled dsum[] / fcorr[] with and is polled at the take as before. The pieces are older than anything
         // the rest of the panel issues, so the counted wait at the top of the next panel covers them.
-        if (HB_R_EARLY && fwd && wave < RW && have_next) {
+        if (fwd && wave < RW && have_next) {
             const unsigned wo = (unsigned)__builtin_amdgcn_readfirstlane(wave) << 10;
             const int nslot_o = (oslot + 1 == HB_RD) ? 0 : oslot + 1;
             dma_piece_s(reinterpret_cast<const char *>(v.dsum + (size_t)(p + 1) * P) + wo, oring_lds + (unsigned)nslot_o * OSLOT + wo, true);
@@ -1202,7 +1041,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         // (... and the band rows the panel's first 32 moves fold into the next panel: the loads fly while the moves are published and the
         // results written, instead of starting after them)
         int fgv[HB_FPRE_N];
-        const bool fpre = HB_R_FOLDPRE && K1 <= 3 && fwd && nev > 0 && have_next; // (K1 = 7 has no registers to spare)
+        const bool fpre = K1 <= 3 && fwd && nev > 0 && have_next; // (K1 = 7 has no registers to spare)
         int fixl[HB_FPRE_N / 64 + 1];
         if (fpre) {
             const int32_t *blk1 = v.gram + ((size_t)(p + 1) * (pv.Lg + 1) + 1) * ((size_t)P * P) + t;
@@ -1257,14 +1096,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             HB_STAMP(5);
             // ---- fold the moves forward into the corrections of the next Lb panels ----
             const int lcount = min(min(fwd ? 1 : pv.Lb, (pv.Lv + 1) * pv.D - 1 - pmodD), np - 1 - p); // panels that need the correction FROM HERE (k_fwd: the others)
-            bool from_pre = NPL > 0 && nev > 0 && nev <= HB_NPF;
-            int w0 = 0, w1 = 0;
-            if (from_pre) { // did exactly (a subset of) the first two candidates move? Their rows are already here
-                const int e0 = ev_ix[0] & 0xffff, e1 = ev_ix[nev - 1] & 0xffff;
-                w0 = e0 == c1 ? 0 : (HB_NPF > 1 && e0 == c2 ? 1 : -1);
-                w1 = e1 == c1 ? 0 : (HB_NPF > 1 && e1 == c2 ? 1 : -1);
-                from_pre = w0 >= 0 && w1 >= 0;
-            }
+            bool from_pre = NPL > 0 && nev == 1;
+            if (from_pre) from_pre = (ev_ix[0] & 0xffff) == c1; // did exactly the first candidate move? Its rows are already here
             if (fpre) { // (k_fwd beside the chain: the next panel only; the rows were requested before the publish; the same fused multiply-adds in the same order as fold_forward's)
                 const int slot = (pslot + 1 == R) ? 0 : pslot + 1;
                 double *cp = corrL + (size_t)slot * P + t;
@@ -1282,7 +1115,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 *cp = acc;
                 if (nev > HB_FPRE_N) fold_forward<1, 32>(corrL, R, v.gram, pv.Lg, lcount, pslot, P, t, nev - HB_FPRE_N, ev_ix + HB_FPRE_N, ev_del + HB_FPRE_N, p);
             } else if (from_pre) {
-                const double d0 = ev_del[0], d1 = nev > 1 ? ev_del[1] : 0.0;
+                const double d0 = ev_del[0];
                 int slot = pslot;
 #pragma unroll
                 for (int l = 1; l <= (NPL > 0 ? NPL : 1); l++) {
@@ -1290,8 +1123,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     if (l <= lcount) { // (lcount <= Lb = NPL here; the same fused multiply-adds, in event order, as fold_forward's)
                         double *cp = corrL + (size_t)slot * P + t;
                         double acc = *cp;
-                        acc = fma((double)(HB_NPF > 1 && w0 ? pre[1][l - 1] : pre[0][l - 1]), d0, acc);
-                        if (HB_NPF > 1 && nev > 1) acc = fma((double)(w1 ? pre[1][l - 1] : pre[0][l - 1]), d1, acc);
+                        acc = fma((double)pre[l - 1], d0, acc);
                         *cp = acc;
                     }
                 }
@@ -1332,9 +1164,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         // (k_fwd's sums for the NEXT panel first — one 1-KiB piece per ring wave, P = 512 — so that the counted wait at the top of the
         // next panel, which lets the youngest ring group stay in flight, covers them; a word k_fwd has not written yet shows the
         // sentinel the sweep filled fcorr[] with and is polled at the take)
-        if (!HB_R_EARLY && fwd && wave < RW && have_next && p + 1 >= pv.p0 + 2)
-            dma_piece_s(reinterpret_cast<const char *>(pv.fcorr + (size_t)(p + 1) * P) + (__builtin_amdgcn_readfirstlane(wave) << 10),
-                        (unsigned)(uintptr_t)fcring + (unsigned)(((p + 1) & 1) * P * 8) + ((unsigned)__builtin_amdgcn_readfirstlane(wave) << 10), true);
         if (wave < RW && p + HB_RD - 1 < np) issue_group(p + HB_RD - 1, (oslot + HB_RD - 1) % HB_RD);
         // (1) Gram rows of the next panel's hot markers, straight into the other half of the LDS row cache by LDS-DMA; the
         // first reader of that half — the first round of the next panel that has candidates — drains vmcnt before its
@@ -1342,13 +1171,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         // then holds ring groups only, which is what makes its counted wait at the top of the panel exact.)
         const int *hpk = reinterpret_cast<const int *>(oslotp + OSZ); // packed list of panel p + 1 (came with group p)
         if (have_next) n_nhot = hpk[0];
-        const bool tri = HB_ROW_TRI && P == 512;
+        const bool tri = P == 512;
         const int n2s = tri ? __builtin_amdgcn_readfirstlane(hpk[2]) : 0, shp = tri ? __builtin_amdgcn_readfirstlane(hpk[3]) : 0;
         const int n_total = n_nhot << lgP, n_items = tri ? n_nhot + n2s : (n_total + 255) >> 8;
-        // (HB_FILL_ALL, panels of 256 and more: every wave issues its share — the four non-ring waves alone took ~8 000 cycles over
+        // (panels of 256 and more: every wave issues its share — the four non-ring waves alone took ~8 000 cycles over
         // the ~80 pieces of a BayesR panel while the ring waves stood at the next panel's barrier; a ring wave's pieces go out behind
         // its ring group and its counted wait at the top of the next panel leaves them in flight too)
-        const bool fill_all = HB_FILL_ALL && P >= 256 && S > 1;
+        const bool fill_all = P >= 256 && S > 1;
         my_rowp = 0;
         if (have_next && (S == 1 || wave >= RW || fill_all)) {
             const unsigned rown_lds = (unsigned)(uintptr_t)rown;

@@ -870,14 +870,6 @@ static int fetch_acc(hb_ctx *c)
         const long long ch = ((long long)c->h_flags[17] << 32) | c->h_flags[16], fo = ((long long)c->h_flags[19] << 32) | c->h_flags[18];
         fprintf(stderr, "hibayes_gpu: k_fold_dense's first workgroup started %.1f us after k_chain_dense's first panel (%u fold workgroups started)\n", (double)(fo - ch) * 1e-2, c->h_flags[13]);
     }
-    if (c->ldiag) { // (HB_DEBUG_ABORT) a long wait that flushed its L2 and went on leaves no other trace
-        static unsigned seen = 0;
-        const unsigned now = hbk_long_wait_flushes();
-        if (now != seen) {
-            fprintf(stderr, "hibayes_gpu: %u long waits flushed their L2 so far (+%u in this sweep)%s\n", now, now - seen, c->h_flags[1] ? " — and the sweep was aborted" : "");
-            seen = now;
-        }
-    }
     // (a sharded sweep: the rank whose pipeline gave up poisons the sums it contributes, so every rank sees a NaN here — hb_run.hip)
     if (c->h_flags[1] || c->h_acc[HB_ACC_EVENTS] != c->h_acc[HB_ACC_EVENTS]) {
         c->aborted = true;

@@ -18,24 +18,12 @@
 // by LDS-DMA, double-buffered, counted vmcnt.
 #pragma once
 
-#ifndef Q2_DIAG
-#define Q2_DIAG 0 /* timing diagnostics only (wrong results): 1 = no atomics at the tile's end, 2 = no dot4 (loads + reduction only), 3 = plain stores instead of the atomics */
-#endif
 #define Q2_RS 512   /* individuals per stage of the default shape (the padded column length is a multiple of it) */
 // Q2_SCALED (round 4): the four genotypes of a byte are masked WITHOUT shifting them down — w & 0x03030303, w & 0x0c0c0c0c,
 // w & 0x30303030 leave them scaled by 1, 4, 16, and (w >> 1) & 0x60606060 by 32 (0xc0 would be a negative int8) — and each scale
 // sums into its own accumulator; the four are combined exactly at the tile's end (a sum of multiples of 4^k shifts back without
 // loss). Five mask operations per 16 genotypes instead of seven, and four independent dot4 chains per plane instead of one.
 // The scale-32 sums bound a tile: rows x 96 x 128 < 2^31, i.e. at most 174 000 individuals per tile (the host splits taller columns).
-#ifndef Q2_SCALED
-#define Q2_SCALED 1
-#endif
-#ifndef Q2_TWO_PER_SIMD
-#define Q2_TWO_PER_SIMD 1 /* k_dotq2 allocates 176 VGPRs so that two of its waves fit a SIMD, not three (A/B on one box, twice: 295.8 / 295.9 sweeps/s without and 2000 tiles, 300.7 / 299.2 with and 1600; with and 2000: 277 — the launch no longer fits the chip at once) */
-#endif
-#ifndef Q2_AHEAD
-#define Q2_AHEAD 2 /* chunks the digit reads run ahead of the dot4 that use them: two since round 4 (a ring of three register sets, the stage fully unrolled: 24.2 against 25.7 us per launch isolated, 22.6 against 23.2 in situ); 1 = the round-3 loop */
-#endif
 
 // RS: individuals per stage (512 or 256). A 1-KiB DMA piece holds 4096 / RS columns x RS individuals of the tile, or 1024 / RS
 // digit planes x RS individuals.
@@ -59,7 +47,7 @@ __device__ __forceinline__ void dotq2_tile(const dq_view &v, char *smem, int b)
 #pragma unroll
     for (int j = 0; j < NDP; j++) doff[j] = (unsigned)(min(j * PPP + lane / LPP, HB_ND - 1) * ld + (lane % LPP) * 16);
     const unsigned lds0 = (unsigned)(uintptr_t)smem;
-    constexpr int NSC = Q2_SCALED ? 4 : 1;
+    constexpr int NSC = 4;
     int acc[CPL][HB_ND][NSC];
 #pragma unroll
     for (int c = 0; c < CPL; c++)
@@ -99,11 +87,12 @@ __device__ __forceinline__ void dotq2_tile(const dq_view &v, char *smem, int b)
         // software-pipelined by hand: the seven digit reads of chunk ch + 1 (and the column's next 16 bytes) are issued BEFORE
         // the 28 dot4 of chunk ch — a wave parks 78 % of its cycles otherwise (rocprofv3 SQ_WAIT_ANY), every chunk waiting out
         // its own LDS round trip behind the other waves' reads
-#if Q2_AHEAD >= 2
-        // (the digit reads Q2_AHEAD chunks ahead of the dot4 that use them, a ring of Q2_AHEAD + 1 register sets, the stage fully unrolled)
-        hb_v4i dr[Q2_AHEAD + 1][HB_ND], xq[CPL], xqn[CPL];
+        // (the digit reads run AH chunks ahead of the dot4 that use them, a ring of AH + 1 register sets, the stage fully unrolled: two since
+        // round 4 — 24.2 against 25.7 us per launch isolated, 22.6 against 23.2 in situ, than one chunk ahead in a loop unrolled by four)
+        constexpr int AH = 2;
+        hb_v4i dr[AH + 1][HB_ND], xq[CPL], xqn[CPL];
 #pragma unroll
-        for (int a = 0; a < Q2_AHEAD; a++)
+        for (int a = 0; a < AH; a++)
 #pragma unroll
             for (int k = 0; k < HB_ND; k++) dr[a][k] = *reinterpret_cast<const hb_v4i *>(pd + k * RS + a * 16);
 #pragma unroll
@@ -115,9 +104,9 @@ __device__ __forceinline__ void dotq2_tile(const dq_view &v, char *smem, int b)
 #pragma unroll
                 for (int c = 0; c < CPL; c++) xq[c] = xqn[c];
             }
-            const int chn = min(ch + Q2_AHEAD, RS / 16 - 1);
+            const int chn = min(ch + AH, RS / 16 - 1);
 #pragma unroll
-            for (int k = 0; k < HB_ND; k++) dr[(ch + Q2_AHEAD) % (Q2_AHEAD + 1)][k] = *reinterpret_cast<const hb_v4i *>(pd + k * RS + chn * 16);
+            for (int k = 0; k < HB_ND; k++) dr[(ch + AH) % (AH + 1)][k] = *reinterpret_cast<const hb_v4i *>(pd + k * RS + chn * 16);
             if (w == 2) {
 #pragma unroll
                 for (int c = 0; c < CPL; c++) xqn[c] = px[c][min((ch >> 2) + 1, RS / 64 - 1)];
@@ -125,35 +114,10 @@ __device__ __forceinline__ void dotq2_tile(const dq_view &v, char *smem, int b)
             __builtin_amdgcn_sched_barrier(0);
             hb_v4i d[HB_ND];
 #pragma unroll
-            for (int k = 0; k < HB_ND; k++) d[k] = dr[ch % (Q2_AHEAD + 1)][k];
-#else
-        hb_v4i dn[HB_ND], xq[CPL], xqn[CPL];
-#pragma unroll
-        for (int k = 0; k < HB_ND; k++) dn[k] = *reinterpret_cast<const hb_v4i *>(pd + k * RS);
-#pragma unroll
-        for (int c = 0; c < CPL; c++) xqn[c] = px[c][0];
-#pragma unroll 4
-        for (int ch = 0; ch < RS / 16; ch++) { // 16 individuals per chunk; four chunks per 16-byte read of a column
-            hb_v4i d[HB_ND];
-#pragma unroll
-            for (int k = 0; k < HB_ND; k++) d[k] = dn[k];
-            const int w = ch & 3;
-            if (w == 0) {
-#pragma unroll
-                for (int c = 0; c < CPL; c++) xq[c] = xqn[c];
-            }
-            const int chn = min(ch + 1, RS / 16 - 1);
-#pragma unroll
-            for (int k = 0; k < HB_ND; k++) dn[k] = *reinterpret_cast<const hb_v4i *>(pd + k * RS + chn * 16);
-            if (w == 3) {
-#pragma unroll
-                for (int c = 0; c < CPL; c++) xqn[c] = px[c][min((ch >> 2) + 1, RS / 64 - 1)];
-            }
-#endif
+            for (int k = 0; k < HB_ND; k++) d[k] = dr[ch % (AH + 1)][k];
 #pragma unroll
             for (int c = 0; c < CPL; c++) {
                 const unsigned xw = (unsigned)(w == 0 ? xq[c].x : w == 1 ? xq[c].y : w == 2 ? xq[c].z : xq[c].w);
-#if Q2_SCALED
                 const int m0 = (int)(xw & 0x03030303u), m1 = (int)(xw & 0x0c0c0c0cu), m2 = (int)(xw & 0x30303030u),
                           m3 = (int)((xw >> 1) & 0x60606060u);
 #pragma unroll
@@ -163,17 +127,6 @@ __device__ __forceinline__ void dotq2_tile(const dq_view &v, char *smem, int b)
                     acc[c][k][2] = __builtin_amdgcn_sdot4(m2, d[k].z, acc[c][k][2], false);
                     acc[c][k][3] = __builtin_amdgcn_sdot4(m3, d[k].w, acc[c][k][3], false);
                 }
-#else
-                const int m0 = (int)(xw & 0x03030303u), m1 = (int)((xw >> 2) & 0x03030303u), m2 = (int)((xw >> 4) & 0x03030303u),
-                          m3 = (int)((xw >> 6) & 0x03030303u);
-#pragma unroll
-                for (int k = 0; k < HB_ND; k++) {
-                    acc[c][k][0] = __builtin_amdgcn_sdot4(m0, d[k].x, acc[c][k][0], false);
-                    acc[c][k][0] = __builtin_amdgcn_sdot4(m1, d[k].y, acc[c][k][0], false);
-                    acc[c][k][0] = __builtin_amdgcn_sdot4(m2, d[k].z, acc[c][k][0], false);
-                    acc[c][k][0] = __builtin_amdgcn_sdot4(m3, d[k].w, acc[c][k][0], false);
-                }
-#endif
             }
         }
         buf ^= 1;
@@ -182,10 +135,7 @@ __device__ __forceinline__ void dotq2_tile(const dq_view &v, char *smem, int b)
     for (int c = 0; c < CPL; c++)
 #pragma unroll
         for (int k = 0; k < HB_ND; k++) {
-            const int tot = Q2_SCALED ? acc[c][k][0] + (acc[c][k][NSC > 1 ? 1 : 0] >> 2) + (acc[c][k][NSC > 2 ? 2 : 0] >> 4) + (acc[c][k][NSC > 3 ? 3 : 0] >> 5) : acc[c][k][0];
-            if (Q2_DIAG == 1) { if (tot == 0x12345678) v.accq[0] = 1; } // (timing diagnostic: the tile without its closing atomics)
-            else if (Q2_DIAG == 3) v.accq[(int64_t)k * v.accstride + cg * (64 * CPL) + c * 64 + lane] = (long long)tot; // (... plain stores in their place)
-            else
+            const int tot = acc[c][k][0] + (acc[c][k][1] >> 2) + (acc[c][k][2] >> 4) + (acc[c][k][3] >> 5);
             __hip_atomic_fetch_add(v.accq + (int64_t)k * v.accstride + cg * (64 * CPL) + c * 64 + lane, (long long)tot, __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_AGENT);
         }
@@ -195,11 +145,10 @@ template <int CPL, int RS>
 __global__ __launch_bounds__(64) void k_dotq2(dq_view v, upd_view uq)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-#if Q2_TWO_PER_SIMD
     // (a register the kernel does not need, named so that its allocation passes 170: the hardware then fits two of its waves on a SIMD,
-    // not three — a launch's tiles are VALU-bound, a SIMD with three of them ends half a tile time after one with two)
+    // not three — a launch's tiles are VALU-bound, a SIMD with three of them ends half a tile time after one with two. A/B on one box,
+    // twice: 295.8 / 295.9 sweeps/s without and 2000 tiles, 300.7 / 299.2 with and 1600; with and 2000: 277 — the launch no longer fits the chip at once)
     asm volatile("" ::: "v175");
-#endif
     unsigned long long t0 = 0;
     if (v.stamp || v.ldiag) t0 = wall_clock64();
     int b = blockIdx.x;
@@ -208,7 +157,7 @@ __global__ __launch_bounds__(64) void k_dotq2(dq_view v, upd_view uq)
         if (col < v.fin_ncols) hbq_finalize(v.fin_acc, v.accstride, col, *v.fin_exp, v.fin_out);
     } else if (b < v.nfin + v.nupd) { // residual update of an earlier group (2-bit columns: upd_view.X2), lists staged in the tile buffers
         b -= v.nfin;
-        update_rows(v.ld, uq, b, reinterpret_cast<int *>(smem), reinterpret_cast<double *>(smem + 2048), reinterpret_cast<int *>(smem + 2048 + 4096), v.ldiag ? v.ldiag + 3 : nullptr);
+        update_rows(v.ld, uq, b, reinterpret_cast<int *>(smem), reinterpret_cast<double *>(smem + 2048), v.ldiag ? v.ldiag + 3 : nullptr);
     } else {
         dotq2_tile<CPL, RS>(v, smem, b - v.nupd - v.nfin);
     }
@@ -248,12 +197,6 @@ static constexpr int q2_lds(int cpl, int rs) { return 2 * ((64 * cpl / (4096 / r
 #define Q2M_DSTRIDE 1088
 #ifndef Q2M_NBUF
 #define Q2M_NBUF 3 /* stage buffers: NBUF - 1 (super-)stages in flight ahead of the one being multiplied (a stage computes in ~0.3 us, a loaded round trip takes ~2) */
-#endif
-#ifndef Q2M_NODIG
-#define Q2M_NODIG 0 /* TIMING DIAGNOSTIC ONLY (wrong results): dotq2m512_tile requests no digit pieces at all — the round-5 verdict's test of "the launch is bound by LDS-DMA ingest, a third of which is digits every single-wave tile re-reads" (profiles/r06_q2m_digits.txt) */
-#endif
-#ifndef Q2M_NT
-#define Q2M_NT 1 /* the genotype tile's DMA pieces carry the non-temporal hint (k_dotq: so that the digit planes and the chain's rows stay in L2) */
 #endif
 static_assert(Q2M_NBUF >= 2 && Q2M_NBUF <= 6, "the counted waits of dotq2m_tile cover up to five stages in flight");
 // Shape (round 5). CT = column tiles of 16 per wave (4: 64 columns, the round-4 shape; 8: 128; 16: 256) — the stage's digit planes
@@ -301,7 +244,7 @@ __device__ __forceinline__ void dotq2m_tile(const dq_view &v, char *smem, int b)
             const int8_t *ds = uni_p(v.rq + (int64_t)st * Q2M_RS);
             const unsigned dst = (unsigned)__builtin_amdgcn_readfirstlane((int)(lds0 + (unsigned)(buf * G + g) * BUF));
 #pragma unroll
-            for (int i = 0; i < CT; i++) hbq_dma16<Q2M_NT != 0>(voff, xs + (int64_t)(16 * i) * ld2, dst + i * HBQ_SLOT);
+            for (int i = 0; i < CT; i++) hbq_dma16<true>(voff, xs + (int64_t)(16 * i) * ld2, dst + i * HBQ_SLOT); // (non-temporal, as in k_dotq: the digit planes and the chain's rows stay in L2)
 #pragma unroll
             for (int j = 0; j < 2; j++) hbq_dma16<false>(doff[j], ds, dst + XB + j * Q2M_DSTRIDE);
         }
@@ -382,9 +325,6 @@ __device__ __forceinline__ void dotq2m_tile(const dq_view &v, char *smem, int b)
 #pragma unroll
         for (int q = 0; q < CT / 4; q++) {
             const int tv = tr[k * (16 * CT) + q * 64 + lane];
-            if (Q2_DIAG == 1) { if (tv == 0x12345678) v.accq[0] = 1; } // (timing diagnostic: the tile without its closing atomics)
-            else if (Q2_DIAG == 3) v.accq[(int64_t)k * v.accstride + cg * (16 * CT) + q * 64 + lane] = (long long)tv; // (... with plain stores in their place)
-            else
             __hip_atomic_fetch_add(v.accq + (int64_t)k * v.accstride + cg * (16 * CT) + q * 64 + lane, (long long)tv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
 }
@@ -402,7 +342,7 @@ __device__ __forceinline__ void dotq2m512_tile(const dq_view &v, char *smem, int
     // chunk 8 j + l / 8 (slot = chunk * 8 + plane: the seven planes of a read group are neighbours). The eight lanes that share a 128-byte line are then
     // eight apart; without SWZ they are neighbours and the reads conflict four- and seven-fold.
     constexpr int XSL = SWZ ? 1152 : HBQ_SLOT;
-    constexpr int NXP = 8, NDP = 4, XB = NXP * XSL, BUF = XB + NDP * 1024, PER = NXP + (Q2M_NODIG ? 0 : NDP), NSC = SC ? 4 : 1;
+    constexpr int NXP = 8, NDP = 4, XB = NXP * XSL, BUF = XB + NDP * 1024, PER = NXP + NDP, NSC = SC ? 4 : 1;
     static_assert((Q2M_NBUF - 1) * PER <= 63, "the in-flight DMA pieces must fit the 6-bit vmcnt");
     const int lane = threadIdx.x;
     const int cg = b % v.ncg, sp = b / v.ncg;
@@ -428,11 +368,9 @@ __device__ __forceinline__ void dotq2m512_tile(const dq_view &v, char *smem, int
         const int8_t *ds = uni_p(v.rq + (int64_t)st * 512);
         const unsigned dst = (unsigned)__builtin_amdgcn_readfirstlane((int)(lds0 + (unsigned)buf * BUF));
 #pragma unroll
-        for (int i = 0; i < NXP; i++) hbq_dma16<Q2M_NT != 0>(voff, xs + (int64_t)(8 * i) * ld2, dst + i * XSL);
-        if constexpr (!Q2M_NODIG) {
+        for (int i = 0; i < NXP; i++) hbq_dma16<true>(voff, xs + (int64_t)(8 * i) * ld2, dst + i * XSL);
 #pragma unroll
-            for (int j = 0; j < NDP; j++) hbq_dma16<false>(doff[j], ds, dst + XB + j * 1024);
-        }
+        for (int j = 0; j < NDP; j++) hbq_dma16<false>(doff[j], ds, dst + XB + j * 1024);
     };
     hb_v4i C[4][NSC];
 #pragma unroll
@@ -521,7 +459,7 @@ __global__ __launch_bounds__(64) void k_dotq2m(dq_view v, upd_view uq)
         if (col < v.fin_ncols) hbq_finalize(v.fin_acc, v.accstride, col, *v.fin_exp, v.fin_out);
     } else if (b < v.nfin + v.nupd) {
         b -= v.nfin;
-        update_rows(v.ld, uq, b, reinterpret_cast<int *>(smem), reinterpret_cast<double *>(smem + 2048), reinterpret_cast<int *>(smem + 2048 + 4096), v.ldiag ? v.ldiag + 3 : nullptr);
+        update_rows(v.ld, uq, b, reinterpret_cast<int *>(smem), reinterpret_cast<double *>(smem + 2048), v.ldiag ? v.ldiag + 3 : nullptr);
     } else {
         if constexpr (G == 0) dotq2m512_tile<SC, false>(v, smem, b - v.nupd - v.nfin);
         else if constexpr (G == 3) dotq2m512_tile<SC, true>(v, smem, b - v.nupd - v.nfin);
@@ -610,8 +548,7 @@ __device__ __forceinline__ void dotq2r_tile(const dq_view &v, int b)
                     const int m = (int)((xw >> (2 * k)) & 0x03030303u);
 #pragma unroll
                     for (int p = 0; p < HB_ND; p++) {
-                        if (Q2_DIAG == 2) { if (p == 0 && k == 0) a[c * 8 + p] += m ^ dig[p][4 * w + k]; }
-                        else a[c * 8 + p] = __builtin_amdgcn_sdot4(m, dig[p][4 * w + k], a[c * 8 + p], false);
+                        a[c * 8 + p] = __builtin_amdgcn_sdot4(m, dig[p][4 * w + k], a[c * 8 + p], false);
                     }
                 }
             }
@@ -636,7 +573,6 @@ __device__ __forceinline__ void dotq2r_tile(const dq_view &v, int b)
         // which sum this lane holds: bit 32 of the lane picked the upper 16, bit 16 the upper 8, ... bit 2 the upper 1
         const int vi = ((lane >> 5) & 1) * 16 + ((lane >> 4) & 1) * 8 + ((lane >> 3) & 1) * 4 + ((lane >> 2) & 1) * 2 + ((lane >> 1) & 1);
         const int cc = vi >> 3, pp = vi & 7;
-        if (Q2_DIAG == 1) { if (tot == 0x12345678) v.accq[0] = tot; } else
         if (!(lane & 1) && pp < HB_ND)
             __hip_atomic_fetch_add(v.accq + (int64_t)pp * v.accstride + cgi * NC + c0 + cc, (long long)tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
@@ -654,7 +590,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
         if (col < v.fin_ncols) hbq_finalize(v.fin_acc, v.accstride, col, *v.fin_exp, v.fin_out);
     } else if (b < v.nfin + v.nupd) {
         b -= v.nfin;
-        update_rows(v.ld, uq, b, reinterpret_cast<int *>(smem), reinterpret_cast<double *>(smem + 2048), reinterpret_cast<int *>(smem + 2048 + 4096), v.ldiag ? v.ldiag + 3 : nullptr);
+        update_rows(v.ld, uq, b, reinterpret_cast<int *>(smem), reinterpret_cast<double *>(smem + 2048), v.ldiag ? v.ldiag + 3 : nullptr);
     } else {
         dotq2r_tile(v, b - v.nupd - v.nfin);
     }

@@ -33,28 +33,13 @@ __device__ unsigned long long hb_timeout_ticks = 10000000ull;
 #define HB_LOG_GROUP 7        /* k_chain_group / k_fwd / k_chain_persist: a = code, b = panel or group */
 
 __device__ __forceinline__ unsigned ld_flag(const unsigned *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_flag(unsigned *p, unsigned v)
-{
-#if defined(HB_PUBLISH_ATOMIC) && HB_PUBLISH_ATOMIC
-    (void)__hip_atomic_exchange(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
-}
+__device__ __forceinline__ void st_flag(unsigned *p, unsigned v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ double ld_sc1(const double *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ int ld_sc1(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// HB_PUBLISH_ATOMIC (an A/B for the dense stall): publish with a no-return atomic exchange — performed at the memory side,
-// the point all XCDs share — instead of a write-through store that the writer's L2 forwards
-#ifndef HB_PUBLISH_ATOMIC
-#define HB_PUBLISH_ATOMIC 0
-#endif
-#if HB_PUBLISH_ATOMIC
-__device__ __forceinline__ void st_sc1(double *p, double v) { (void)__hip_atomic_exchange(reinterpret_cast<unsigned long long *>(p), (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_sc1(int *p, int v) { (void)__hip_atomic_exchange(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-#else
+// (write-through stores that the writer's L2 forwards; publishing with a no-return atomic exchange at the memory side instead was an
+// A/B for the dense stall and changed nothing)
 __device__ __forceinline__ void st_sc1(double *p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void st_sc1(int *p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-#endif
 
 __device__ __attribute__((noinline)) void hb_abort_log(unsigned *flags, unsigned kind, bool own, unsigned a, unsigned b, unsigned long long seen)
 {
@@ -74,98 +59,42 @@ __device__ __attribute__((noinline)) void hb_abort_log(unsigned *flags, unsigned
     r[7] = (unsigned)(seen >> 32);
 }
 
-// Polling pace. A waiter looks again after a short sleep; HB_BACKOFF builds (an A/B for the dense stall) stretch the
-// sleep once a wait has lasted a few hundred looks, so that a long wait stops being continuous traffic on the memory path.
-#ifndef HB_BACKOFF
-#define HB_BACKOFF 0
-#endif
-__device__ __forceinline__ void hb_poll_pause(unsigned &looks, int base)
+// Polling pace: a waiter looks again after a short sleep. (Stretching the sleep of a long wait did not help the dense stall)
+__device__ __forceinline__ void hb_poll_pause(int base)
 {
-#if HB_BACKOFF
-    if (looks > 4096u) { __builtin_amdgcn_s_sleep(127); __builtin_amdgcn_s_sleep(127); __builtin_amdgcn_s_sleep(127); __builtin_amdgcn_s_sleep(127); }
-    else if (looks > 256u) __builtin_amdgcn_s_sleep(64);
-    else if (base <= 1) __builtin_amdgcn_s_sleep(1);
-    else __builtin_amdgcn_s_sleep(8);
-#else
-    (void)looks;
     if (base <= 1) __builtin_amdgcn_s_sleep(1);
     else __builtin_amdgcn_s_sleep(8);
-#endif
 }
 
-// A poll that cannot be served a stale line. The hand-offs are polled with agent-scope (sc1) loads, which the XCD's L2 may serve;
-// round 4's abort log (profiles/r04_dense_stall_diagnostics.txt) shows what the dense stall of round 3 was: once in ~10^9 polled
-// words a reader's L2 keeps returning the sentinel a word was pre-filled with although the producer's write-through store reached
-// memory long ago (the reader asked for the line ahead of time, and its copy was never dropped) — every later look hits that copy,
-// and the pipeline waits until its 3 s time-out. A returning agent-scope atomic (fetch-or with 0) is performed at the memory side,
-// the one place all eight XCDs agree on: it returns what memory holds and leaves it unchanged. Every wait looks that way once in
-// HB_FRESH_EVERY looks — a wait that is served at once never pays for it.
-#ifndef HB_FRESH_EVERY
-#define HB_FRESH_EVERY 0 /* 0: never (the default since the stall turned out to be on the WRITER's side, see hb_long_wait) */
-#endif
+// A look that cannot be served a stale line. The hand-offs are polled with agent-scope (sc1) loads, which the XCD's L2 may serve. A
+// returning agent-scope atomic (fetch-or with 0) is performed at the memory side, the one place all eight XCDs agree on: it returns what
+// memory holds and leaves it unchanged. The waits of the pipeline do not look this way: the dense stall of round 3 — one write-through
+// store of the chain workgroup in nobody's view for seconds after one of the device's ~1 ms pauses, profiles/r04_dense_stall_diagnostics.txt
+// — is on the WRITER's side, and neither memory-side looks in every wait nor a write-back of the waiter's own L2 after a few hundred looks
+// released it (11 sweeps in 16 000 still timed out, §9.0). hb_reduce.hpp and the re-look of hb_update.hpp read this way.
 __device__ __forceinline__ double ld_fresh(const double *p)
 {
     return __longlong_as_double((long long)__hip_atomic_fetch_or(reinterpret_cast<unsigned long long *>(const_cast<double *>(p)), 0ull,
                                                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
 }
-__device__ __forceinline__ unsigned ld_flag_fresh(const unsigned *p)
-{
-    return __hip_atomic_fetch_or(const_cast<unsigned *>(p), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 __device__ __forceinline__ int ld_fresh(const int *p)
 {
     return (int)__hip_atomic_fetch_or(reinterpret_cast<unsigned *>(const_cast<int *>(p)), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-// (uniform) is this look of a wait a memory-side one?
-__device__ __forceinline__ bool hb_fresh_look(unsigned looks)
-{
-#if HB_FRESH_EVERY > 0
-    if ((looks % HB_FRESH_EVERY) == HB_FRESH_EVERY - 1) return true;
-#endif
-    (void)looks;
-    return false;
-}
-__device__ __forceinline__ int ld_poll(const int *p, unsigned looks) { return hb_fresh_look(looks) ? ld_fresh(p) : ld_sc1(p); }
-__device__ __forceinline__ double ld_poll(const double *p, unsigned looks) { return hb_fresh_look(looks) ? ld_fresh(p) : ld_sc1(p); }
-
-// A wait that has lasted a few hundred looks writes back the dirty lines of ITS OWN XCD's L2 (buffer_wbl2 sc1). What the launch
-// stamps and the memory-side looks of round 4 showed about the dense stall (profiles/r04_dense_stall_diagnostics.txt): once in a few
-// thousand sweeps the device pauses for ~1 ms (a launch starts 0.85 ms after its predecessor ended; `max_ms` of the in-situ stamps shows
-// the same pauses in runs that do not stall), and afterwards ONE write-through store instruction of the chain workgroup — a sub-block's
-// 64 changes of effect — is in nobody's view: every reader on every other XCD, memory-side atomics included, sees the pre-filled sentinel
-// for 3 s, while the value appears in memory the moment the kernels end (their end-of-kernel release writes the L2 back). The line sits
-// dirty in the WRITER's L2. The writer is by then waiting itself — for the sums that depend on that very store — so the remedy lives in
-// the waits: whoever has published write-through data and then waits longer than any healthy hand-off takes flushes its L2. A healthy
-// wait never gets here (hand-offs take microseconds); a stalled one is released within a fraction of a millisecond instead of 3 s.
-#ifndef HB_UPD_FLAG_FIRST
-#define HB_UPD_FLAG_FIRST 0
-#endif
-#ifndef HB_FLUSH_LOOKS
-#define HB_FLUSH_LOOKS 0 /* off: measured, it does not release a stall (§9.0) — 11 sweeps in 16 000 still timed out with it */
-#endif
-__device__ unsigned hb_long_wait_flushes; // (diagnostics: how often a wait got that far; read by fetch_acc with HB_DEBUG_ABORT)
-__device__ __forceinline__ void hb_long_wait(unsigned looks)
-{
-#if HB_FLUSH_LOOKS > 0
-    if ((looks % HB_FLUSH_LOOKS) == HB_FLUSH_LOOKS - 1) { // (uniform)
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if ((threadIdx.x & 63) == 0) atomicAdd(&hb_long_wait_flushes, 1u);
-    }
-#else
-    (void)looks;
-#endif
-}
+// (uniform) is this look of a wait a memory-side one? Settled: never. Two waits still ask — the take of k_chain_persist and the opening of
+// k_chain_group — because hipcc allocates registers (persist) and schedules three instructions of the stamps build (group) differently once
+// their never-taken memory-side branches are deleted; the change that settled the other switches shipped byte-identical kernels, so these
+// two go with the next change to either kernel.
+__device__ __forceinline__ bool hb_fresh_look(unsigned looks) { (void)looks; return false; }
 
 // one lane waits until *word >= want; bounded; returns false when the run is being aborted
 template <int SLEEP = 8>
 __device__ __forceinline__ bool wait_ge(unsigned *flags, int word, unsigned want)
 {
     const unsigned long long t0 = wall_clock64();
-    for (unsigned looks = 0;; looks++) {
-        if ((hb_fresh_look(looks) ? ld_flag_fresh(flags + word) : ld_flag(flags + word)) >= want) return true;
-        if (hb_fresh_look(looks) ? ld_flag_fresh(flags + HB_FLAG_ABORT) : ld_flag(flags + HB_FLAG_ABORT)) return false;
-        hb_long_wait(looks);
+    for (;;) {
+        if (ld_flag(flags + word) >= want) return true;
+        if (ld_flag(flags + HB_FLAG_ABORT)) return false;
         if (wall_clock64() - t0 > HB_TIMEOUT_TICKS) {
             st_flag(flags + HB_FLAG_ABORT, 1u);
             st_flag(flags + 8, want); // (diagnostics: who gave up, hb_ctx.hip fetch_acc)

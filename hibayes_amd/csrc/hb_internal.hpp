@@ -75,7 +75,7 @@ struct hb_ctx {
     int layout = 8;      // 8: int8 columns, 2: 2-bit columns
     int dotq_tiles = 768;          // tiles per k_dotq launch (HB_DOTQ_TILES): about three waves per compute unit
     bool dotq2_tiles_set = false;  // HB_DOTQ2_TILES given: it then also holds for k_dotq2m, whose own targets and XCD budget (launch_dotq2) are skipped
-    int dotq2_cpl = 1, dotq2_tiles = 1600, dotq2_rs = 256; // (tiles per full-width k_dotq2 launch, HB_DOTQ2_TILES: 1568 of seven stages at n = 50k — with two waves per SIMD (Q2_TWO_PER_SIMD) 2048 waves are resident, and tiles + update rows + the chain's and k_fwd's compute units must fit; until that cap 2000 -> 1848 tiles of six stages: 296 against 300 sweeps/s)
+    int dotq2_cpl = 1, dotq2_tiles = 1600, dotq2_rs = 256; // (tiles per full-width k_dotq2 launch, HB_DOTQ2_TILES: 1568 of seven stages at n = 50k — with two waves per SIMD (k_dotq2 allocates 176 VGPRs for that) 2048 waves are resident, and tiles + update rows + the chain's and k_fwd's compute units must fit; until that cap 2000 -> 1848 tiles of six stages: 296 against 300 sweeps/s)
     // which kernel computes the panel mat-vec on 2-bit resident genotypes (HB_DOTQ2_KIND / hb_ctx_set_matvec_kernel; all three give the same exact integers):
     // 2 (default since round 5) k_dotq2m, the seven digit planes as a skinny int8 GEMM on the matrix cores — 12.0 us per 3584-column launch isolated; 0 k_dotq2,
     // lane = column through LDS, v_dot4 (22 us: VALU-issue-bound; the default until round 4); 1 k_dotq2r, individuals across the lanes, no LDS, NC columns per tile (26 us)
@@ -202,7 +202,6 @@ struct hb_ctx {
 
 extern "C" int hb_ctx_snapshot(hb_ctx *c, int model_index, bool store, bool count_pip);
 extern "C" int hb_ctx_restore(hb_ctx *c);
-unsigned hbk_long_wait_flushes();
 int hbk_set_timeout(hb_ctx *c);
 int hbk_time_stream_read(hb_ctx *c, int reps, double *avg_ms, int64_t *bytes);
 int hbk_copy_segs(hb_ctx *c, const std::vector<hb_ctx::snap_seg> &segs, bool restore);

@@ -134,8 +134,7 @@ __global__ __launch_bounds__(256) void k_update(int64_t ld, upd_view q)
 {
     __shared__ int s_ix[512];
     __shared__ double s_dl[512];
-    __shared__ int s_ok[2];
-    update_rows(ld, q, blockIdx.x, s_ix, s_dl, s_ok);
+    update_rows(ld, q, blockIdx.x, s_ix, s_dl);
 }
 
 #include "hb_reduce.hpp"
@@ -997,13 +996,6 @@ int hbk_set_timeout(hb_ctx *c)
     HB_HIP(hipStreamSynchronize(c->stream)); // (the source is a stack word; this happens once per change of the value)
     uploaded_ms[c->device] = ms;
     return HB_OK;
-}
-
-unsigned hbk_long_wait_flushes()
-{
-    unsigned v = 0;
-    (void)hipMemcpyFromSymbol(&v, HIP_SYMBOL(hb_long_wait_flushes), sizeof v);
-    return v;
 }
 
 int hbk_windows(hb_ctx *c)

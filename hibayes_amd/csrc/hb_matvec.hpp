@@ -59,8 +59,7 @@ __global__ __launch_bounds__(256) void k_dot(const int8_t *__restrict__ X, int64
         if (sp == 0) {
             __shared__ int s_ix[512];
             __shared__ double s_dl[512];
-            __shared__ int s_ok[2];
-            for (int blk = ct; (int64_t)blk * 1024 < ld; blk += gridDim.x) update_rows(ld, uq, blk, s_ix, s_dl, s_ok);
+            for (int blk = ct; (int64_t)blk * 1024 < ld; blk += gridDim.x) update_rows(ld, uq, blk, s_ix, s_dl);
             return;
         }
         sp -= 1;
@@ -229,7 +228,7 @@ __device__ __forceinline__ void dotq_block(const dq_view &v, const upd_view &uq,
     if (b < v.nupd) { // residual update of an earlier group: 256 rows per block (64 where every marker moves), lists staged in the (unused) tile buffers
         if (uq.dense) update_rows_dense(v.ld, uq, b, v.nupd, smem); // (launched with HBU_LDS bytes of dynamic LDS)
         else update_rows(v.ld, uq, b, reinterpret_cast<int *>(smem), reinterpret_cast<double *>(smem + 2048),
-                         reinterpret_cast<int *>(smem + 2048 + 4096), v.ldiag ? v.ldiag + 3 : nullptr);
+                         v.ldiag ? v.ldiag + 3 : nullptr);
         return;
     }
     b -= v.nupd;

@@ -66,7 +66,7 @@ __device__ __forceinline__ void hb_store_digits(int8_t *rq, int64_t ld, int64_t 
 
 // rows [row0, row0 + 4) of the residual: yadj -= sum_e x_e D_e, u += the same, r32 = (float)yadj
 __device__ __forceinline__ void update_rows(int64_t ld, const upd_view &q, int blk, int *s_ix,
-                                            double *s_dl, int *s_ok, unsigned long long *ust = nullptr)
+                                            double *s_dl, unsigned long long *ust = nullptr)
 {
     // (ust: HB_DEBUG_ABORT diagnostics — block 64 of the launch leaves the lengths of its phases, four 16-bit counts of 100 MHz ticks:
     // poll of counts and bound | move lists | columns and sums | stores; tools/launch_roles.py prints their means)
@@ -96,15 +96,6 @@ __device__ __forceinline__ void update_rows(int64_t ld, const upd_view &q, int b
     {
         double mbv = 0.0;
         const bool poll = q.flags != nullptr;
-#if HB_UPD_FLAG_FIRST
-        // (A/B: one lane waits for chain_done first — ONE polled word for all update blocks — and the counts and the bound are then read
-        // once, validated like below: a trip more, but the lines the chain stores its counts and bounds to are not polled)
-        if (poll) {
-            if (threadIdx.x == 0) *s_ok = wait_ge(q.flags, HB_FLAG_CHAIN_DONE, (unsigned)q.p1) ? 1 : 0;
-            __syncthreads();
-            if (!*s_ok) return;
-        }
-#endif
         const unsigned long long t0 = wall_clock64();
         for (;;) {
             if (q.rq) mbv = ld_sc1(q.mbv); // (every thread the same word: one broadcast load per wave, in flight with the counts)
@@ -303,16 +294,9 @@ __device__ __forceinline__ void update_rows_dense(int64_t ld, const upd_view &q,
             // everything again afterwards (784 waves polling 17 words each would be traffic the chain does not need)
             const double *last = q.rq ? q.mbv : q.dd + (size_t)q.p0 * q.P + (ncol - 1);
             bool dead = false;
-            unsigned looks = 0;
-            while (HBU_SENT(hb_fresh_look(looks) ? ld_fresh(last) : ld_sc1(last))) {
-                if ((hb_fresh_look(looks) ? ld_flag_fresh(q.flags + HB_FLAG_ABORT) : ld_flag(q.flags + HB_FLAG_ABORT)) || wall_clock64() - t0 > HB_TIMEOUT_TICKS) { dead = true; break; }
-#ifdef HB_UPD_SLEEP
-                __builtin_amdgcn_s_sleep(HB_UPD_SLEEP);
-                __builtin_amdgcn_s_sleep(HB_UPD_SLEEP);
-#else
-                hb_poll_pause(looks, 8);
-#endif
-                looks++;
+            while (HBU_SENT(ld_sc1(last))) {
+                if (ld_flag(q.flags + HB_FLAG_ABORT) || wall_clock64() - t0 > HB_TIMEOUT_TICKS) { dead = true; break; }
+                hb_poll_pause(8);
             }
             // (the last word is there and an earlier one is not yet visible: look again, but never without the bound on the wait)
             if (!dead && (ld_flag(q.flags + HB_FLAG_ABORT) || wall_clock64() - t0 > HB_TIMEOUT_TICKS)) dead = true;
