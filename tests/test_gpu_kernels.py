@@ -19,6 +19,19 @@ def rand_geno(rng, n, m, signed=False):
     return np.asfortranarray(X.astype(np.int8))
 
 
+def rand_geno3(rng, n, m):
+    """rand_geno with a third allele draw: codes 0..3, i.e. genotypes with BOTH bits of their 2-bit field set (hb_dotq2.hpp: individual
+    16 w + 4 k + b sits in bits 8 b + 2 k of word w; at k = 3 a code 3 is the 0xc0 pattern that must not become a negative int8). Column 0
+    holds a 3 at each of the 16 positions of its first word (so at each of the four sub-positions of a byte), column 1 is all 3."""
+    p = rng.uniform(0.05, 0.5, m)
+    X = sum((rng.random((n, m)) < p).astype(np.int8) for _ in range(3))
+    X[:16, 0] = 3
+    X[:, 1] = 3
+    X = np.asfortranarray(X.astype(np.int8))
+    assert X.min() == 0 and X.max() == 3 and all((X[k::16] == 3).any() for k in range(16)) and (X[:, 1] == 3).all()
+    return X
+
+
 @pytest.mark.parametrize("n,m,panel", [(300, 1000, 0), (1000, 777, 64), (4097, 130, 128), (257, 2049, 512)])
 def test_marker_stats_exact(n, m, panel):
     rng = np.random.default_rng(n + m)
@@ -266,18 +279,16 @@ def test_bigmemory_file_to_device_without_a_host_copy(tmp_path, demo):
     assert np.array_equal(r["alpha"], r2["alpha"])
 
 
-@pytest.mark.parametrize("shape", [{"HB_Q2M_G": "1"}, {"HB_Q2M_G": "2"}, {"HB_Q2M_G": "3"}, {"HB_Q2M_G": "1", "HB_Q2M_CT": "8"},
-                                   {"HB_Q2M_G": "1", "HB_Q2M_CT": "16", "HB_Q2M_SC": "0"}, {"HB_Q2M_G": "0", "HB_Q2M_SC": "0"}])
-def test_every_shape_of_the_matrix_core_matvec_gives_the_same_integers(shape, monkeypatch):
-    """k_dotq2m's template shapes (hb_dotq2.hpp; round 5): 256-individual stages singly or in pairs, 512-individual stages of whole-line DMA
-    pieces in plain and in bank-conflict-free lane order (the default is G = 0), 64 / 128 / 256 columns per wave, one accumulator set per
-    genotype scale or one in all. Integer sums in another order: every shape must give the int8 layout's dot products bit for bit, on
-    a padded length that is a multiple of 512 and on one that is not (the 512-individual shapes then fall back to 256)."""
+Q2M_SHAPES = [{"HB_Q2M_G": "1"}, {"HB_Q2M_G": "2"}, {"HB_Q2M_G": "3"}, {"HB_Q2M_G": "1", "HB_Q2M_CT": "8"},
+              {"HB_Q2M_G": "1", "HB_Q2M_CT": "16", "HB_Q2M_SC": "0"}, {"HB_Q2M_G": "0", "HB_Q2M_SC": "0"}]
+
+
+def _matrix_core_matvec_gives_the_int8_integers(shape, monkeypatch, make):
     for k, v in shape.items():
         monkeypatch.setenv(k, v)
     rng = np.random.default_rng(31)
     for n, m, panel in ((2000, 1024, 512), (1300, 640, 128), (5100, 2048, 512)):    # ld = 2048, 1536 (odd multiple of 256), 5120
-        X = rand_geno(rng, n, m)
+        X = make(rng, n, m)
         r = rng.normal(0, 3.0, n)
         r[rng.integers(0, n, 5)] *= 1e6
         with H.Context(n, m, panel=panel, precise=2) as c:
@@ -289,14 +300,27 @@ def test_every_shape_of_the_matrix_core_matvec_gives_the_same_integers(shape, mo
             assert np.array_equal(c.dot(), d8), (shape, n, m)
 
 
-def test_two_bit_layout_pack_unpack_dot_and_products():
-    """SURVEY §8 f1 (second half): genotypes resident at PLINK's density, 2 bits each (reference src/read_bed.cpp:116-167 is
-    the format; hb_dotq2.hpp the packed word). Packing on the device, dropping the int8 copy, unpacking (genotype download),
-    the fixed-point mat-vec and X * alpha must all give what the int8 layout gives — the dot products bit for bit: they are
-    exact integers either way (checked against a Python big-integer dot product)."""
+@pytest.mark.parametrize("shape", Q2M_SHAPES)
+def test_every_shape_of_the_matrix_core_matvec_gives_the_same_integers(shape, monkeypatch):
+    """k_dotq2m's template shapes (hb_dotq2.hpp; round 5): 256-individual stages singly or in pairs, 512-individual stages of whole-line DMA
+    pieces in plain and in bank-conflict-free lane order (the default is G = 0), 64 / 128 / 256 columns per wave, one accumulator set per
+    genotype scale or one in all. Integer sums in another order: every shape must give the int8 layout's dot products bit for bit, on
+    a padded length that is a multiple of 512 and on one that is not (the 512-individual shapes then fall back to 256)."""
+    _matrix_core_matvec_gives_the_int8_integers(shape, monkeypatch, rand_geno)
+
+
+@pytest.mark.parametrize("shape", Q2M_SHAPES)
+def test_every_shape_of_the_matrix_core_matvec_with_code_three(shape, monkeypatch):
+    """The same shapes on genotypes with code 3: in the scaled shapes (HB_Q2M_SC, the default) a 3 at sub-position 3 of a byte is masked as
+    (w >> 1) & 0x60606060 because 0xc0 would be a negative int8; in the unscaled ones it is shifted down. An all-3 column carries the
+    largest partial sums a tile can hold."""
+    _matrix_core_matvec_gives_the_int8_integers(shape, monkeypatch, rand_geno3)
+
+
+def _two_bit_layout_pack_unpack_dot_and_products(make):
     rng = np.random.default_rng(22)
     for n, m, panel in ((777, 300, 64), (1300, 1100, 128), (5000, 1024, 512)):   # ld = 1024 (two stages of 512), 1536 (an odd multiple of 256), 5120
-        X = rand_geno(rng, n, m)
+        X = make(rng, n, m)
         r = rng.normal(0, 3.0, n)
         r[rng.integers(0, n, 5)] *= 1e6
         with H.Context(n, m, panel=panel, precise=2) as c:
@@ -304,6 +328,7 @@ def test_two_bit_layout_pack_unpack_dot_and_products():
             c.set_residual(r, np.zeros(n))
             d8 = c.dot()
             xpx8, vx8, sumvx8, nvar08 = c.marker_stats()
+            assert np.array_equal(xpx8, (X.astype(np.int64) ** 2).sum(0))
             c.set_layout(2, keep_int8=True)
             assert c.layout() == (2, True)
             assert np.array_equal(c.dot(), d8)                # identical integers -> identical doubles
@@ -335,6 +360,21 @@ def test_two_bit_layout_pack_unpack_dot_and_products():
             assert c.layout() == (8, True) and np.array_equal(c.download(), X) and np.array_equal(c.dot(), d8)
 
 
+def test_two_bit_layout_pack_unpack_dot_and_products():
+    """SURVEY §8 f1 (second half): genotypes resident at PLINK's density, 2 bits each (reference src/read_bed.cpp:116-167 is
+    the format; hb_dotq2.hpp the packed word). Packing on the device, dropping the int8 copy, unpacking (genotype download),
+    the fixed-point mat-vec and X * alpha must all give what the int8 layout gives — the dot products bit for bit: they are
+    exact integers either way (checked against a Python big-integer dot product)."""
+    _two_bit_layout_pack_unpack_dot_and_products(rand_geno)
+
+
+def test_two_bit_layout_with_code_three():
+    """The same on codes 0..3 (the layout's whole alphabet, hb_ctx.hip: "codes 0..3"; the run picks 2 bits by itself when max x <= 3): a
+    genotype with both bits set at every position of a packed word, and a column that is all 3. Pack, unpack, the dot products of the three
+    2-bit kernels (bit for bit the Python big-integer product), X * alpha, the sample product and the marker statistics."""
+    _two_bit_layout_pack_unpack_dot_and_products(rand_geno3)
+
+
 def test_two_bit_layout_refuses_what_it_cannot_hold():
     rng = np.random.default_rng(23)
     X = rand_geno(rng, 300, 200, signed=True)               # -1 / 0 / 1 coding (README.md:55-59): int8 layout only
@@ -349,13 +389,10 @@ def test_two_bit_layout_refuses_what_it_cannot_hold():
             c.set_layout(2)
 
 
-def test_gram_rebuild_from_the_two_bit_layout_alone():
-    """A context that dropped its int8 copy (hb_ctx_set_layout(c, 2, 0)) and is then asked for a wider band rebuilds the Gram blocks
-    from the packed genotypes: a window of panels at a time is unpacked into a scratch buffer (never the whole matrix), and every
-    block is the exact int32 product."""
+def _gram_rebuild_from_the_two_bit_layout_alone(make):
     rng = np.random.default_rng(31)
     n, panel, m = 900, 64, 64 * 9 + 5
-    X = rand_geno(rng, n, m)
+    X = make(rng, n, m)
     with H.Context(n, m, panel=panel, precise=2) as c:
         c.upload(X)
         c.set_pipeline(1, 1, 1)
@@ -372,3 +409,15 @@ def test_gram_rebuild_from_the_two_bit_layout_alone():
             for l in range(0, min(band, p) + 1):
                 a, b = Xi[:, (p - l) * panel:(p - l + 1) * panel], Xi[:, p * panel:(p + 1) * panel]
                 assert np.array_equal(c.gram_band(p, l), a.T @ b), (p, l)
+
+
+def test_gram_rebuild_from_the_two_bit_layout_alone():
+    """A context that dropped its int8 copy (hb_ctx_set_layout(c, 2, 0)) and is then asked for a wider band rebuilds the Gram blocks
+    from the packed genotypes: a window of panels at a time is unpacked into a scratch buffer (never the whole matrix), and every
+    block is the exact int32 product."""
+    _gram_rebuild_from_the_two_bit_layout_alone(rand_geno)
+
+
+def test_gram_rebuild_from_the_two_bit_layout_alone_with_code_three():
+    """... and on codes 0..3: entries up to 9 n from the all-3 column, unpacked from fields with both bits set."""
+    _gram_rebuild_from_the_two_bit_layout_alone(rand_geno3)
