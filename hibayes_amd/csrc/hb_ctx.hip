@@ -277,6 +277,7 @@ int hb_ctx_create(const hb_ctx_params *p, hb_ctx **out)
             hb_ctx_destroy(c);
             return hb_fail(HB_ERR_HIP, std::string("hipHostMalloc: ") + hipGetErrorString(e));
         }
+        memset(c->h_in, 0, sizeof(hb_sweep_in)); // (model_index 0: no sweep yet, hb_ctx_debug_get_pre)
     }
 #undef TRY
     // the allocation memsets ran on the null stream, which the context's non-blocking streams do not wait for
@@ -957,6 +958,21 @@ extern "C" int hb_ctx_debug_inject_abort(hb_ctx *c, int32_t panel, int32_t times
     c->inject_abort_panel = times > 0 ? panel : -1;
     c->inject_abort_times = times;
     if (panel >= 0 && !c->s_dbg) HB_HIP(hipStreamCreateWithFlags(&c->s_dbg, hipStreamNonBlocking));
+    return HB_OK;
+}
+
+extern "C" int hb_ctx_debug_get_pre(hb_ctx *c, int32_t *kpad, double *thr, double *invv, double *sdz)
+{
+    int rc = check_cols(c, 0, 0, "hb_ctx_debug_get_pre");
+    if (rc) return rc;
+    if (!c->h_in || c->h_in->model_index == 0) return hb_fail(HB_ERR_INVALID, "hb_ctx_debug_get_pre: no sweep has run on this context");
+    HB_HIP(hipStreamSynchronize(c->stream));
+    const int kp = kpad_for(c->h_in->model_index, c->h_in->n_fold); // (h_in: the parameters of the last sweep enqueued)
+    const size_t bytes = sizeof(double) * (size_t)kp * (size_t)c->m_pad;
+    if (kpad) *kpad = kp;
+    if (thr) HB_HIP(hipMemcpy(thr, c->thr, bytes, hipMemcpyDeviceToHost));
+    if (invv) HB_HIP(hipMemcpy(invv, c->invv, bytes, hipMemcpyDeviceToHost));
+    if (sdz) HB_HIP(hipMemcpy(sdz, c->sdz, bytes, hipMemcpyDeviceToHost));
     return HB_OK;
 }
 

@@ -98,6 +98,14 @@ class Context:
         """Debug hook: abort the next `times` pipeline sweeps once the chain has published `panel` panels (hb_run_step replays them)."""
         check(self.L.hb_ctx_debug_inject_abort(self.h, panel, times))
 
+    def pre(self):
+        """Debug read-out: (thr, invv, sdz) as k_pre left them in the last sweep, each kpad x m_pad (m_pad = whole panels)."""
+        m_pad = -(-self.m // self.panel) * self.panel
+        out = [np.zeros((7, m_pad)) for _ in range(3)]
+        kp = C.c_int32()
+        check(self.L.hb_ctx_debug_get_pre(self.h, C.byref(kp), *[x.ctypes.data for x in out]))
+        return tuple(x[:kp.value].copy() for x in out)
+
     def build_gram(self):
         s = C.c_double()
         check(self.L.hb_ctx_build_gram(self.h, C.byref(s)))

@@ -524,6 +524,11 @@ int hb_ctx_matvec_stamps(hb_ctx *c, hb_launch_stats *out);
  * hb_ctx_sweep_end() returns HB_ERR_ABORTED for them; hb_run_step() restores the saved state and replays (twice on the pipeline,
  * then on the per-panel kernels, which the hook does not touch). times <= 0 disarms it. */
 int hb_ctx_debug_inject_abort(hb_ctx *c, int32_t panel, int32_t times);
+/* Debug read-out for the kernel-level tests (tests/test_gpu_boundary.py): what k_pre left for the chain in the last sweep of the context —
+ * the thresholds on rhs^2, 1/v and sd*z — as kpad rows of m_pad doubles each (m_pad = the markers rounded up to whole panels; kpad = 1,
+ * or BayesR's n_fold - 1 rounded up to 3 or 7; rows and columns beyond the model's are (+inf, 0, 0)). Synchronises the context's stream and
+ * changes nothing; any of the pointers may be NULL. Fails before the first sweep. */
+int hb_ctx_debug_get_pre(hb_ctx *c, int32_t *kpad, double *thr, double *invv, double *sdz);
 
 #ifdef __cplusplus
 }

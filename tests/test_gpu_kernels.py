@@ -104,6 +104,76 @@ def test_panel_matvec_against_fp64(signed):
     assert np.max(np.abs(d - ref) / scale) < 2e-6                       # fp32 accumulation: stated tolerance
 
 
+def _digit_edge_residuals(n, rng):
+    """Residuals at the edges of the quantiser (k_absmax, k_quant0, hb_store_digits): name -> vector. Rows 0..6 of most hold values whose
+    scaled integer r 2^E is exactly 1, 1.5, -0.5, 0.5, -1.5, 2.5, -2.5 — ties, to even — and which give another sum on any other E."""
+    def with_max(top, E, body=True):
+        r = np.zeros(n)
+        if body:
+            r[7:n - 1] = np.ldexp(rng.normal(0, 0.1, n - 8), 53 - E)
+        r[:7] = np.ldexp([1.0, 1.5, -0.5, 0.5, -1.5, 2.5, -2.5], -E)
+        r[n - 1] = top                                     # the maximum alone in the last row, ragged or not
+        assert np.abs(r).argmax() == n - 1 and (np.abs(r[:n - 1]) < abs(top)).all()
+        return r
+
+    out = {"zero": np.zeros(n)}
+    for k in (-20, 0, 20):
+        for s in (1.0, -1.0):
+            out["max=%+g*2^%d" % (s, k)] = with_max(s * 2.0 ** k, 53 - k)                             # |q| = 2^53
+            out["max=%+g*(2^%d-ulp)" % (s, k)] = with_max(s * np.nextafter(2.0 ** k, 0.0), 54 - k)    # |q| = 2^54 - 2
+    top = np.nextafter(1.0, 0.0)
+    out["every row at the maximum"] = np.full(n, top)
+    out["every row at the maximum, signs"] = top * rng.choice([-1.0, 1.0], size=n)
+    # carries: 0x80 in every byte is digit -128 and a carry into the next plane, seven times over; 0x7f in every byte is the largest digit
+    # without one. (The issue's 0x7f7f7f7f7f7f7f has 55 bits: no residual quantises to it, |q| < 2^54 and a double holds 53 bits.)
+    r = with_max(1.0, 53, body=False)
+    qs = [0x1f808080808080, 0x1f7f7f7f7f7f7f, 0x007f7f7f7f7f7f, 0x00808080808080, 0x1fffffffffffff, 0x00ffffffffff80]
+    for i, q in enumerate(qs):
+        r[10 + 2 * i], r[11 + 2 * i] = np.ldexp(float(q), -53), -np.ldexp(float(q), -53)
+        assert int(np.ldexp(r[10 + 2 * i], 53)) == q
+    out["carries through the seven digits"] = r
+    r = with_max(2.0 ** 20, 33, body=False)                # a range of 2^60: the small end quantises to 0
+    r[7:67] = np.ldexp(rng.choice([-1.0, 1.0], size=60), 20 - np.arange(1, 61))
+    out["range 2^60"] = r
+    return out
+
+
+@pytest.mark.parametrize("n", [257, 1021, 1300])
+def test_quantiser_and_finalize_at_the_digit_edges(n):
+    """The fixed-point mat-vec (precise = 2) on residuals at the quantiser's edges, by the int8 layout's kernel and the three 2-bit ones:
+    the four agree bit for bit, and the result is the Python big-integer product of the genotypes with q = rint(r 2^E),
+    E = 53 - ilogb(max |r|) (0 for the zero vector), scaled back. hbq_finalize is a Horner recurrence in double over the seven plane sums,
+    a = fma(a, 256, acc_k): every step is exact while |a| < 2^53, so with the exact sum below 2^61 only the last step rounds and the result
+    is the correctly rounded product; from 2^61 on the last two steps can round (sums here stay below 2^69), and it is within 1 ulp."""
+    rng = np.random.default_rng(n)
+    X = rand_geno3(rng, n, 192)
+    Xo = X.astype(object).T
+    cases = _digit_edge_residuals(n, rng)
+    with H.Context(n, 192, panel=64, precise=2) as c8, H.Context(n, 192, panel=64, precise=2) as c2:
+        c8.upload(X)
+        c2.upload(X)
+        c2.set_layout(2, keep_int8=False)
+        big = 0
+        for name, r in cases.items():
+            c8.set_residual(r, np.zeros(n))
+            c2.set_residual(r, np.zeros(n))
+            d = c8.dot()
+            for kind in (0, 1, 2):
+                c2.set_matvec_kernel(kind)
+                assert np.array_equal(c2.dot().view(np.uint64), d.view(np.uint64)), (name, kind)
+            mx = np.abs(r).max()
+            E = 54 - int(np.frexp(mx)[1]) if mx > 0 else 0  # (frexp's exponent is ilogb + 1)
+            q = np.rint(np.ldexp(r, E))
+            assert np.abs(q).max() < 2.0 ** 54
+            exact = Xo @ np.array([int(v) for v in q], dtype=object)
+            want = np.array([np.ldexp(float(v), -E) for v in exact])
+            small = np.array([abs(v) < 2 ** 61 for v in exact])
+            big += int((~small).sum())
+            assert np.array_equal(d[small], want[small]), name
+            assert (np.abs(d[~small] - want[~small]) <= np.spacing(np.abs(want[~small]))).all(), name
+        assert big > 0                                      # both rules were used
+
+
 def test_matvec_and_residual_helpers():
     rng = np.random.default_rng(4)
     n, m = 2000, 900
