@@ -135,6 +135,15 @@ class SBayesOut(C.Structure):
     ]
 
 
+class LdmStats(C.Structure):
+    """hb_ldm_stats"""
+    _fields_ = [
+        ("m", C.c_int32), ("kind", C.c_int32), ("on_device", C.c_int32), ("n_strips", C.c_int32), ("nnz", C.c_int64),
+        ("seconds", C.c_double), ("stats_seconds", C.c_double), ("strip_seconds", C.c_double), ("compact_seconds", C.c_double),
+        ("transfer_seconds", C.c_double),
+    ]
+
+
 class RunInfo(C.Structure):
     _fields_ = [
         ("iter", C.c_int32), ("records", C.c_int32), ("nnz", C.c_double),
@@ -200,6 +209,9 @@ SYMBOLS = [
     "hb_comm_unique_id", "hb_comm_init", "hb_comm_world", "hb_comm_rank", "hb_comm_selftest", "hb_comm_destroy",
     "hb_ctx_debug_inject_abort", "hb_ctx_debug_get_pre", "hb_ctx_set_matvec_kernel", "hb_ctx_time_stream_read",
     "hb_run_create", "hb_run_step", "hb_run_state", "hb_run_ctx", "hb_run_finish", "hb_run_destroy",
+    # ldmat(): R/ldm.r:31-112, src/tXXmat.cpp:43-77 (BigStat), :100-206 (tXXmat_Geno), :504-626 (tXXmat_Chr)
+    "hb_ldm_build", "hb_ldm_info", "hb_ldm_download_dense", "hb_ldm_download_csc", "hb_ldm_destroy",
+    "hb_sbayes_run_ldm",  # ldmat() -> sbrm(), R/ldm.r:88 -> R/sbayes.r:213, from the handle's device copy
 ]
 
 
@@ -232,6 +244,13 @@ def lib():
     L.hb_exchange_count.argtypes = [C.c_int32]
     L.hb_bayes_run.argtypes = [C.POINTER(BayesArgs), C.POINTER(BayesOut)]
     L.hb_sbayes_run.argtypes = [C.POINTER(SBayesArgs), C.POINTER(SBayesOut)]
+    L.hb_sbayes_run_ldm.argtypes = [C.POINTER(SBayesArgs), C.c_void_p, C.POINTER(SBayesOut)]
+    L.hb_ldm_build.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_int64, C.POINTER(C.c_void_p)]
+    L.hb_ldm_info.argtypes = [C.c_void_p, C.POINTER(LdmStats)]
+    L.hb_ldm_download_dense.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    L.hb_ldm_download_csc.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.hb_ldm_destroy.argtypes = [C.c_void_p]
+    L.hb_ldm_destroy.restype = None
     L.hb_ctx_create.argtypes = [C.POINTER(CtxParams), C.POINTER(C.c_void_p)]
     L.hb_ctx_destroy.argtypes = [C.c_void_p]
     L.hb_ctx_destroy.restype = None

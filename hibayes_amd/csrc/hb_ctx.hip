@@ -7,6 +7,8 @@
 #include <cstring>
 #include <cstdlib>
 #include <cstdio>
+#include <mutex>
+#include <unordered_set>
 
 // launch wrappers implemented in hb_kernels.hip
 int hbk_init_attrs();
@@ -35,6 +37,15 @@ int hbk_pack2(hb_ctx *c);
 int hbk_unpack2(hb_ctx *c, int col0, int ncols, int8_t *dst);
 
 static thread_local std::string g_err;
+
+// contexts that were given genotypes (upload / decode / generate): hb_ldm_build refuses the others before any device work
+static std::mutex g_loaded_mu;
+static std::unordered_set<const hb_ctx *> g_loaded;
+bool hb_ctx_has_genotypes(const hb_ctx *c)
+{
+    std::lock_guard<std::mutex> lk(g_loaded_mu);
+    return g_loaded.count(c) != 0;
+}
 
 void hb_set_error(const std::string &msg) { g_err = msg; }
 int hb_fail(int status, const std::string &msg)
@@ -314,6 +325,10 @@ static void blocks_free(hb_ctx *c);
 void hb_ctx_destroy(hb_ctx *c)
 {
     if (!c) return;
+    {
+        std::lock_guard<std::mutex> lk(g_loaded_mu);
+        g_loaded.erase(c);
+    }
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (auto &ge : c->gcache) {
@@ -356,6 +371,10 @@ static int check_cols(hb_ctx *c, int col0, int ncols, const char *who)
 
 static void invalidate(hb_ctx *c)
 {
+    {
+        std::lock_guard<std::mutex> lk(g_loaded_mu);
+        g_loaded.insert(c);
+    }
     c->gram_ready = false;
     c->stats_ready = false;
     if (c->layout == 2) { // new genotypes: the packed copy is stale

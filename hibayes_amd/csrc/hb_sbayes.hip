@@ -2,6 +2,7 @@
 // the outer MCMC loop with its hyper-parameter draws and the posterior assembly; every m-long operation runs on the device
 // (hb_sbayes.hpp). SURVEY §8 f4.
 #include "hb_internal.hpp"
+#include "hb_ldm.hpp"
 #include "hb_rng.hpp"
 #include <algorithm>
 #include <chrono>
@@ -53,13 +54,15 @@ struct sb_run {
 };
 } // namespace
 
-extern "C" int hb_sbayes_run(const hb_sbayes_args *args, hb_sbayes_out *o)
+// hb_sbayes_run (H == nullptr: the matrix is args->ldm on the host) and hb_sbayes_run_ldm (the matrix is the handle's dense device copy)
+static int sbayes_run(const hb_sbayes_args *args, hb_ldm *H, hb_sbayes_out *o)
 {
     if (!args || !o) return hb_fail(HB_ERR_INVALID, "hb_sbayes_run: null argument");
     const auto t_setup = clk::now();
     const hb_sbayes_args &a = *args;
     const int m = a.m;
-    if (m < 1 || !a.sumstat || !a.ldm || a.ld_sumstat < m || a.ld_ldm < m) return hb_fail(HB_ERR_INVALID, "Number of SNPs not equals."); // :29-31
+    if (H ? (m < 1 || !a.sumstat || a.ldm || a.ld_sumstat < m || H->m != m)
+          : (m < 1 || !a.sumstat || !a.ldm || a.ld_sumstat < m || a.ld_ldm < m)) return hb_fail(HB_ERR_INVALID, "Number of SNPs not equals."); // :29-31
     if (!a.model) return hb_fail(HB_ERR_INVALID, "hb_sbayes_run: model is NULL");
     const std::string model = a.model;
     auto line = [&](const char *fmt, ...) {
@@ -131,7 +134,7 @@ extern "C" int hb_sbayes_run(const hb_sbayes_args *args, hb_sbayes_out *o)
     // ---- :95-115 ----
     std::vector<double> vx(m), xpx(m), xy(m, 0.0), yyi(m, 0.0), ifest(m, 1.0);
     for (int i = 0; i < m; i++) {
-        vx[i] = a.ldm[(size_t)i * a.ld_ldm + i];
+        vx[i] = H ? H->diag[i] : a.ldm[(size_t)i * a.ld_ldm + i];
         xpx[i] = vx[i] * n;
     }
     int count_y = 0, nvar0 = 0;
@@ -176,6 +179,7 @@ extern "C" int hb_sbayes_run(const hb_sbayes_args *args, hb_sbayes_out *o)
 
     // ---- device ----
     if (hb_device_count() <= 0) return hb_fail(HB_ERR_NO_DEVICE, "no HIP device available: the hibayes GPU engine has no CPU fallback");
+    if (H && H->device != a.device) return hb_fail(HB_ERR_INVALID, "hb_sbayes_run_ldm: the LD matrix was built on another device");
     HB_HIP(hipSetDevice(a.device));
     sb_run R;
     hb_sb_dev &d = R.d;
@@ -187,7 +191,13 @@ extern "C" int hb_sbayes_run(const hb_sbayes_args *args, hb_sbayes_out *o)
     d.nw = nw;
     int rc;
 #define TRYA(x) do { rc = (x); if (rc) return rc; } while (0)
-    TRYA(R.alloc(&d.ldm, (size_t)m * m));
+    if (H) { // adopted, not owned: the sweep only reads it
+        const double *dl = nullptr;
+        TRYA(hb_ldm_device_dense(H, &dl));
+        d.ldm = const_cast<double *>(dl);
+    } else {
+        TRYA(R.alloc(&d.ldm, (size_t)m * m));
+    }
     TRYA(R.alloc(&d.r_hat, d.m_pad));
     TRYA(R.alloc(&d.xy, d.m_pad));
     TRYA(R.alloc(&d.g, d.m_pad));
@@ -212,7 +222,7 @@ extern "C" int hb_sbayes_run(const hb_sbayes_args *args, hb_sbayes_out *o)
     }
     HB_HIP(hipHostMalloc(reinterpret_cast<void **>(&R.h_acc), sizeof(double) * HB_ACC_N));
     HB_HIP(hipHostMalloc(reinterpret_cast<void **>(&R.h_in), sizeof(hb_sweep_in)));
-    HB_HIP(hipMemcpy2DAsync(d.ldm, sizeof(double) * m, a.ldm, sizeof(double) * a.ld_ldm, sizeof(double) * m, m, hipMemcpyHostToDevice, d.stream));
+    if (!H) HB_HIP(hipMemcpy2DAsync(d.ldm, sizeof(double) * m, a.ldm, sizeof(double) * a.ld_ldm, sizeof(double) * m, m, hipMemcpyHostToDevice, d.stream));
     HB_HIP(hipMemcpyAsync(d.xy, xy.data(), sizeof(double) * m, hipMemcpyHostToDevice, d.stream));
     HB_HIP(hipMemcpyAsync(d.r_hat, xy.data(), sizeof(double) * m, hipMemcpyHostToDevice, d.stream)); // :108 r_hat = xy
     HB_HIP(hipMemcpyAsync(d.xpx, xpx.data(), sizeof(double) * m, hipMemcpyHostToDevice, d.stream));
@@ -421,4 +431,12 @@ extern "C" int hb_sbayes_run(const hb_sbayes_args *args, hb_sbayes_out *o)
     line("Finished: set-up %.2fs, MCMC %.2fs, %.1f sweeps/s", setup_seconds, loop_seconds, loop_seconds > 0 ? iter / loop_seconds : 0.0);
     return HB_OK;
 #undef TRYA
+}
+
+extern "C" int hb_sbayes_run(const hb_sbayes_args *args, hb_sbayes_out *o) { return sbayes_run(args, nullptr, o); }
+
+extern "C" int hb_sbayes_run_ldm(const hb_sbayes_args *args, hb_ldm *ldm, hb_sbayes_out *o)
+{
+    if (!ldm) return hb_fail(HB_ERR_INVALID, "hb_sbayes_run_ldm: null LD matrix handle");
+    return sbayes_run(args, ldm, o);
 }

@@ -16,7 +16,7 @@ class Context:
         p = CtxParams(device=device, n=n, m=m, panel=panel, precise=int(precise), m_offset=m_offset, seed=seed)
         h = C.c_void_p()
         check(self.L.hb_ctx_create(C.byref(p), C.byref(h)))
-        self.h, self.n, self.m = h, n, m
+        self.h, self.n, self.m, self.device = h, n, m, device
 
     def close(self):
         if self.h:
@@ -116,6 +116,19 @@ class Context:
         G = np.zeros((P, P), dtype=np.int32)
         check(self.L.hb_ctx_download_gram(self.h, p, G.ctypes.data))
         return G
+
+    def ldmat(self, chr=None, chisq=None, strip_bytes=0):
+        """The LD variance-covariance matrix of the resident genotypes as an LDMatrix (hb_ldm_build; ldmat() of the reference,
+        R/ldm.r:88-91): chr = m chromosome ids for one block per chromosome or None for the genome-wide matrix, chisq = None or the
+        sparsification threshold. hibayes_amd.ldmat() is the full mirror with the reference's argument handling."""
+        from .ldm import LDMatrix
+        ch = None if chr is None else np.ascontiguousarray(chr, dtype=np.int32)
+        if ch is not None and ch.shape != (self.m,):
+            raise ValueError("chr must hold one chromosome id per marker")
+        h = C.c_void_p()
+        check(self.L.hb_ldm_build(self.h, None if ch is None else ch.ctypes.data, 0 if chisq is None else 1,
+                                  0.0 if chisq is None else float(chisq), int(strip_bytes), C.byref(h)))
+        return LDMatrix(h, self.device)
 
     def pipeline_note(self):
         v = self.L.hb_ctx_pipeline_note(self.h)

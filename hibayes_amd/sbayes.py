@@ -6,20 +6,29 @@ import ctypes as C
 import numpy as np
 
 from ._lib import LOG_FN, SBayesArgs, SBayesOut, check, lib
+from .ldm import LDMatrix
 
 
 def SBayesD(sumstat, ldm, model, Pi, niter=50000, nburn=20000, thin=5, fold=None, windindx=None, vg=None, dfvg=None, s2vg=None,
             ve=None, dfve=None, s2ve=None, outfreq=100, threads=0, verbose=True, *, seed=666666, device=0, store_alpha=True, log=None):
-    """sumstat: m x 4 (MAF, BETA, SE, NMISS — what sbrm() keeps of the COJO file, R/sbayes.r:207; NaN = NA); ldm: m x m dense."""
+    """sumstat: m x 4 (MAF, BETA, SE, NMISS — what sbrm() keeps of the COJO file, R/sbayes.r:207; NaN = NA); ldm: m x m dense,
+    or an LDMatrix (ldmat(..., keep_on_device=True)): the run then reads the handle's device copy (hb_sbayes_run_ldm; a sparse
+    or per-chromosome handle as the dense matrix with zeros where it stores nothing) on the handle's device."""
     L = lib()
     ss = np.asfortranarray(sumstat, dtype=np.float64)
-    ld = np.asfortranarray(ldm, dtype=np.float64)
+    handle = ldm if isinstance(ldm, LDMatrix) else None
+    ld = None if handle is not None else np.asfortranarray(ldm, dtype=np.float64)
     if ss.ndim != 2 or ss.shape[1] != 4:
         raise ValueError("sumstat must have the four columns MAF, BETA, SE, NMISS")
     m = ss.shape[0]
     a = SBayesArgs()
-    a.m = m if ld.ndim == 2 and ld.shape[0] == m and ld.shape[1] == m else -1   # -> "Number of SNPs not equals."
-    a.sumstat, a.ld_sumstat, a.ldm, a.ld_ldm = ss.ctypes.data, m, ld.ctypes.data, (ld.shape[0] if ld.ndim == 2 else 0)
+    if handle is not None:
+        a.m = m if handle.shape[0] == m else -1
+        a.sumstat, a.ld_sumstat, a.ldm, a.ld_ldm = ss.ctypes.data, m, None, 0
+        device = handle.device
+    else:
+        a.m = m if ld.ndim == 2 and ld.shape[0] == m and ld.shape[1] == m else -1   # -> "Number of SNPs not equals."
+        a.sumstat, a.ld_sumstat, a.ldm, a.ld_ldm = ss.ctypes.data, m, ld.ctypes.data, (ld.shape[0] if ld.ndim == 2 else 0)
     a.model = model.encode()
     pv = np.ascontiguousarray(Pi, dtype=np.float64)
     a.Pi, a.n_pi = pv.ctypes.data, pv.size
@@ -59,7 +68,10 @@ def SBayesD(sumstat, ldm, model, Pi, niter=50000, nburn=20000, thin=5, fold=None
     o.s_alpha = buf(mc, "alpha", (mm, nrec)) if store_alpha else None
     o.s_pi = buf(mc, "pi", (pv.size, nrec))
     o.r_hat, o.g_last = buf(res, "r_hat", mm), buf(res, "g_last", mm)
-    check(L.hb_sbayes_run(C.byref(a), C.byref(o)))
+    if handle is not None:
+        check(L.hb_sbayes_run_ldm(C.byref(a), handle._handle(), C.byref(o)))
+    else:
+        check(L.hb_sbayes_run(C.byref(a), C.byref(o)))
     for k in ("Vg", "Ve", "h2", "n_records", "nzct", "nw", "n", "count_y"):
         res[k] = getattr(o, k)
     res["MCMCsamples"] = mc
@@ -80,7 +92,7 @@ def sbrm(sumstat, ldm, method="BayesB", map=None, Pi=None, fold=None, niter=None
             raise NotImplementedError("a sparse ldm (dgCMatrix: SBayesS, src/SBayesS.cpp) is outside the GPU path; pass the dense LD matrix")
     except ImportError:
         pass
-    if not (isinstance(ldm, np.ndarray) or hasattr(ldm, "__array__")):
+    if not (isinstance(ldm, (np.ndarray, LDMatrix)) or hasattr(ldm, "__array__")):
         raise ValueError("Unrecognized type of ldm.")
     if method == "CG":
         raise NotImplementedError("method = 'CG' (conjgt_den / conjgt_spa) is outside the GPU path")

@@ -326,6 +326,51 @@ typedef struct hb_sbayes_out {
 
 int hb_sbayes_run(const hb_sbayes_args *args, hb_sbayes_out *out);
 
+/* ------------------------------------------------------------------------------------
+ * The LD variance-covariance matrix of a context's resident genotypes: replaces ldmat(), reference R/ldm.r:31-112, i.e.
+ * BigStat (src/tXXmat.cpp:43-77) and tXXmat_Geno (:100-206) / tXXmat_Chr (:504-626); the four *_gwas variants (:208-502,
+ * :628-) are out of scope. The cross-products run on the matrix cores as exact integers, the reference's fp64 arithmetic
+ * follows per entry in its own order (`p12 -= sum1 * m2 + sum2 * m1 - ind * m1 * m2; p12 / ind`, :145-152, with the marker of
+ * the smaller index in the sum1 / m1 role): every entry equals the reference's bit for bit.
+ * ------------------------------------------------------------------------------------ */
+typedef struct hb_ldm hb_ldm; /* a finished LD matrix: host copy (pinned), optionally a dense device copy for the sampler */
+
+enum {
+    HB_LDM_KIND_DENSE = 0,        /* tXXmat_Geno, dense arm (:158-184): diagonal xx * xx / ind (:168)                      */
+    HB_LDM_KIND_SPARSE = 1,       /* tXXmat_Geno, sparse arm (:124-157): entries with r * r * ind <= chisq dropped (:147),
+                                     the diagonal through the same formula and test                                        */
+    HB_LDM_KIND_BLOCK_DENSE = 2,  /* tXXmat_Chr without chisq (:565-604): nothing across chromosomes, sp_mat result        */
+    HB_LDM_KIND_BLOCK_SPARSE = 3  /* tXXmat_Chr with chisq (:527-564), chisq = 0 included (:520-523)                       */
+};
+
+typedef struct hb_ldm_stats {
+    int32_t m, kind;
+    int32_t on_device;       /* a dense m x m device copy (leading dimension m) is held */
+    int32_t n_strips;        /* column strips the build took */
+    int64_t nnz;             /* stored entries (m * m for HB_LDM_KIND_DENSE) */
+    double seconds;          /* the whole build */
+    double stats_seconds, strip_seconds, compact_seconds, transfer_seconds; /* BigStat / cross-products and epilogue /
+                                compaction to (row, value) lists / device-to-host copies */
+} hb_ldm_stats;
+
+/* chr: m chromosome ids (tXXmat_Chr's `chr`, R/ldm.r:91; markers of one id need not be contiguous, :531) or NULL for the
+ * genome-wide matrix (R/ldm.r:88). has_chisq / chisq: Nullable<double> chisq. The mode follows the reference: without chr
+ * sparse iff chisq > 0 (src/tXXmat.cpp:117-120), with chr sparse iff chisq is given (:520-523), block-dense otherwise.
+ * strip_bytes: device staging per column strip, 0 = at most 1 GiB. The context must hold genotypes (int8 or 2-bit resident)
+ * with max|x|^2 * n < 2^31, as for hb_ctx_build_gram. */
+int hb_ldm_build(hb_ctx *ctx, const int32_t *chr, int32_t has_chisq, double chisq, int64_t strip_bytes, hb_ldm **out);
+int hb_ldm_info(const hb_ldm *ldm, hb_ldm_stats *stats);
+/* m x m column-major, zeros where a sparse or block matrix stores nothing (src/tXXmat.cpp:179, :152) */
+int hb_ldm_download_dense(hb_ldm *ldm, double *out, int64_t ldo);
+/* canonical CSC as arma::sp_mat / dgCMatrix holds it (src/tXXmat.cpp:152, :558, :599): indptr m + 1, indices and data nnz,
+ * rows sorted inside a column, no stored zero. Not for HB_LDM_KIND_DENSE. */
+int hb_ldm_download_csc(hb_ldm *ldm, int64_t *indptr, int32_t *indices, double *data);
+void hb_ldm_destroy(hb_ldm *ldm);
+
+/* hb_sbayes_run with args->ldm == NULL and the matrix taken from the handle's dense device copy (made on the device from the
+ * stored entries if the build kept none): ldmat() -> sbrm() (R/ldm.r:88 -> R/sbayes.r:213) with no host matrix in between. */
+int hb_sbayes_run_ldm(const hb_sbayes_args *args, hb_ldm *ldm, hb_sbayes_out *out);
+
 /* ====================================================================================
  * Fine-grained engine API.  hb_bayes_run() is built on it; the parity tests and bench.py
  * drive the device pieces through it one at a time.  A context owns all device state of
