@@ -1,6 +1,6 @@
 // hb_ctx.hip — device context of one genotype shard and the fine-grained C ABI on top of it.
 #include "hb_internal.hpp"
-#include "hb_plan.hpp"
+#include "hb_runplan.hpp"
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -83,19 +83,11 @@ static int dev_alloc_handoff(T **p, size_t count)
     return HB_OK;
 }
 
-// normalise (pipeline, Lv, D) and derive the Gram band / version ring sizes
+// normalise (pipeline, Lv, D) and derive the Gram band / version ring sizes (plan_geometry, hb_runplan.hpp)
 static void hb_pipeline_geometry(hb_ctx *c)
 {
-    if (!c->concurrent) c->pipeline = 0; // the persistent pipeline needs co-resident kernels (hbk_probe_concurrency)
-    c->Lv = std::max(0, std::min(6, c->Lv));
-    c->D = c->pipeline ? std::max(1, std::min(8, c->D)) : 1;
-    // Lv counts mat-vec GROUPS of look-ahead; the Gram band then spans (Lv + 1) * D - 1 earlier panels
-    const int lbmax = plan_band_limit(c->P, c->Lv, c->D);
-    while ((c->Lv + 1) * c->D - 1 > lbmax) {
-        if (c->Lv > 1) c->Lv--; else c->D--;
-    }
-    c->L = std::max((c->Lv + 1) * c->D - 1, c->Lv);
-    c->NB = c->Lv + 1;
+    const hb_geometry g = plan_geometry(c->concurrent, c->pipeline, c->P, c->Lv, c->D);
+    c->pipeline = g.pipeline, c->Lv = g.Lv, c->D = g.D, c->L = g.L, c->NB = g.NB;
 }
 
 extern "C" {
@@ -115,14 +107,6 @@ int hb_device_count(void)
 }
 
 size_t hb_exchange_count(int32_t n) { return (size_t)n + 16; }
-
-static int auto_panel(int m)
-{
-    if (m >= 4096) return 512;
-    if (m >= 1024) return 256;
-    if (m >= 256) return 128;
-    return 64;
-}
 
 // development aid (HB_DEBUG_SEGV=1): a native backtrace on SIGSEGV — there is no debugger in the image
 #include <execinfo.h>
@@ -148,7 +132,7 @@ int hb_ctx_create(const hb_ctx_params *p, hb_ctx **out)
     const int ndev = hb_device_count();
     if (ndev <= 0) return hb_fail(HB_ERR_NO_DEVICE, "no HIP device available: the hibayes GPU engine has no CPU fallback");
     if (p->device < 0 || p->device >= ndev) return hb_fail(HB_ERR_INVALID, "hb_ctx_create: bad device ordinal");
-    int P = p->panel ? p->panel : auto_panel(p->m);
+    const int P = plan_panel(p->m, false, p->panel);
     if (P != 64 && P != 128 && P != 256 && P != 512)
         return hb_fail(HB_ERR_INVALID, "hb_ctx_create: panel must be 64, 128, 256 or 512");
     HB_HIP(hipSetDevice(p->device));
@@ -614,12 +598,10 @@ int hb_ctx_switch_geometry(hb_ctx *c, int32_t pipeline, int32_t lookahead, int32
     int rc = check_cols(c, 0, 0, "hb_ctx_set_pipeline");
     if (rc) return rc;
     if (c->env_pinned && c->concurrent && !c->force_geometry) return HB_OK; // HB_PIPELINE / HB_LOOKAHEAD / HB_DOTGROUP in the environment win (tuning runs)
-    const int op = c->pipeline, ol = c->Lv, od = c->D;
     c->pipeline = pipeline ? 1 : 0;
     c->Lv = lookahead;
     c->D = dotgroup;
     hb_pipeline_geometry(c);
-    (void)op; (void)ol; (void)od;
     // the stored band serves every geometry whose band fits into it (the captured sweeps are cached per geometry)
     if (c->L > c->Lg) c->gram_ready = false;
     return HB_OK;

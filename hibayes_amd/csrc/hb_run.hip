@@ -11,6 +11,7 @@
 // three separately so that exactly K iterations sit between its barriers.
 #include "hb_internal.hpp"
 #include "hb_rng.hpp"
+#include "hb_runplan.hpp"
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -80,7 +81,9 @@ struct hb_run {
     double *r0 = nullptr, *u0 = nullptr, *xbuf_own = nullptr, *xbuf = nullptr;
     size_t xcount = 0;
     // ---- state of the chain ----
+    static constexpr double h2 = 0.5; // :119-124
     double vary = 0, sumvx = 0, ymean_glob = 0;
+    std::vector<double> vx_host; // the markers' variances from marker_statistics to start_chain, where a g_init needs them (monomorphic markers start at zero)
     int nvar0 = 0, nw = 0, n_levels = 0;
     std::vector<double> beta, cpc, beta_sum, vr, vrtmp, vr_sum, zz, estR, estR_sum, vara_fold, fold_snp_num, pi_sum;
     std::vector<int32_t> zid, nlev, lev_first;
@@ -93,14 +96,13 @@ struct hb_run {
     double mu_sum = 0, vara_sum = 0, vare_sum = 0, hsq_sum = 0, events_sum = 0, miss_sum = 0, redo_sum = 0;
     int sync_blocks = 1;       // runs of mat-vec groups per sweep, an exchange after each (hb_bayes_args.sync_blocks)
     bool recover_on = true;    // replay a sweep whose pipeline timed out (HB_RECOVER=0: fail the run, as before round 4)
+    int wide_lv = 2;           // look-ahead groups of the point-mass models' wide geometry (HB_WIDE_LV=3: 3)
+    bool no_adaptive_r = false, no_auto_bits = false; // HB_NO_ADAPTIVE_R, HB_NO_AUTO_BITS
     int pipeline_setup = -1;   // sharded runs: the context's pipeline switch as the ranks agreed on it in setup (checked at every step)
     int aborts = 0;            // sweeps replayed so far
     int abort_win_start = 0, abort_win_count = 0, slow_timeout = 0; // three aborts within 64 iterations: a slow device, the run's time-out is raised
-    bool adaptive_geo = false; // choose (Lv, D) per sweep from the previous sweep's moves (BayesB/C; round 6: BayesR)
-    int geo_wide_lv = 2;       // look-ahead groups of the wide geometry (3 with k_fwd beside the chain, else 2)
+    hb_regime regime{};        // geometry by regime (plan_regime, hb_runplan.hpp): choose (Lv, D) per sweep from the previous sweep's moves
     int geo_cur = 0;           // 0: the wide geometry — (2 | 3, 7) for BayesB / C, (2, 2) for BayesR; 1: the narrow one — (2, 2), (2, 1)
-    int geo_wide_d = 7, geo_narrow_lv = 2, geo_narrow_d = 2;
-    double geo_to_wide = 2.0, geo_to_narrow = 2.6; // moves per panel of the previous sweep below / above which the geometry changes
     double last_events_pp = 0;
     bool done = false;
     double setup_seconds = 0, gram_seconds = 0, loop_seconds = 0;
@@ -171,9 +173,37 @@ struct hb_run {
         for (double s : slot) *v = std::max(*v, s);
         return rc;
     }
+    // K sums over ALL individuals, the same numbers on every rank AND for every number of shards: partial sums of fixed 256-row chunks
+    // (add(i, p, nch) adds row i to its chunk's sums p[0], p[nch], ..., sequential inside a chunk), gathered over the ranks, added in chunk order
+    template <int K, class F>
+    int chunk_sums(double (&sum)[K], F add)
+    {
+        const size_t nch = (size_t)((n_glob + 255) / 256), c0 = (size_t)(row_off / 256);
+        std::vector<double> part(K * nch, 0.0);
+        for (int i = 0; i < n; i++) add(i, &part[c0 + (size_t)i / 256], nch);
+        const int rc = allreduce_chunks(part.data(), part.size());
+        if (rc) return rc;
+        for (int k = 0; k < K; k++) {
+            sum[k] = 0;
+            for (size_t ch = 0; ch < nch; ch++) sum[k] += part[k * nch + ch];
+        }
+        return HB_OK;
+    }
+    // arma::var, two-pass, N - 1, from the second pass's sums over all individuals
+    double var_glob(double a2, double a3) const { return n_glob > 1 ? (a2 - a3 * a3 / (double)n_glob) / (double)(n_glob - 1) : 0.0; }
     int row_stats_and_gram();
     int row_sums(double *sr, double *sr2, double *varu);
     int setup(const hb_bayes_args *args);
+    // setup's parts, in the order it calls them
+    int take_args();
+    int encode_random_effects();
+    int take_model_args();
+    int configure_device();
+    int open_exchange();
+    int marker_statistics();
+    int prior_defaults();
+    void console() const;
+    int start_chain();
     int step();
     int finish(hb_bayes_out *o);
 };
@@ -225,40 +255,29 @@ int hb_run::row_stats_and_gram()
     return HB_OK;
 }
 
-// sum(yadj), yadj.yadj, var(u) over ALL individuals, the same numbers on every rank AND for every number of shards: partial
-// sums of fixed 256-row chunks (sequential inside a chunk), gathered over the ranks, added in chunk order.
+// sum(yadj), yadj.yadj, var(u) over ALL individuals, the same numbers on every rank AND for every number of shards (chunk_sums)
 int hb_run::row_sums(double *sr, double *sr2, double *varu)
 {
     std::vector<double> r(n), u(n);
     int rc = hb_ctx_get_residual(c, r.data(), u.data());
     if (rc) return rc;
-    const size_t nch = (size_t)((n_glob + 255) / 256), c0 = (size_t)(row_off / 256);
-    std::vector<double> part(3 * nch, 0.0);
-    for (int i = 0; i < n; i++) {
-        const size_t ch = c0 + (size_t)i / 256;
-        part[ch] += r[i];
-        part[nch + ch] = std::fma(r[i], r[i], part[nch + ch]);
-        part[2 * nch + ch] += u[i];
-    }
-    rc = allreduce_chunks(part.data(), part.size());
+    double s[3], q[2];
+    rc = chunk_sums(s, [&](int i, double *p, size_t nch) {
+        p[0] += r[i];
+        p[nch] = std::fma(r[i], r[i], p[nch]);
+        p[2 * nch] += u[i];
+    });
     if (rc) return rc;
-    double a = 0, b = 0, su = 0;
-    for (size_t k = 0; k < nch; k++) { a += part[k]; b += part[nch + k]; su += part[2 * nch + k]; }
-    *sr = a;
-    *sr2 = b;
-    const double mean = su / (double)n_glob;
-    std::vector<double> p2(2 * nch, 0.0);
-    for (int i = 0; i < n; i++) {
-        const size_t ch = c0 + (size_t)i / 256;
+    *sr = s[0];
+    *sr2 = s[1];
+    const double mean = s[2] / (double)n_glob;
+    rc = chunk_sums(q, [&](int i, double *p, size_t nch) {
         const double d = mean - u[i];
-        p2[ch] = std::fma(d, d, p2[ch]);
-        p2[nch + ch] += d;
-    }
-    rc = allreduce_chunks(p2.data(), p2.size());
+        p[0] = std::fma(d, d, p[0]);
+        p[nch] += d;
+    });
     if (rc) return rc;
-    double a2 = 0, a3 = 0;
-    for (size_t k = 0; k < nch; k++) { a2 += p2[k]; a3 += p2[nch + k]; }
-    *varu = n_glob > 1 ? (a2 - a3 * a3 / (double)n_glob) / (double)(n_glob - 1) : 0.0; // arma::var, two-pass, N - 1
+    *varu = var_glob(q[0], q[1]);
     return HB_OK;
 }
 
@@ -266,6 +285,27 @@ int hb_run::setup(const hb_bayes_args *args)
 {
     const auto t0 = clk::now();
     a = *args;
+    // the environment's switches, each read here and nowhere else
+    if (const char *e = getenv("HB_RECOVER")) recover_on = atoi(e) != 0;
+    if (const char *e = getenv("HB_WIDE_LV")) wide_lv = atoi(e) == 3 ? 3 : 2;
+    no_adaptive_r = getenv("HB_NO_ADAPTIVE_R") != nullptr;
+    no_auto_bits = getenv("HB_NO_AUTO_BITS") != nullptr;
+    int rc = take_args();
+    if (!rc) rc = encode_random_effects();
+    if (!rc) rc = take_model_args();
+    if (!rc) rc = configure_device();
+    if (!rc) rc = prior_defaults();
+    if (rc) return rc;
+    console();
+    rc = start_chain();
+    if (rc) return rc;
+    setup_seconds = std::chrono::duration<double>(clk::now() - t0).count();
+    return HB_OK;
+}
+
+// the arguments' validation and deep copies, first half
+int hb_run::take_args()
+{
     n = a.n;
     m = a.m;
     if (n < 2 || m < 1 || !a.y) return hb_fail(HB_ERR_INVALID, "Number of individuals not equals.");
@@ -322,9 +362,9 @@ int hb_run::setup(const hb_bayes_args *args)
         if ((a.C && a.nc) || (a.R && a.nr)) return hb_fail(HB_ERR_UNSUPPORTED, "shard_rows: covariates and random effects are not part of the cross-check mode");
         if (a.genotype_bits == 2) return hb_fail(HB_ERR_UNSUPPORTED, "shard_rows runs on the int8 layout");
     }
+    if (a.genotype_bits != 0 && a.genotype_bits != 8 && a.genotype_bits != 2)
+        return hb_fail(HB_ERR_INVALID, "hb_bayes_run: genotype_bits must be 0 (auto), 8 or 2");
     sync_blocks = std::max(1, std::min(64, (int)a.sync_blocks));
-    if (const char *e = getenv("HB_RECOVER")) recover_on = atoi(e) != 0;
-    const int wide_lv = (getenv("HB_WIDE_LV") && atoi(getenv("HB_WIDE_LV")) == 3) ? 3 : 2; // look-ahead groups of the point-mass models' wide geometry
     m_global = (!rowmode && (world > 1 || a.m_global > 0)) ? a.m_global : m;
     if (!rowmode && world > 1 && ((!a.allreduce && !a.comm) || m_global < m))
         return hb_fail(HB_ERR_INVALID, "hb_bayes_run: sharded run needs a communicator (comm or allreduce) and m_global");
@@ -332,7 +372,6 @@ int hb_run::setup(const hb_bayes_args *args)
 
     // ---- sizes, :119-124 ----
     vary = var_n1(y.data(), n); // (row-sharded mode: replaced by the variance over all shards once the exchange is up)
-    const double h2 = 0.5;
     niter = a.niter;
     nburn = a.nburn;
     thin = a.thin;
@@ -355,7 +394,11 @@ int hb_run::setup(const hb_bayes_args *args)
             cpc[i] = s;
         }
     }
+    return HB_OK;
+}
 
+int hb_run::encode_random_effects()
+{
     // ---- environmental random effects, :149-201 with makeZ :29-57 ----
     nr = a.R ? a.nr : 0;
     dfr = a.has_dfvr ? a.dfvr : -1;
@@ -393,7 +436,12 @@ int hb_run::setup(const hb_bayes_args *args)
     a.R = nullptr; // consumed
     estR.assign(n_levels, 0.0);
     estR_sum.assign(n_levels, 0.0);
+    return HB_OK;
+}
 
+// validation and copies, second half: what depends on the model
+int hb_run::take_model_args()
+{
     // ---- :288-296 ----
     always_in = (model_index == 1 || model_index == 2 || model_index == 5);
     if (always_in) {
@@ -461,8 +509,13 @@ int hb_run::setup(const hb_bayes_args *args)
         warm_.vargL = nullptr;
         a.warm = nullptr; // consumed
     }
+    return HB_OK;
+}
 
-    // =========================== device set-up ===========================
+// the context, its geometry, the exchange, the marker statistics, the resident layout, the Gram blocks and the regime: every decision is
+// hb_runplan.hpp's, asked as soon as its facts are known and applied here
+int hb_run::configure_device()
+{
     int rc;
     if (a.ctx) {
         c = a.ctx;
@@ -476,27 +529,15 @@ int hb_run::setup(const hb_bayes_args *args)
         cp.device = a.device;
         cp.n = n;
         cp.m = m;
-        cp.panel = a.panel;
-        // every marker moves: panels of 512 run k_chain_dense (hb_chain_dense.hpp: static order, the band folded by other compute
-        // units); small problems keep small panels, whose Gram rows are all LDS-resident in k_chain_persist
-        if (!cp.panel && always_in) cp.panel = m >= 4096 ? 512 : (m >= 128 ? 128 : 64);
+        cp.panel = plan_panel(m, always_in, a.panel);
         cp.precise = a.precise;
         cp.m_offset = sharded ? a.m_offset : 0;
         cp.seed = a.seed;
         rc = hb_ctx_create(&cp, &c);
         if (rc) return rc;
         own_ctx = true;
-        // few markers move per sweep in the point-mass models: long look-ahead, big mat-vec launches; where many or
-        // all markers move the forward corrections dominate: one panel per launch, two groups of look-ahead (with one, the
-        // chain idles for an update + launch boundary per panel)
-        if (rowmode) rc = hb_ctx_set_pipeline(c, 0, 0, 1); // per-panel kernels: an exchange sits between each mat-vec and its chain
-        else if (model_index == 3 || model_index == 4) // (2, 7): seven panels per launch, two groups of look-ahead. (Round 5 ran three on the 2-bit layout — 2 % faster then; with
-            rc = hb_ctx_set_pipeline(c, 1, wide_lv, 7);   // round 6's chain it is 2.4 % SLOWER, 445-449 against 456-462 sweeps/s, and its band is 28 blocks instead of 21: HB_WIDE_LV=3 brings it back)
-        else if (always_in && c->P == 512) // k_chain_dense: two panels per launch (45.6 against 39.4 sweeps/s at n=50k, m=500k; (1, 1) 24.8, (1, 2) 27.7)
-            rc = hb_ctx_set_pipeline(c, 1, 2, 2);
-        else if (model_index == 6 && n_fold <= 4 && c->P == 512 && !getenv("HB_NO_ADAPTIVE_R")) // BayesR: (2, 2) stored, (2, 1) while many markers move (geometry by regime, below)
-            rc = hb_ctx_set_pipeline(c, 1, 2, 2);
-        else rc = hb_ctx_set_pipeline(c, 1, 2, 1); // (BayesR with more classes; RR / A / L on small panels: the second group of look-ahead hides the update + launch boundary)
+        const hb_geometry ask = plan_default_geometry(model_index, n_fold, c->P, rowmode, wide_lv, no_adaptive_r);
+        rc = hb_ctx_set_pipeline(c, ask.pipeline, ask.Lv, ask.D);
         if (rc) return rc;
         if (a.X_i8) rc = hb_ctx_upload_genotype_i8(c, a.X_i8, a.ld_i8, 0, m);
         else rc = hb_ctx_upload_genotype_f64(c, a.X_f64, a.ld_f64, 0, m);
@@ -506,6 +547,50 @@ int hb_run::setup(const hb_bayes_args *args)
     a.X_f64 = nullptr;
     HB_HIP(hipSetDevice(c->device));
 
+    rc = open_exchange();
+    if (!rc) rc = marker_statistics();
+    if (rc) return rc;
+    // resident layout
+    auto layout = [&](size_t free_bytes) {
+        return plan_layout(a.genotype_bits, own_ctx, rowmode, a.precise, model_index, n_fold, c->P, c->pipeline, c->xmin, c->xmax, no_auto_bits,
+                           free_bytes, c->m_pad, c->ld, wide_lv);
+    };
+    int bits_run = layout(SIZE_MAX); // a probe with all the memory there could be: the device is asked only where its answer decides
+    if (bits_run == 2 && a.genotype_bits == 0) {
+        size_t fr = 0, tot = 0;
+        if (hipMemGetInfo(&fr, &tot) != hipSuccess) fr = 0;
+        bits_run = layout(fr);
+        if (bits_run != 2) (void)hipGetLastError(); // (a failed query must not stay behind as the thread's last error)
+    }
+    if (!c->gram_ready) {
+        rc = hb_ctx_build_gram(c, &gram_seconds);
+        if (rc) return rc;
+    }
+    if (bits_run == 2) { // the Gram blocks (built from the int8 columns) are in place: pack, drop the int8 copy
+        rc = hb_ctx_set_layout(c, 2, 0);
+        if (rc) return rc;
+    }
+    if (!own_ctx && c->adaptive && c->pipeline && c->home_d > 0 && (c->home_lv != c->Lv || c->home_d != c->D) && !rowmode) {
+        // an adaptive context that an earlier run left in its narrow geometry: start from the geometry its owner set (round 6: a second fit
+        // on the same context used to stay narrow for good, because only the wide geometry switches adaptivity on)
+        rc = hb_ctx_switch_geometry(c, 1, c->home_lv, c->home_d);
+        if (rc) return rc;
+    }
+    regime = plan_regime(model_index, n_fold, c->P, own_ctx, c->adaptive, hb_geometry{c->pipeline, c->Lv, c->D, c->L, c->NB}, c->Lg, no_adaptive_r);
+    geo_cur = 0;
+    if (regime.on) { // the first sweep: as many moves as markers are expected in the model (a cold start) or are in it
+        double nz = 0;
+        for (double gv : g_init) nz += gv != 0.0;
+        if (g_init.empty()) nz = (1.0 - Pi[0]) * (double)m;
+        last_events_pp = nz / std::max(1, c->npanels);
+    }
+    return HB_OK;
+}
+
+// the exchange buffers; row-sharded mode: its hook into the context, the per-panel kernels and var(y) over all shards
+int hb_run::open_exchange()
+{
+    int rc;
     // (row-sharded mode: the shards hold different numbers of individuals, the message must not depend on n)
     xcount = rowmode ? hb_exchange_count(4096) : hb_exchange_count(n);
     if (sharded || rowmode) {
@@ -527,32 +612,27 @@ int hb_run::setup(const hb_bayes_args *args)
             rc = hb_ctx_set_pipeline(c, 0, 0, 1);
             if (rc) return rc;
         }
-        // var(y) over all shards, two-pass (arma::var), in the shard-count-independent order of row_sums(): partial sums of
-        // fixed 256-row chunks, gathered, added in chunk order
-        const size_t nch = (size_t)((n_glob + 255) / 256), c0 = (size_t)(row_off / 256);
-        std::vector<double> p1(nch, 0.0);
-        for (int i = 0; i < n; i++) p1[c0 + (size_t)i / 256] += y[i];
-        rc = allreduce_chunks(p1.data(), p1.size());
+        // var(y) over all shards, two-pass (arma::var), in the shard-count-independent order of chunk_sums()
+        double tot[1], q[2];
+        rc = chunk_sums(tot, [&](int i, double *p, size_t) { p[0] += y[i]; });
         if (rc) return rc;
-        double tot = 0;
-        for (double v : p1) tot += v;
-        ymean_glob = tot / (double)n_glob;
-        std::vector<double> p2(2 * nch, 0.0);
-        for (int i = 0; i < n; i++) {
-            const size_t ch = c0 + (size_t)i / 256;
+        ymean_glob = tot[0] / (double)n_glob;
+        rc = chunk_sums(q, [&](int i, double *p, size_t nch) {
             const double t = ymean_glob - y[i];
-            p2[ch] += t * t;
-            p2[nch + ch] += t;
-        }
-        rc = allreduce_chunks(p2.data(), p2.size());
+            p[0] += t * t;
+            p[nch] += t;
+        });
         if (rc) return rc;
-        double a2 = 0, a3 = 0;
-        for (size_t k = 0; k < nch; k++) { a2 += p2[k]; a3 += p2[nch + k]; }
-        vary = n_glob > 1 ? (a2 - a3 * a3 / (double)n_glob) / (double)(n_glob - 1) : 0.0;
+        vary = var_glob(q[0], q[1]);
     }
+    return HB_OK;
+}
 
-    // ---- marker statistics, :310-317 ----
-    std::vector<double> vx_host(g_init.empty() ? 0 : m);
+// marker statistics, :310-317, and what the ranks agree on about replaying a sweep
+int hb_run::marker_statistics()
+{
+    int rc;
+    vx_host.assign(g_init.empty() ? 0 : m, 0.0);
     if (rowmode) {
         rc = row_stats_and_gram();
         if (rc) return rc;
@@ -581,80 +661,12 @@ int hb_run::setup(const hb_bayes_args *args)
         }
         pipeline_setup = c->pipeline ? 1 : 0;
     }
-    // ---- resident layout (round 6): genotype_bits = 0 is "auto" — 2 bits per genotype where that is exact AND the faster sweep: codes
-    // 0..3 (PLINK's own alphabet, src/read_bed.cpp:116-120), the fixed-point mat-vec, and the point-mass models' wide launches
-    // (BayesB / BayesC at panel 512: 450 against 213 sweeps/s at n = 50k, m = 500k; the same chain bit for bit). The models whose
-    // launches cover one or two panels are bound by their chain workgroup and run the lighter int8 kernel beside it. 8 forces int8. ----
-    int bits_run = a.genotype_bits == 2 ? 2 : 8;
-    const bool sparse_bc = model_index == 3 || model_index == 4, mix_r = model_index == 6 && n_fold <= 4;
-    if (a.genotype_bits == 0 && own_ctx && !rowmode && a.precise == 2 && (sparse_bc || mix_r) && c->P == 512 &&
-        c->pipeline && c->xmin >= 0 && c->xmax <= 3 && !getenv("HB_NO_AUTO_BITS")) {
-        // (BayesR, measured late in round 6 with k_dotq2m beside both of its chains: 64.5 against 57.8 sweeps/s 300 sweeps after a cold start, 102.8 against 98.3
-        // converged — a quarter of the genotype bytes streaming past the chain workgroup's own round trips; round 4's "the 2-bit kernel only lengthens the
-        // launches" was the v_dot4 kernel)
-        // the band of the geometry — (2, 7): 21 blocks ((3, 7): 28), BayesR's (2, 2): 6 — and the packed genotypes must fit beside the int8 columns the band is built from
-        size_t fr = 0, tot = 0;
-        const size_t band = (size_t)(sparse_bc ? 7 * (wide_lv + 1) : 6) * c->m_pad * c->P * sizeof(int32_t), x2 = (size_t)((c->ld + 511) / 512 * 128) * c->m_pad;
-        if (hipMemGetInfo(&fr, &tot) == hipSuccess && fr > band + x2 + ((size_t)2 << 30)) bits_run = 2;
-        else (void)hipGetLastError();
-    }
-    if (bits_run == 2 && own_ctx && a.genotype_bits == 0 && sparse_bc && wide_lv != 2) {
-        rc = hb_ctx_set_pipeline(c, 1, wide_lv, 7); // (HB_WIDE_LV=3: round 5's third group of look-ahead on the 2-bit layout)
-        if (rc) return rc;
-    }
-    if (!c->gram_ready) {
-        rc = hb_ctx_build_gram(c, &gram_seconds);
-        if (rc) return rc;
-    }
-    if (a.genotype_bits != 0 && a.genotype_bits != 8 && a.genotype_bits != 2)
-        return hb_fail(HB_ERR_INVALID, "hb_bayes_run: genotype_bits must be 0 (auto), 8 or 2");
-    if (bits_run == 2 && own_ctx) { // the Gram blocks (built from the int8 columns) are in place: pack, drop the int8 copy
-        rc = hb_ctx_set_layout(c, 2, 0);
-        if (rc) return rc;
-    }
-    if (!own_ctx && c->adaptive && c->pipeline && c->home_d > 0 && (c->home_lv != c->Lv || c->home_d != c->D) && !rowmode) {
-        // an adaptive context that an earlier run left in its narrow geometry: start from the geometry its owner set (round 6: a second fit
-        // on the same context used to stay narrow for good, because only the wide geometry switches adaptivity on)
-        rc = hb_ctx_switch_geometry(c, 1, c->home_lv, c->home_d);
-        if (rc) return rc;
-    }
-    {   // geometry by regime: only from the wide-band geometry of the point-mass models, whose stored band serves the narrow one
-        int32_t gp = 0, gl = 0, gd = 0, gb = 0;
-        (void)hb_ctx_get_pipeline(c, &gp, &gl, &gd, &gb);
-        adaptive_geo = (model_index == 3 || model_index == 4) && (own_ctx || c->adaptive) && gp == 1 && (((gl == 2 || gl == 3) && gd == 7) || (gl == 2 && gd == 8)) && c->Lg >= 20;
-        geo_wide_lv = gl;
-        if (adaptive_geo) geo_wide_d = gd;
-        geo_cur = 0;
-        // round 6, re-measured at n = 50k, m = 500k from a cold start with this round's chains (profiles/r06_regime_bayescpi*.txt; round 3's 2.0 / 2.6 were taken when
-        // the wide geometry ran 166 sweeps/s): 2-bit genotypes — at 3.6 moves a panel (2, 2) 148 against (2, 7) 141 sweeps/s, at 2.6: 173 against 189, at 2.1: 187
-        // against 233; int8 columns — at 5.8: 97 against 80, at 3.6: 124 against 131, at 2.6: 131 against 168
-        // One pair of thresholds for both layouts (the geometries cross at 3.2 moves a panel on 2-bit genotypes, at 4.2 on int8 columns): a run on 2-bit genotypes
-        // is the int8 run BIT FOR BIT only if both take the same geometry in every sweep (tests/test_gpu_depth.py test_two_bit_resident_layout_is_the_same_chain;
-        // per-layout thresholds broke exactly that), and between 3.2 and 4.2 the int8 run loses 5 % for a handful of sweeps.
-        if (model_index == 3 || model_index == 4) {
-            geo_to_wide = 3.2;
-            geo_to_narrow = 4.0;
-        }
-        // round 6, BayesR with up to four classes at panel 512: two panels per launch and the certified group chain (k_chain_group<3, 2, 2, 15> + k_fwd + warmers)
-        // once fewer than ~22 markers a panel move, one panel per launch and the per-panel chain with its row cache (k_chain_persist) above ~27
-        // (measured at n = 50k, m = 500k from a cold start, profiles/r06_bayesr_regime.txt: they cross at 19 moves per panel — 47.5 sweeps/s both;
-        // at 51: 37 against 54; at 11: 68 against 60; at 8: 85 against 69)
-        if (model_index == 6 && n_fold <= 4 && c->P == 512 && (own_ctx || c->adaptive) && gp == 1 && gl == 2 && gd == 2 && c->Lg >= 5 && !getenv("HB_NO_ADAPTIVE_R")) {
-            adaptive_geo = true;
-            geo_wide_d = 2;
-            geo_narrow_lv = 2;
-            geo_narrow_d = 1;
-            geo_to_wide = 22.0;   // (re-measured with k_fwd and the warmers beside the group chain, profiles/r06_bayesr_regime2.txt: at 19.6 moves a panel 51.4 against 49.6
-            geo_to_narrow = 27.0; //  sweeps/s, at 11: 78 against 63; at 47: 39 against 54 — no measurement in between)
-        }
-        if (adaptive_geo) { // the first sweep: as many moves as markers are expected in the model (a cold start) or are in it
-            double nz = 0;
-            for (double gv : g_init) nz += gv != 0.0;
-            if (g_init.empty()) nz = (1.0 - Pi[0]) * (double)m;
-            last_events_pp = nz / std::max(1, c->npanels);
-        }
-    }
+    return HB_OK;
+}
 
+int hb_run::prior_defaults()
+{
+    int rc;
     // ---- prior defaults, :327-374 ----
     vara_ = a.has_vg ? a.vg : ((dfvara_ - 2) / dfvara_) * vary * h2;
     vare_ = a.has_ve ? a.ve : vary * (1 - h2) / (nr + 1);
@@ -684,11 +696,10 @@ int hb_run::setup(const hb_bayes_args *args)
         for (int i = 0; i < m; i++) nw = std::max(nw, (int)wind[i]);
         if (world > 1) { // window ids are global: every rank needs the same nw (max over ranks)
             if ((size_t)world > xcount) return hb_fail(HB_ERR_INVALID, "too many ranks for the exchange buffer");
-            std::vector<double> slots(world, 0.0);
-            slots[a.rank] = nw;
-            rc = allreduce_host(slots.data(), world);
+            double nwmax = nw;
+            rc = allreduce_max(&nwmax);
             if (rc) return rc;
-            for (double s : slots) nw = std::max(nw, (int)s);
+            nw = (int)nwmax;
         }
         rc = hb_ctx_set_windows(c, wind.data(), nw);
         if (rc) return rc;
@@ -702,7 +713,11 @@ int hb_run::setup(const hb_bayes_args *args)
     if (rc) return rc;
     rc = hb_ctx_blocks_setup(c, cpc.data(), zz.data(), vrtmp.data());
     if (rc) return rc;
+    return HB_OK;
+}
 
+void hb_run::console() const
+{
     // ---- console, :393-461 ----
     line("Prior parameters:");
     line("    Model fitted at [%s]", model == "BayesRR" ? "Bayes Ridge Regression" : model.c_str());
@@ -726,7 +741,12 @@ int hb_run::setup(const hb_bayes_args *args)
              "respect to each other inside a sweep, variance components are biased (DESIGN.md section 8)", world, model.c_str());
     line("MCMC started: ");
     line(" Iter  NumNZSnp  pi  %sVg  Ve  h2  Timeleft", model == "BayesL" ? "Lambda  " : "");
+}
 
+// the chain's first state: a continued chain's scalars, the intercept, the residual and its sums, the sample stores
+int hb_run::start_chain()
+{
+    int rc;
     // ---- warm state: the scalars of a chain that is continued (the constants above stay the cold run's) ----
     if (has_warm) {
         vare_ = warm_.vare;
@@ -753,6 +773,7 @@ int hb_run::setup(const hb_bayes_args *args)
                 if (vx_host[i] == 0.0) g_init[i] = 0.0;
                 trk[i] = g_init[i] != 0.0;
             }
+            std::vector<double>().swap(vx_host); // (needed no longer: not kept for the length of the run)
             rc = hb_ctx_set_effects(c, g_init.data(), trk.data(), nullptr);
             if (rc) return rc;
             rc = hb_ctx_matvec(c, g_init.data(), zero.data()); // u = X g
@@ -783,7 +804,6 @@ int hb_run::setup(const hb_bayes_args *args)
     s_Vr.assign((size_t)n_records * nr, 0.0);
     s_r.assign((size_t)n_records * n_levels, 0.0);
     if (a.store_alpha) s_alpha.assign((size_t)n_records * m, 0.0);
-    setup_seconds = std::chrono::duration<double>(clk::now() - t0).count();
     return HB_OK;
 }
 
@@ -842,17 +862,11 @@ int hb_run::step()
     in.count_pip = (iter >= nburn) && !always_in;
     in.store = (iter >= nburn) && ((iter + 1 - nburn) % thin == 0);
     hb_sweep_out so{};
-    // geometry by regime (point-mass models, when the context is ours or its owner asked for it): while many markers move
-    // every move costs one band row per block of the band, so a narrow band wins; once few move, the wide band with its
-    // big mat-vec launches does (measured at n=50k, m=500k: (2,2) 114 vs (2,7) 92 sweeps/s at 3.5 moves per panel,
-    // 136 vs 166 at 1.4). The stored band serves both; each geometry's captured sweep is cached.
-    if (adaptive_geo) {
-        const double pp = last_events_pp; // moves per panel of the previous sweep on this shard
-        int want = geo_cur;
-        if (geo_cur == 1 && pp < geo_to_wide) want = 0;         // -> (2 | 3, 7); BayesR: (2, 2)
-        else if (geo_cur == 0 && pp > geo_to_narrow) want = 1;  // -> (2, 2); BayesR: (2, 1)
+    // geometry by regime (hb_runplan.hpp), when the context is ours or its owner asked for it
+    if (regime.on) {
+        const int want = regime_next(regime, geo_cur, last_events_pp); // (moves per panel of the previous sweep on this shard)
         if (want != geo_cur) {
-            rc = hb_ctx_switch_geometry(c, 1, want == 0 ? geo_wide_lv : geo_narrow_lv, want == 0 ? geo_wide_d : geo_narrow_d);
+            rc = hb_ctx_switch_geometry(c, 1, regime.Lv[want], regime.D[want]);
             if (rc) return rc;
             geo_cur = want;
         }
@@ -1162,10 +1176,8 @@ int hb_run::finish(hb_bayes_out *o)
         rc = hb_ctx_get_windows(c, w.data());
         if (rc) return rc;
         if (sharded) { // (chunked: the exchange buffer holds n + 16 values)
-            for (int k0 = 0; k0 < nw; k0 += (int)xcount) {
-                rc = allreduce_host(w.data() + k0, std::min((int)xcount, nw - k0));
-                if (rc) return rc;
-            }
+            rc = allreduce_chunks(w.data(), w.size());
+            if (rc) return rc;
         }
         for (int k = 0; k < nw; k++) {
             double p = w[k] / nzct;

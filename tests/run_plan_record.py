@@ -1,0 +1,17 @@
+"""tests/golden/run_plan_table.json, the recorded decisions of hb_runplan.hpp, for the tests that read it (test_host_logic.py, test_gpu_runplan.py)."""
+import os
+
+
+def recorded_run_plan():
+    """tests/golden/run_plan_table.json as {stage: {key: outcome}}, the keys in the order of the stage's dims (the first varies slowest)."""
+    import itertools
+    import json
+    table = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "run_plan_table.json")))
+    out = {}
+    for stage, rec in table.items():
+        if stage != "about":
+            keys = [" ".join(str(x) for x in t) for t in itertools.product(*[v for _, v in rec["dims"]])]
+            vals = [rec["outcomes"][i] for i, cnt in zip(rec["runs"][0::2], rec["runs"][1::2]) for _ in range(cnt)]
+            assert len(keys) == len(vals), stage
+            out[stage] = dict(zip(keys, vals))
+    return out

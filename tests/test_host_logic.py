@@ -396,3 +396,147 @@ def test_every_sweep_plan_equals_the_recorded_dispatch_and_names_a_built_kernel(
             named.update(x for x in v.split()[:2] if x != "-")
     assert named <= listed, "plans name kernels that are in no launch table: %s" % sorted(named - listed)
     assert listed <= named, "listed kernels that no input of the domain runs: %s" % sorted(listed - named)
+
+
+_RUNPLAN_PROGRAM = r"""
+#include "hb_runplan.hpp"
+#include <cmath>
+#include <cstdio>
+static const int MODEL_NF[12][2] = {{1, 2}, {2, 2}, {3, 2}, {4, 2}, {5, 2}, {6, 2}, {6, 3}, {6, 4}, {6, 5}, {6, 6}, {6, 7}, {6, 8}};
+static const int ON_REGIMES[4][4] = {{3, 2, 2, 7}, {4, 2, 3, 7}, {3, 2, 2, 8}, {6, 4, 2, 2}}; // model, n_fold, Lv, D
+static hb_regime on_regime(const int o[4]) { return plan_regime(o[0], o[1], 512, true, false, hb_geometry{1, o[2], o[3], 0, 0}, 27, false); }
+
+// not in the record: every default geometry of an own context is one plan_sweep has kernels for, and the hysteresis holds between its thresholds
+static void cross_properties()
+{
+    for (auto &mn : MODEL_NF) for (int P : {64, 128, 256, 512}) for (int row = 0; row < 2; row++) for (int wlv = 2; wlv <= 3; wlv++)
+    for (int noad = 0; noad < 2; noad++) for (int conc = 0; conc < 2; conc++) for (int cert = 0; cert < 2; cert++) for (int lg = 0; lg < 2; lg++) {
+        const hb_geometry a = plan_default_geometry(mn[0], mn[1], P, row, wlv, noad), g = plan_geometry(conc, a.pipeline, P, a.Lv, a.D);
+        printf("sweep %d %d %d %d %d %d %d %d %d | %d\n", mn[0], mn[1], P, row, wlv, noad, conc, cert, lg,
+               (int)plan_sweep(hb_sweep_shape{mn[0], mn[1], P, g.Lv, g.D, g.L, cert != 0, false, false, lg != 0, true}).ok);
+    }
+    for (auto &o : ON_REGIMES) {
+        const hb_regime r = on_regime(o);
+        for (int cur = 0; cur < 2; cur++) for (int k = 0; k <= 1000; k++) {
+            const double pp = r.to_wide + (r.to_narrow - r.to_wide) * k / 1000.0;
+            if (regime_next(r, cur, pp) != cur) printf("moved %d %d %d %d %d %.17g | 1\n", o[0], o[1], o[2], o[3], cur, pp);
+        }
+        printf("held %d %d %d %d | %d\n", o[0], o[1], o[2], o[3], (int)r.on);
+    }
+}
+
+int main()
+{
+    for (int m : {100, 128, 255, 256, 300, 1023, 1024, 4095, 4096, 4608, 500000}) for (int moves = 0; moves < 2; moves++) for (int asked : {0, 64, 128, 256, 512})
+        printf("panel %d %d %d | %d\n", m, moves, asked, plan_panel(m, moves, asked));
+    for (int conc = 0; conc < 2; conc++) for (int pl = 0; pl < 2; pl++) for (int P : {64, 128, 256, 512})
+    for (int Lv : {-1, 0, 1, 2, 3, 4, 5, 6, 9}) for (int D : {0, 1, 2, 3, 4, 5, 6, 7, 8, 12}) {
+        const hb_geometry g = plan_geometry(conc, pl, P, Lv, D);
+        printf("geometry %d %d %d %d %d | %d %d %d %d %d\n", conc, pl, P, Lv, D, g.pipeline, g.Lv, g.D, g.L, g.NB);
+    }
+    // the geometry of a context of the run's own: what it asks for, and what the context makes of it
+    for (auto &mn : MODEL_NF) for (int P : {64, 128, 256, 512}) for (int row = 0; row < 2; row++) for (int wlv = 2; wlv <= 3; wlv++)
+    for (int noad = 0; noad < 2; noad++) for (int conc = 0; conc < 2; conc++) {
+        const hb_geometry a = plan_default_geometry(mn[0], mn[1], P, row, wlv, noad), g = plan_geometry(conc, a.pipeline, P, a.Lv, a.D);
+        printf("default %d %d %d %d %d %d %d | %d %d %d -> %d %d %d %d %d\n", mn[0], mn[1], P, row, wlv, noad, conc, a.pipeline, a.Lv, a.D, g.pipeline, g.Lv, g.D, g.L, g.NB);
+    }
+    static const int CODES[3][2] = {{0, 3}, {-1, 2}, {0, 4}};
+    static const long long SIZES[2][2] = {{4608, 512}, {500224, 50176}}; // m_pad, ld
+    for (int bits : {0, 2, 8}) for (int own = 0; own < 2; own++) for (int row = 0; row < 2; row++) for (int precise = 1; precise <= 2; precise++)
+    for (int noauto = 0; noauto < 2; noauto++) for (int pl = 0; pl < 2; pl++) for (auto &cd : CODES) for (int mem = 0; mem < 4; mem++)
+    for (int P : {64, 128, 256, 512}) for (auto &mn : MODEL_NF) for (int wlv = 2; wlv <= 3; wlv++) for (auto &sz : SIZES) {
+        // memory above band + packed + 2 GiB: the band is 7 * (wide_lv + 1) blocks for BayesB / C, 6 for BayesR
+        const unsigned long long blocks = (mn[0] == 3 || mn[0] == 4) ? 7 * (wlv + 1) : 6;
+        const unsigned long long bound = blocks * sz[0] * P * 4 + (unsigned long long)((sz[1] + 511) / 512 * 128) * sz[0] + (2ull << 30);
+        const unsigned long long fr = mem == 0 ? 0 : mem == 1 ? bound : mem == 2 ? bound + 1 : (200ull << 30);
+        printf("layout %d %d %d %d %d %d %d %d %d %d %d %d %d %lld | %d\n", bits, own, row, precise, noauto, pl, cd[0], cd[1], mem, P, mn[0], mn[1], wlv, sz[0],
+               plan_layout(bits, own, row, precise, mn[0], mn[1], P, pl, cd[0], cd[1], noauto, (size_t)fr, (int)sz[0], (int64_t)sz[1], wlv));
+    }
+    for (auto &mn : MODEL_NF) for (int P : {64, 128, 256, 512}) for (int own = 0; own < 2; own++) for (int adp = 0; adp < 2; adp++)
+    for (int noad = 0; noad < 2; noad++) for (int Lg : {0, 2, 4, 5, 19, 20, 27}) for (int pl = 0; pl < 2; pl++) for (int Lv = 0; Lv <= 6; Lv++) for (int D = 1; D <= 8; D++) {
+        const hb_regime r = plan_regime(mn[0], mn[1], P, own, adp, hb_geometry{pl, Lv, D, 0, 0}, Lg, noad);
+        printf("regime %d %d %d %d %d %d %d %d %d %d | ", mn[0], mn[1], P, own, adp, noad, Lg, pl, Lv, D);
+        if (!r.on) { puts("off"); continue; }
+        printf("wide %d %d narrow %d %d thresholds %.17g %.17g\n", r.Lv[0], r.D[0], r.Lv[1], r.D[1], r.to_wide, r.to_narrow);
+    }
+    // the hysteresis of each regime, at, beside and between its thresholds
+    for (auto &o : ON_REGIMES) {
+        const hb_regime r = on_regime(o);
+        if (!r.on) continue;
+        for (int cur = 0; cur < 2; cur++)
+            for (int k = 0; k < 9; k++) { // moves per panel: 0, then below, at and above to_wide, half way, below, at and above to_narrow, then 1e6
+                const double pp[9] = {0.0, std::nextafter(r.to_wide, 0.0), r.to_wide, std::nextafter(r.to_wide, 1e9), 0.5 * (r.to_wide + r.to_narrow),
+                                      std::nextafter(r.to_narrow, 0.0), r.to_narrow, std::nextafter(r.to_narrow, 1e9), 1e6};
+                printf("next %d %d %d %d %d %d | %d\n", o[0], o[1], o[2], o[3], cur, k, regime_next(r, cur, pp[k]));
+            }
+    }
+    cross_properties();
+}
+"""
+
+
+def test_every_run_plan_equals_the_recorded_decisions(tmp_path):
+    """hb_runplan.hpp (plain C++, compiled here with g++) decides the configuration a run gives plan_sweep: the panel, the geometry a context
+    normalises a request to, the geometry a run asks for on a context of its own, the resident layout, and whether and between which geometries
+    the run follows the regime. Every stage over its domain against tests/golden/run_plan_table.json, which was recorded from the decision lines
+    as they stood inside hb_run::setup, hb_run::step, hb_ctx_create and hb_pipeline_geometry before they became these functions. A few rows are
+    asserted literally as well, read off that code: they guard the recording itself. Two properties across the stages: every default geometry,
+    as a context normalises it, is one plan_sweep has kernels for, and the hysteresis changes nothing between its two thresholds."""
+    import subprocess
+    from run_plan_record import recorded_run_plan
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    src, exe = tmp_path / "runplan.cpp", tmp_path / "runplan"
+    src.write_text(_RUNPLAN_PROGRAM)
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(root, "hibayes_amd", "csrc"), str(src), "-o", str(exe)])
+    got = {}
+    for line in subprocess.check_output([str(exe)]).decode().splitlines():
+        k, v = line.split(" | ")
+        stage, key = k.split(" ", 1)
+        got.setdefault(stage, {})[key] = v
+    want = recorded_run_plan()
+    assert {k: len(v) for k, v in want.items()} == {"panel": 110, "geometry": 1440, "default": 768, "layout": 221184, "regime": 301056, "next": 72}
+    assert set(got) == set(want) | {"sweep", "held"}, "stages: %s" % sorted(got)  # (a "moved" row is a hysteresis that moved between its thresholds)
+    for stage, rows in want.items():
+        assert list(got[stage]) == list(rows), "the domains differ: %s" % stage
+        wrong = ["%s: %s, recorded %s" % (k, got[stage][k], w) for k, w in rows.items() if got[stage][k] != w]
+        assert not wrong, "%d rows of '%s' differ from the record, the first:\n%s" % (len(wrong), stage, "\n".join(wrong[:20]))
+    assert len(got["sweep"]) == 3072 and set(got["sweep"].values()) == {"1"}, [k for k, v in got["sweep"].items() if v != "1"][:20]
+    assert got["held"] == {"3 2 2 7": "1", "4 2 3 7": "1", "3 2 2 8": "1", "6 4 2 2": "1"}
+
+    # ---- the literal rows ----
+    def default(model, nf, P, row=0, wlv=2, noad=0, conc=1):  # -> (asked, the context's (pipeline, Lv, D), its band)
+        asked, ctx = got["default"]["%d %d %d %d %d %d %d" % (model, nf, P, row, wlv, noad, conc)].split(" -> ")
+        g = tuple(int(x) for x in ctx.split())
+        return tuple(int(x) for x in asked.split()), g[:3], g[3]
+
+    def regime(model, nf, P, own, adp, noad, Lg, pl, Lv, D):
+        return got["regime"]["%d %d %d %d %d %d %d %d %d %d" % (model, nf, P, own, adp, noad, Lg, pl, Lv, D)]
+
+    for model in (3, 4):  # BayesB / C on a context of the run's own
+        assert default(model, 2, 512) == ((1, 2, 7), (1, 2, 7), 20) and default(model, 2, 512, wlv=3) == ((1, 3, 7), (1, 3, 7), 27)
+        assert default(model, 2, 256, wlv=3)[1] == (1, 2, 7)
+        assert all(default(model, 2, P, conc=0)[1] == (0, 2, 1) for P in (64, 128, 256, 512))  # (with wide_lv = 3: (0, 3, 1))
+    for model in (1, 2, 5):  # BayesRR / A / L
+        for m, P, geo in ((4096, 512, (1, 2, 2)), (500000, 512, (1, 2, 2)), (128, 128, (1, 2, 1)), (255, 128, (1, 2, 1)), (1024, 128, (1, 2, 1)), (4095, 128, (1, 2, 1))):
+            assert int(got["panel"]["%d 1 0" % m]) == P and default(model, 2, P)[1] == geo, (model, m)
+    for nf in (2, 3, 4):  # BayesR with up to four classes at panel 512
+        assert default(6, nf, 512)[1] == (1, 2, 2) and regime(6, nf, 512, 1, 0, 0, 5, 1, 2, 2) == "wide 2 2 narrow 2 1 thresholds 22 27"
+        assert default(6, nf, 512, noad=1)[1] == (1, 2, 1) and {regime(6, nf, 512, 1, 0, 1, 27, 1, 2, D) for D in (1, 2)} == {"off"}
+    assert default(6, 5, 512)[1] == (1, 2, 1) and {regime(6, 5, 512, 1, 1, 0, 27, 1, 2, D) for D in (1, 2)} == {"off"}
+    for model in (3, 4):  # BayesB / C: on only from (2 | 3, 7) or (2, 8) with a stored band of 20 panels or more
+        on = {k: v for k, v in got["regime"].items() if k.startswith("%d 2 " % model) and v != "off"}
+        assert len(on) == 4 * 3 * 2 * 2 * 3 and all(v == "wide %s narrow 2 2 thresholds 3.2000000000000002 4" % k[-3:] for k, v in on.items())
+        for k in on:
+            _, _, _, own, adp, _, Lg, pl, Lv, D = (int(x) for x in k.split())
+            assert (own or adp) and Lg >= 20 and pl == 1 and (Lv, D) in ((2, 7), (3, 7), (2, 8)), k
+    for k, v in got["default"].items():  # row mode
+        if k.split()[3] == "1":
+            assert v == "0 0 1 -> 0 0 1 0 1", k
+    assert {v for k, v in got["layout"].items() if k.startswith("0 1 1 ")} == {"8"}
+    for k, v in got["layout"].items():  # the automatic layout
+        bits, own, row, precise, noauto, pl, xmin, xmax, mem, P, model, nf, _, _ = (int(x) for x in k.split())
+        if bits == 0:
+            assert (v == "2") == (own == 1 and row == 0 and precise == 2 and P == 512 and pl == 1 and noauto == 0 and (xmin, xmax) == (0, 3)
+                                  and mem >= 2 and (model in (3, 4) or (model == 6 and nf <= 4))), k
+        else:
+            assert (v == "2") == (bits == 2 and own == 1), k
