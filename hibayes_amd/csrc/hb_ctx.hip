@@ -161,16 +161,8 @@ int hb_ctx_create(const hb_ctx_params *p, hb_ctx **out)
     if (const char *e = getenv("HB_LOOKAHEAD")) c->Lv = atoi(e);
     if (const char *e = getenv("HB_DOTGROUP")) c->D = atoi(e);
     if (const char *e = getenv("HB_GRAPH")) c->use_graph = atoi(e) != 0;
-    if (const char *e = getenv("HB_DOTQ2_CPL")) c->dotq2_cpl = atoi(e) == 1 ? 1 : 2;
-    if (const char *e = getenv("HB_DOTQ_TILES")) c->dotq_tiles = std::max(1, atoi(e));
-    if (const char *e = getenv("HB_DOTQ2_TILES")) { c->dotq2_tiles = std::max(1, atoi(e)); c->dotq2_tiles_set = true; }
-    if (const char *e = getenv("HB_DOTQ2_KIND")) c->dotq2_kind = std::max(0, std::min(2, atoi(e)));
+    c->mv = matvec_knobs_from_env([](const char *name) -> const char * { return getenv(name); });
     if (const char *e = getenv("HB_CERT")) c->gcert_on = atoi(e) != 0;
-    if (const char *e = getenv("HB_Q2M_CT")) c->q2m_ct = atoi(e) >= 16 ? 16 : atoi(e) >= 8 ? 8 : 4;
-    if (const char *e = getenv("HB_Q2M_G")) c->q2m_g = atoi(e) == 3 ? 3 : atoi(e) >= 2 ? 2 : atoi(e) == 0 ? 0 : 1;
-    if (const char *e = getenv("HB_Q2M_SC")) c->q2m_sc = atoi(e) != 0;
-    if (const char *e = getenv("HB_DOTQ2_NC")) c->dotq2_nc = std::max(4, atoi(e) / 4 * 4);
-    if (const char *e = getenv("HB_DOTQ2_RS")) c->dotq2_rs = atoi(e) == 256 ? 256 : atoi(e) == 128 ? 128 : 512;
     if (getenv("HB_DENSE_UPD")) c->dense_upd = false;
     if (const char *e = getenv("HB_TIMEOUT_MS")) { c->timeout_ms = std::max(1, std::min(60000, atoi(e))); c->timeout_env = true; }
     if (const char *e = getenv("HB_KAPPA")) c->kappa = atof(e);
@@ -945,9 +937,9 @@ int hb_ctx_set_matvec_kernel(hb_ctx *c, int32_t kind)
 {
     if (!c) return hb_fail(HB_ERR_INVALID, "hb_ctx_set_matvec_kernel: null context");
     if (kind < 0 || kind > 2) return hb_fail(HB_ERR_INVALID, "hb_ctx_set_matvec_kernel: kind must be 0 (lane = column, v_dot4), 1 (individuals across the lanes, v_dot4) or 2 (matrix cores)");
-    if (kind != c->dotq2_kind) {
+    if (kind != c->mv.kind) {
         HB_HIP(hipStreamSynchronize(c->stream));
-        c->dotq2_kind = kind;
+        c->mv.kind = kind;
         c->graph_model = -1; // the captured sweeps hold the other kernel
     }
     return HB_OK;

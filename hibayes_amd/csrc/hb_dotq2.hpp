@@ -167,7 +167,6 @@ __global__ __launch_bounds__(64) void k_dotq2(dq_view v, upd_view uq)
     }
     if (v.ldiag) hb_ldiag_note(v.ldiag, t0);
 }
-static constexpr int q2_lds(int cpl, int rs) { return 2 * ((64 * cpl / (4096 / rs)) * HBQ_SLOT + ((HB_ND + 1024 / rs - 1) / (1024 / rs)) * 1024); }
 
 // ---------------------------------------------------------------------------------------------
 // k_dotq2m: the same product on the MATRIX CORES — an A/B kernel, not the default (hb_ctx_set_matvec_kernel(c, 2) /
@@ -193,11 +192,7 @@ static constexpr int q2_lds(int cpl, int rs) { return 2 * ((64 * cpl / (4096 / r
 //   * Cost per stage of 64 columns x 256 individuals: 16 MFMA + 80 mask operations + 8 LDS reads, against 448 v_dot4 + 112
 //     mask operations + 116 LDS reads: the launch becomes HBM-bound.
 // ---------------------------------------------------------------------------------------------
-#define Q2M_RS 256
-#define Q2M_DSTRIDE 1088
-#ifndef Q2M_NBUF
-#define Q2M_NBUF 3 /* stage buffers: NBUF - 1 (super-)stages in flight ahead of the one being multiplied (a stage computes in ~0.3 us, a loaded round trip takes ~2) */
-#endif
+// (Q2M_RS, Q2M_DSTRIDE, Q2M_NBUF and the shapes' LDS, q2_lds / q2m_lds / q2m512_lds: hb_matvecplan.hpp)
 static_assert(Q2M_NBUF >= 2 && Q2M_NBUF <= 6, "the counted waits of dotq2m_tile cover up to five stages in flight");
 // Shape (round 5). CT = column tiles of 16 per wave (4: 64 columns, the round-4 shape; 8: 128; 16: 256) — the stage's digit planes
 // (1.75 KB, re-read from L2 by every wave) then serve CT * 16 columns, and what the launch moves through the compute units'
@@ -205,8 +200,6 @@ static_assert(Q2M_NBUF >= 2 && Q2M_NBUF <= 6, "the counted waits of dotq2m_tile 
 // 54 at CT = 8, 49 at CT = 16. G = 256-individual stages requested together (2: both halves of every 128-byte line of a column
 // are asked for back to back). One accumulator set per scale (SC = true, 16 registers per column tile) or one in all (SC = false:
 // the genotypes shifted down to one scale, 7 mask / shift operations per register instead of 5, 4 registers per column tile).
-template <int CT, int G>
-static constexpr int q2m_lds() { return Q2M_NBUF * G * (CT * HBQ_SLOT + 2 * Q2M_DSTRIDE); }
 
 template <int CT, int G, bool SC>
 __device__ __forceinline__ void dotq2m_tile(const dq_view &v, char *smem, int b)
@@ -444,8 +437,6 @@ __device__ __forceinline__ void dotq2m512_tile(const dq_view &v, char *smem, int
     for (int k = 0; k < HB_ND; k++)
         __hip_atomic_fetch_add(v.accq + (int64_t)k * v.accstride + cg * 64 + lane, (long long)tr[k * 64 + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-template <bool SWZ>
-static constexpr int q2m512_lds() { return Q2M_NBUF * (8 * (SWZ ? 1152 : HBQ_SLOT) + 4 * 1024); }
 
 template <int CT, int G, bool SC>
 __global__ __launch_bounds__(64) void k_dotq2m(dq_view v, upd_view uq)
@@ -484,8 +475,7 @@ __global__ __launch_bounds__(64) void k_dotq2m(dq_view v, upd_view uq)
 // halving butterfly (31 exchanges) so that lane v ends up with the total of sum v — about a fifth on top of the dot4 stream.
 // Integer sums are order-independent: the results are the same exact integers as k_dotq's and k_dotq2's.
 // ---------------------------------------------------------------------------------------------
-#define Q2R_RB 4096 /* individuals per row block (64 lanes x 64) */
-#define Q2R_CB 4    /* columns per batch */
+// (Q2R_RB individuals per row block, Q2R_CB columns per batch: hb_matvecplan.hpp)
 #ifndef Q2R_PF
 #define Q2R_PF 2    /* batches requested ahead */
 #endif

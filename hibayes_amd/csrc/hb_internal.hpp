@@ -5,6 +5,7 @@
 #include <string>
 #include <vector>
 #include "../../include/hibayes_gpu.h"
+#include "hb_matvecplan.hpp"
 
 // thread-local last error (hb_last_error)
 void hb_set_error(const std::string &msg);
@@ -18,7 +19,6 @@ int hb_fail(int status, const std::string &msg);
     } while (0)
 
 // layout of the per-sweep scalar block the kernels accumulate into / the host reads back
-#define HB_ND 7 /* int8 digits of the fixed-point residual: 55 bits + sign */
 // Words that one workgroup writes through and others read behind a flag — the panels' move counts, the groups' bounds on max |yadj| —
 // live ONE PER 128-BYTE LINE: a reader that touched the line for panel p while the chain was writing panel p + 1's word into it could
 // otherwise be left with a copy that shows the neighbour's old value (the stale-line hazard of DESIGN.md §9.0), and such a word is not
@@ -73,13 +73,7 @@ struct hb_ctx {
     uint32_t *X2 = nullptr;
     int64_t ld2 = 0;     // bytes per column of X2 = 128 * ceil(ld / 512)
     int layout = 8;      // 8: int8 columns, 2: 2-bit columns
-    int dotq_tiles = 768;          // tiles per k_dotq launch (HB_DOTQ_TILES): about three waves per compute unit
-    bool dotq2_tiles_set = false;  // HB_DOTQ2_TILES given: it then also holds for k_dotq2m, whose own targets and XCD budget (launch_dotq2) are skipped
-    int dotq2_cpl = 1, dotq2_tiles = 1600, dotq2_rs = 256; // (tiles per full-width k_dotq2 launch, HB_DOTQ2_TILES: 1568 of seven stages at n = 50k — with two waves per SIMD (k_dotq2 allocates 176 VGPRs for that) 2048 waves are resident, and tiles + update rows + the chain's and k_fwd's compute units must fit; until that cap 2000 -> 1848 tiles of six stages: 296 against 300 sweeps/s)
-    // which kernel computes the panel mat-vec on 2-bit resident genotypes (HB_DOTQ2_KIND / hb_ctx_set_matvec_kernel; all three give the same exact integers):
-    // 2 (default since round 5) k_dotq2m, the seven digit planes as a skinny int8 GEMM on the matrix cores — 12.0 us per 3584-column launch isolated; 0 k_dotq2,
-    // lane = column through LDS, v_dot4 (22 us: VALU-issue-bound; the default until round 4); 1 k_dotq2r, individuals across the lanes, no LDS, NC columns per tile (26 us)
-    int dotq2_kind = 2, dotq2_nc = 16;
+    hb_matvec_knobs mv;  // the mat-vec launches' kernel and tiling knobs (hb_matvecplan.hpp: plan_matvec reads them)
     double *xpx = nullptr, *vx = nullptr, *g = nullptr, *vargL = nullptr;
     double *s1 = nullptr; // column sums of the resident rows (k_stats), for the row-sharded mode's global statistics
     double *alpha_sum = nullptr, *alpha_sq = nullptr;
@@ -103,8 +97,6 @@ struct hb_ctx {
     bool gcert_ok = false, gcert_on = true;                 // (HB_CERT=0: off)
     bool env_pinned = false;
     int dot_lds = 0;     // dynamic LDS bytes requested by each mat-vec workgroup: caps the workgroups resident per CU
-    int q2m_ct = 4, q2m_g = 0, q2m_sc = 1; // k_dotq2m's shape (HB_Q2M_CT / _G / _SC): column tiles of 16 per wave; stages requested together (1, 2) or 512-individual stages of whole-line
-                                           // DMA pieces (0, the default since round 5: 12.3 against 15.3 us per launch; 3: the same with conflict-free lane order); per-scale accumulators
     double candf = 1.0;  // chain candidates: markers at zero with q >= candf * thr0 (tuning knob; <= 1)
     double kappa = 3.0; // row-cache prediction: markers with thr0 <= kappa * xx * vare get their Gram row prefetched
     bool gram_ready = false, stats_ready = false;

@@ -25,7 +25,8 @@
 //                    hb_reduce.hpp         var(u), yadj.yadj, BayesL's variances, GWAS windows
 //   ingest / egress  hb_stats.hpp          xpx, vx                              hb_ingest.hpp  f64 check, .bed decode, X alpha, GEBV, generator
 //   summary level    hb_sbayes.hpp         SBayesD on a dense LD matrix
-//   host plan        hb_plan.hpp           which chain, k_fwd and warmers a sweep runs (plan_sweep: no HIP, tested on the CPU)
+//   host plans       hb_plan.hpp           which chain, k_fwd and warmers a sweep runs (plan_sweep: no HIP, tested on the CPU)
+//                    hb_matvecplan.hpp     which kernel, tiling and LDS a mat-vec launch gets (plan_matvec: the same), the shapes' lists and LDS formulas
 //   this file        sweep start (k_sweep_init, k_quant0), the launch tables, the launchers, graph capture, probes, thin wrappers for hb_ctx.hip
 #include "hb_internal.hpp"
 #include "hb_plan.hpp"
@@ -160,7 +161,6 @@ template <int N, class... Params>
 struct kernel_entry {
     int arg[N];             // template arguments
     void (*fn)(Params...);  // the kernel
-    int lds;                // (the mat-vec table: dynamic LDS of the shape)
 };
 #define HB_GROUP_ENTRY(K1, DM, FW, CH, CERT) {{K1, DM, FW, CH, CERT}, k_chain_group<K1, DM, FW, CH, (CERT) != 0>},
 #define HB_PERSIST_ENTRY(K1, NPL) {{K1, NPL}, k_chain_persist<K1, NPL>},
@@ -204,146 +204,86 @@ static hipError_t launch_chain(hb_ctx *c, const chain_view &cv, int p, hipStream
 // residual version v (moves of panels <= v applied; v = -1: start of the sweep) lives in slot (v+1) mod NB
 static inline int ver_slot(const hb_ctx *c, int v) { return (v + 1) % c->NB; }
 
-// What every launch of the fixed-point mat-vec (k_dotq, k_dotq2, k_dotq2m, k_dotq2r) shares: the residual slot's digits and exponent, the plane sums,
-// the update and finalize rows that ride in the launch, the finalize window. The launcher adds X or X2, nstages, NS and ncg ...
-static dq_view dq_common(hb_ctx *c, int col0, int slot, int gidx, const upd_view &uq, int fin_col0, int fin_ncols, int fin_gidx)
+// One launch of the panel mat-vec as its caller describes it: the columns, and what the defaults leave out
+struct dot_launch {
+    int col0, ncols;                  // the launch's columns (whole panels)
+    int slot = 0;                     // the residual slot it reads
+    hipStream_t st = nullptr;         // (null: the context's stream)
+    int gidx = 0;                     // its index in the sweep: exponent word, block stamps, time-out diagnostics
+    const upd_view *upd = nullptr;    // the update rows that ride in it
+    int fin_col0 = 0, fin_ncols = 0;  // the columns of launch gidx - 1, whose sums it finalizes (fixed point) or reduces (k_dot)
+};
+
+// the built shapes of the 2-bit mat-vec (hb_dotq2.hpp), expanded from the plan's own lists (hb_matvecplan.hpp): {HB_MV_DOTQ2M, CT, G, SC}, {HB_MV_DOTQ2, CPL, RS, 0}
+#define HB_Q2M_ENTRY(CT, G, SC) {{HB_MV_DOTQ2M, CT, G, SC}, k_dotq2m<CT, G, (SC) != 0>},
+#define HB_Q2_ENTRY(CPL, RS) {{HB_MV_DOTQ2, CPL, RS, 0}, k_dotq2<CPL, RS>},
+static const kernel_entry<4, dq_view, upd_view> dotq2_kernels[] = {HB_DOTQ2M_KERNELS(HB_Q2M_ENTRY) HB_DOTQ2_KERNELS(HB_Q2_ENTRY)};
+// the update rows that ride in a launch stage their move lists at the head of the block's dynamic LDS (k_dotq2r, which asks for none, has a buffer of its own)
+#define HB_Q2M_HOLDS(CT, G, SC) static_assert(q2m_lds(CT, G) >= HBU_ROWS_LDS, "k_dotq2m: a shape's LDS does not hold the update rows' move lists");
+#define HB_Q2_HOLDS(CPL, RS) static_assert(q2_lds(CPL, RS) >= HBU_ROWS_LDS, "k_dotq2: a shape's LDS does not hold the update rows' move lists");
+HB_DOTQ2M_KERNELS(HB_Q2M_HOLDS) HB_DOTQ2_KERNELS(HB_Q2_HOLDS)
+static_assert(HBQ_LDS >= HBU_ROWS_LDS, "k_dotq: its LDS does not hold the update rows' move lists");
+
+// One launch of the fixed-point mat-vec (k_dotq, k_dotq2, k_dotq2m, k_dotq2r). WHAT it is — kernel, template arguments, stages per tile, tiles, blocks,
+// LDS — is plan_matvec's answer (hb_matvecplan.hpp, tested on the CPU); here the launch is described, the view filled, the block count registered.
+static int launch_dotq(hb_ctx *c, const dot_launch &l, hipStream_t st)
 {
+    const upd_view uq = l.upd ? *l.upd : upd_view{};
+    const int gidx = l.gidx;
+    // the residual slot's digits and exponent, the plane sums, the update and finalize rows that ride in the launch, the finalize window
     dq_view v{};
     v.ld = c->ld;
-    v.rq = c->rq + (size_t)slot * HB_ND * c->ld;
-    v.vexp_in = c->vexp + slot;
+    v.rq = c->rq + (size_t)l.slot * HB_ND * c->ld;
+    v.vexp_in = c->vexp + l.slot;
     v.gexp_out = c->gexp + gidx;
-    v.accq = c->accq + col0;
+    v.accq = c->accq + l.col0;
     v.accstride = c->m_pad;
     v.nupd = (uq.p1 > uq.p0) ? (int)(c->ld / (uq.dense ? 64 : 256)) : 0;
-    v.nfin = fin_ncols > 0 ? (fin_ncols + 63) / 64 : 0;
-    v.fin_acc = c->accq + fin_col0;
-    v.fin_out = c->dsum + fin_col0;
-    v.fin_exp = c->gexp + fin_gidx;
-    v.fin_ncols = fin_ncols;
-    return v;
-}
-
-// ... and, once it knows its tiles, has the launch registered for the block stamps and the time-out diagnostics. Returns the launch's blocks.
-static int dq_register(hb_ctx *c, dq_view *v, int gidx, int ncols, int ntiles)
-{
-    const int nblk = v->nupd + v->nfin + ntiles;
-    v->ldiag = (c->ldiag && gidx >= 0 && gidx <= c->npanels) ? c->ldiag + 4 * (size_t)gidx : nullptr;
-    if (v->ldiag) c->ldiag_nblk[gidx] = nblk;
-    if (c->lstamp && gidx >= 0 && gidx <= c->npanels && nblk <= HB_LSTAMP_BLOCKS) {
-        v->stamp = c->lstamp + (size_t)gidx * HB_LSTAMP_BLOCKS * 2;
-        c->lstamp_nblk[gidx] = nblk;
-        c->lstamp_cols[gidx] = ncols;
+    v.nfin = l.fin_ncols > 0 ? (l.fin_ncols + 63) / 64 : 0;
+    v.fin_acc = c->accq + l.fin_col0;
+    v.fin_out = c->dsum + l.fin_col0;
+    v.fin_exp = c->gexp + gidx - 1;
+    v.fin_ncols = l.fin_ncols;
+    if (c->layout == 2) {
+        v.X2 = reinterpret_cast<const uint8_t *>(c->X2) + (int64_t)l.col0 * c->ld2;
+        v.ld2 = c->ld2;
+    } else v.X = c->X + (int64_t)l.col0 * c->ld;
+    const hb_matvec_plan p = plan_matvec(hb_matvec_shape{c->layout, c->ld, c->ld2, l.ncols, v.nupd, v.nfin, uq.dense != 0, c->num_cus}, c->mv);
+    v.nstages = p.nstages;
+    v.NS = p.NS;
+    v.ncg = p.ncg;
+    // the launch's blocks, for the block stamps and the time-out diagnostics
+    v.ldiag = (c->ldiag && gidx >= 0 && gidx <= c->npanels) ? c->ldiag + 4 * (size_t)gidx : nullptr;
+    if (v.ldiag) c->ldiag_nblk[gidx] = p.blocks;
+    if (c->lstamp && gidx >= 0 && gidx <= c->npanels && p.blocks <= HB_LSTAMP_BLOCKS) {
+        v.stamp = c->lstamp + (size_t)gidx * HB_LSTAMP_BLOCKS * 2;
+        c->lstamp_nblk[gidx] = p.blocks;
+        c->lstamp_cols[gidx] = l.ncols;
     }
-    return nblk;
-}
-
-// the shapes of the 2-bit mat-vec (hb_dotq2.hpp) with their LDS: {1, CT, G, SC} k_dotq2m on the matrix cores (G = 0 / 3: the 512-individual stages),
-// {0, CPL, RS, 0} k_dotq2 (RS = 128: 6208 bytes of LDS per wave, twice the waves per compute unit)
-#define HB_Q2M_ENTRY(CT, G, LDS) {{1, CT, G, 0}, k_dotq2m<CT, G, false>, LDS}, {{1, CT, G, 1}, k_dotq2m<CT, G, true>, LDS},
-#define HB_Q2_ENTRY(CPL, RS) {{0, CPL, RS, 0}, k_dotq2<CPL, RS>, q2_lds(CPL, RS)},
-static const kernel_entry<4, dq_view, upd_view> dotq2_kernels[] = {
-    HB_Q2M_ENTRY(4, 0, q2m512_lds<false>()) HB_Q2M_ENTRY(4, 3, q2m512_lds<true>()) HB_Q2M_ENTRY(16, 1, (q2m_lds<16, 1>())) HB_Q2M_ENTRY(8, 2, (q2m_lds<8, 2>()))
-    HB_Q2M_ENTRY(8, 1, (q2m_lds<8, 1>())) HB_Q2M_ENTRY(4, 2, (q2m_lds<4, 2>())) HB_Q2M_ENTRY(4, 1, (q2m_lds<4, 1>()))
-    HB_Q2_ENTRY(2, 512) HB_Q2_ENTRY(2, 256) HB_Q2_ENTRY(1, 512) HB_Q2_ENTRY(1, 128) HB_Q2_ENTRY(1, 256)};
-
-// the mat-vec launch on the 2-bit resident layout (hb_dotq2.hpp): about two long-lived waves per compute unit
-static int launch_dotq2(hb_ctx *c, int col0, int ncols, int slot, hipStream_t st, int gidx, const upd_view *upd, int fin_col0,
-                         int fin_ncols, int fin_gidx)
-{
-    const upd_view uq = upd ? *upd : upd_view{};
-    dq_view v = dq_common(c, col0, slot, gidx, uq, fin_col0, fin_ncols, fin_gidx);
-    v.X2 = reinterpret_cast<const uint8_t *>(c->X2) + (int64_t)col0 * c->ld2;
-    v.ld2 = c->ld2;
-    if (c->dotq2_kind == 1) { // rows across the lanes, no LDS (k_dotq2r): tiles = row blocks x groups of NC columns
-        int NC = c->dotq2_nc;
-        while (NC > Q2R_CB && ncols % NC) NC -= Q2R_CB;
-        if (ncols % NC == 0 && NC % Q2R_CB == 0 && c->ld >= 64) {
-            v.NS = NC;
-            v.ncg = ncols / NC;
-            v.nstages = (int)((c->ld2 * 4 + Q2R_RB - 1) / Q2R_RB);
-            const int nblk = dq_register(c, &v, gidx, ncols, v.ncg * v.nstages);
-            hipLaunchKernelGGL(k_dotq2r, dim3(nblk), dim3(64), 0, st, v, uq);
-            return HB_OK;
-        }
+    void (*fn)(dq_view, upd_view) = p.family == HB_MV_DOTQ ? k_dotq : p.family == HB_MV_DOTQ2R ? k_dotq2r : nullptr;
+    if (!fn) { // (the families with a table)
+        const int shape[4] = {p.family, p.arg[0], p.arg[1], p.arg[2]};
+        const auto *k = find_kernel(dotq2_kernels, shape, p.family == HB_MV_DOTQ2M ? "k_dotq2m" : "k_dotq2");
+        if (!k) return HB_ERR_INVALID;
+        fn = k->fn;
     }
-    const bool mfma = c->dotq2_kind == 2; // (A/B: the digit-plane product on the matrix cores, k_dotq2m; 256-individual stages, 64 columns per wave)
-    int cpl = (ncols % 128 == 0 && !mfma && c->dotq2_rs != 128) ? c->dotq2_cpl : 1;
-    // the matrix-core kernel's shape (hb_dotq2.hpp): column tiles of 16 per wave, stages requested together, one accumulator set per scale or one
-    int q2m_ct = c->q2m_ct, q2m_g = c->q2m_g;
-    while (mfma && q2m_ct > 4 && ncols % (16 * q2m_ct)) q2m_ct /= 2;
-    if (q2m_ct == 16 && q2m_g == 2) q2m_g = 1;
-    if ((q2m_g == 0 || q2m_g == 3) && (c->ld % 512 != 0 || ncols % 64)) q2m_g = 1; // (the 512-individual stages read whole stages of digits: the padded length must be a multiple)
-    if (q2m_g == 0 || q2m_g == 3) q2m_ct = 4;
-    const int RS = mfma ? ((q2m_g == 0 || q2m_g == 3) ? 512 : Q2M_RS) : c->dotq2_rs;
-    const int nst = (int)((c->ld + RS - 1) / RS);
-    const int ncg = mfma ? ncols / (16 * q2m_ct) : ncols / (64 * cpl);
-    // (a tile is at least four stages: its first stage's load latency and its closing atomics are paid per tile)
-    // (the matrix-core kernel streams best with few, long tiles — its per-stage work is an eighth of the v_dot4 kernel's, so a tile's fixed
-    // costs weigh more: ~800 tiles per 3584-column launch)
-    int ns = std::max(1, std::min(std::max(1, nst / 4), (int)((double)(mfma && !c->dotq2_tiles_set ? ((q2m_g == 0 || q2m_g == 3) ? 900 : 800) : c->dotq2_tiles) / ncg + 0.5)));
-    // (int32 accumulators of genotypes scaled by up to 32 — Q2_SCALED, k_dotq2m: rows x 96 x 128 < 2^31 bounds a tile at 174 000 individuals)
-    ns = std::max(ns, (int)(((int64_t)nst * RS + 131071) / 131072));
-    if (mfma && (q2m_g == 0 || q2m_g == 3) && !c->dotq2_tiles_set) {
-        // ALL blocks of the launch resident at once (round 5, the last measurement of the round). A block of this kernel holds 37 KB of LDS: four per
-        // compute unit, 128 per XCD — less the chain workgroup's compute unit and k_fwd's share of another, which sit on ONE XCD — and the
-        // dispatcher deals the blocks round-robin over the eight XCDs whatever they have free. 784 tiles + 196 update + 56 finalize blocks = 1 036
-        // is 130 per XCD: the XCD with the chain started its last nine tiles when its first ones ended, 8.4 us into a 9-us launch, and the launch
-        // took 14.6 us in situ (tools/launch_roles.py). Fewer, longer tiles until the fullest XCD's share fits its slots: 12.6 us, 433 -> 454 sweeps/s.
-        const int lds = q2m_g == 3 ? q2m512_lds<true>() : q2m512_lds<false>();
-        const int per_cu = std::max(1, std::min(8, (160 * 1024) / std::max(1, lds)));
-        const int cus_per_xcd = std::max(1, c->num_cus / 8);
-        const int budget = 8 * (cus_per_xcd * per_cu - (per_cu + 3)); // (the fullest XCD gets ceil(blocks / 8))
-        auto total = [&](int k) { const int NSk = (nst + k - 1) / k; return v.nupd + v.nfin + ncg * ((nst + NSk - 1) / NSk); };
-        const int ns_min = std::max(1, (int)(((int64_t)nst * RS + 131071) / 131072));
-        while (ns > ns_min && total(ns) > budget) ns--;
-    }
-    v.nstages = nst;
-    v.NS = (nst + ns - 1) / ns;
-    v.ncg = ncg;
-    const int nblk = dq_register(c, &v, gidx, ncols, ncg * ((nst + v.NS - 1) / v.NS));
-    // (the update rows stage their lists in the tile buffers: 6152 bytes, below the smallest shape's 12416)
-    const int shape[4] = {mfma, mfma ? q2m_ct : cpl, mfma ? q2m_g : RS, mfma && c->q2m_sc};
-    const auto *k = find_kernel(dotq2_kernels, shape, mfma ? "k_dotq2m" : "k_dotq2");
-    if (!k) return HB_ERR_INVALID;
-    hipLaunchKernelGGL(k->fn, dim3(nblk), dim3(64), k->lds, st, v, uq);
+    hipLaunchKernelGGL(fn, dim3(p.blocks), dim3(64), p.lds, st, v, uq);
     return HB_OK;
 }
 
-static int launch_dotq(hb_ctx *c, int col0, int ncols, int slot, hipStream_t st, int gidx, const upd_view *upd, int fin_col0,
-                        int fin_ncols, int fin_gidx)
+static int launch_dot(hb_ctx *c, const dot_launch &l)
 {
-    if (c->layout == 2) return launch_dotq2(c, col0, ncols, slot, st, gidx, upd, fin_col0, fin_ncols, fin_gidx);
-    // tiles of one k_dotq launch: about three waves per compute unit, each a long run of stages (measured: fewer, longer
-    // waves stream better than many short ones; tools/dotq_bench.hip)
-    const int nst = (int)(c->ld / HBQ_RS), ncg = ncols / 64;
-    const int ns = std::max(1, std::min(nst, (int)((double)c->dotq_tiles / ncg + 0.5)));
-    const upd_view uq = upd ? *upd : upd_view{};
-    dq_view v = dq_common(c, col0, slot, gidx, uq, fin_col0, fin_ncols, fin_gidx);
-    v.X = c->X + (int64_t)col0 * c->ld;
-    v.nstages = nst;
-    v.NS = std::min(1024, (nst + ns - 1) / ns); // (int32 accumulators: NS * 128 rows * 127 * 128 < 2^31)
-    v.ncg = ncg;
-    const int nblk = dq_register(c, &v, gidx, ncols, ncg * ((nst + v.NS - 1) / v.NS));
-    hipLaunchKernelGGL(k_dotq, dim3(nblk), dim3(64), uq.dense ? HBU_LDS : HBQ_LDS, st, v, uq);
-    return HB_OK;
-}
-
-static int launch_dot(hb_ctx *c, int col0, int ncols, int slot = 0, hipStream_t st = nullptr, bool pipeline = false,
-                       const upd_view *upd = nullptr, int red_col0 = 0, int red_ncols = 0, int gidx = 0)
-{
-    if (!st) st = c->stream;
+    hipStream_t st = l.st ? l.st : c->stream;
+    if (c->precise == 2) return launch_dotq(c, l, st);
     upd_view uq{};
-    if (upd) uq = *upd;
-    if (!pipeline) red_ncols = 0;
-    if (c->precise == 2) return launch_dotq(c, col0, ncols, slot, st, gidx, upd, red_col0, red_ncols, gidx - 1);
-    const dim3 grid(ncols / 8, c->nsplit + (uq.p1 > uq.p0 ? 1 : 0) + (red_ncols > 0 ? 1 : 0)), block(256);
-    const int8_t *Xp = c->X + (int64_t)col0 * c->ld;
-    double *part = c->partial + col0;
-    const float *r32 = c->r32 + (size_t)slot * c->ld;
-    const double *r64 = c->r + (size_t)slot * c->ld;
+    if (l.upd) uq = *l.upd;
+    const dim3 grid(l.ncols / 8, c->nsplit + (uq.p1 > uq.p0 ? 1 : 0) + (l.fin_ncols > 0 ? 1 : 0)), block(256);
+    const int8_t *Xp = c->X + (int64_t)l.col0 * c->ld;
+    double *part = c->partial + l.col0;
+    const float *r32 = c->r32 + (size_t)l.slot * c->ld;
+    const double *r64 = c->r + (size_t)l.slot * c->ld;
     const bool sgn = c->xmin < 0;
-    dot_sync sy{c->partial + red_col0, c->dsum + red_col0, red_ncols, c->nsplit};
+    dot_sync sy{c->partial + l.fin_col0, c->dsum + l.fin_col0, l.fin_ncols, c->nsplit};
     if (c->precise) {
         if (sgn) hipLaunchKernelGGL((k_dot<true, true>), grid, block, c->dot_lds, st, Xp, c->ld, r32, r64, c->nchunks, 1, part, c->m_pad, sy, uq);
         else     hipLaunchKernelGGL((k_dot<true, false>), grid, block, c->dot_lds, st, Xp, c->ld, r32, r64, c->nchunks, 1, part, c->m_pad, sy, uq);
@@ -492,7 +432,8 @@ static int enqueue_sweep_kernels(hb_ctx *c, int model, int n_fold, bool timed)
             hipEvent_t b = tm.begin();
             const int vread = pd - L - 1;
             if (!timed && vread >= 0) HB_HIP(hipStreamWaitEvent(sA, c->ev_upd[vread], 0));
-            if (int rc = launch_dot(c, pd * c->P, c->P, ver_slot(c, vread < -1 ? -1 : vread), sA, false, nullptr, 0, 0, pd)) return rc;
+            dot_launch dl{pd * c->P, c->P, ver_slot(c, vread < -1 ? -1 : vread), sA, pd};
+            if (int rc = launch_dot(c, dl)) return rc;
             if (fx && c->row_reduce)
                 if (int rcr = row_reduce_accq(c, pd * c->P, c->P, sA)) return rcr;
             if (fx) launch_dotq_fin(c, pd * c->P, c->P, pd, c->partial + (size_t)pd * c->P, sA); // the chain sums one "split"
@@ -712,8 +653,10 @@ static int enqueue_sweep_pipeline(hb_ctx *c, int model, int n_fold, int pb, int 
             hipLaunchKernelGGL(k_update_dense, dim3((unsigned)(c->ld / 64)), dim3(64), 0, sA, c->ld, uq);
             ride = false;
         }
-        if (int rc = launch_dot(c, p0 * c->P, (p1 - p0) * c->P, slot2(g - Lv - 1), sA, true, ride ? &uq : nullptr,
-                                g > 0 ? (ga - 1) * D * c->P : 0, g > 0 ? D * c->P : 0, ga)) return rc;
+        dot_launch dl{p0 * c->P, (p1 - p0) * c->P, slot2(g - Lv - 1), sA, ga};
+        if (ride) dl.upd = &uq;
+        if (g > 0) dl.fin_col0 = (ga - 1) * D * c->P, dl.fin_ncols = D * c->P;
+        if (int rc = launch_dot(c, dl)) return rc;
     }
     launch_reduce(c, (g0 + ngroups - 1) * D * c->P, last_panels * c->P, sA, g0 + ngroups - 1);
     if (alone)
@@ -860,12 +803,12 @@ int hbk_dot_all(hb_ctx *c)
 {
     if (c->precise == 2) {
         launch_quant0(c, c->stream);
-        for (int p = 0; p < c->npanels; p++) if (int rc = launch_dot(c, p * c->P, c->P)) return rc;
+        for (int p = 0; p < c->npanels; p++) if (int rc = launch_dot(c, dot_launch{p * c->P, c->P})) return rc;
         launch_dotq_fin(c, 0, c->m_pad, 0, c->dots, c->stream);
         HB_HIP(hipGetLastError());
         return HB_OK;
     }
-    for (int p = 0; p < c->npanels; p++) if (int rc = launch_dot(c, p * c->P, c->P)) return rc;
+    for (int p = 0; p < c->npanels; p++) if (int rc = launch_dot(c, dot_launch{p * c->P, c->P})) return rc;
     hipLaunchKernelGGL(k_sum_partials, dim3((c->m_pad + 255) / 256), dim3(256), 0, c->stream, c->partial, c->m_pad,
                        c->nsplit, c->m_pad, c->dots);
     HB_HIP(hipGetLastError());
@@ -875,7 +818,7 @@ int hbk_dot_all(hb_ctx *c)
 int hbk_dot_panels(hb_ctx *c, int reps)
 {
     for (int r = 0; r < reps; r++)
-        for (int p = 0; p < c->npanels; p++) if (int rc = launch_dot(c, p * c->P, c->P)) return rc;
+        for (int p = 0; p < c->npanels; p++) if (int rc = launch_dot(c, dot_launch{p * c->P, c->P})) return rc;
     HB_HIP(hipGetLastError());
     return HB_OK;
 }
@@ -1090,8 +1033,10 @@ int hbk_time_matvec(hb_ctx *c, int D, int reps, int as_pipeline, double *avg_us,
     int rc = HB_OK;
     for (int gi = 0; gi < ngroups && !rc; gi++) {
         const int p0 = gi * D, p1 = std::min(c->npanels, p0 + D);
-        rc = launch_dot(c, p0 * c->P, (p1 - p0) * c->P, 0, c->stream, as_pipeline != 0, nullptr,
-                        gi > 0 ? (gi - 1) * D * c->P : 0, gi > 0 ? D * c->P : 0, gi);
+        dot_launch dl{p0 * c->P, (p1 - p0) * c->P};
+        dl.gidx = gi;
+        if (as_pipeline && gi > 0) dl.fin_col0 = (gi - 1) * D * c->P, dl.fin_ncols = D * c->P;
+        rc = launch_dot(c, dl);
     }
     if (as_pipeline) launch_reduce(c, (ngroups - 1) * D * c->P, (c->npanels - (ngroups - 1) * D) * c->P, c->stream, ngroups - 1);
     HB_HIP(hipStreamEndCapture(c->stream, &g));

@@ -144,13 +144,7 @@ __global__ __launch_bounds__(256) void k_dot(const int8_t *__restrict__ X, int64
 // earlier group (its digits included), then the tiles.
 // ---------------------------------------------------------------------------------------------
 typedef int hb_v4i __attribute__((ext_vector_type(4)));
-#define HBQ_RS 128                       /* rows per stage */
-#define HBQ_SLOT 1040
-#define HBQ_NX 8                         /* DMA pieces per stage for the genotype tile (8 columns x 128 rows each) */
-#define HBQ_XB (HBQ_NX * HBQ_SLOT)
-#define HBQ_BUF (HBQ_XB + 1024)          /* + one piece for the 7 digit planes */
-#define HBQ_PER (HBQ_NX + 1)
-#define HBQ_LDS (2 * HBQ_BUF)
+// (HBQ_RS rows per stage, the slot stride HBQ_SLOT, HBQ_NX pieces, HBQ_BUF, HBQ_PER and HBQ_LDS: hb_matvecplan.hpp — the host plan sizes the launch with them)
 
 struct dq_view {
     const int8_t *X;       // first column of this launch

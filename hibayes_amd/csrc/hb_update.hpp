@@ -65,6 +65,9 @@ __device__ __forceinline__ void hb_store_digits(int8_t *rq, int64_t ld, int64_t 
 }
 
 // rows [row0, row0 + 4) of the residual: yadj -= sum_e x_e D_e, u += the same, r32 = (float)yadj
+// (the move lists s_ix, 512 ints, and s_dl, 512 doubles behind them: in a mat-vec launch they are the head of the block's tile buffers, so every
+// shape's dynamic LDS must hold them — hb_kernels.hip asserts it of every listed shape)
+#define HBU_ROWS_LDS (512 * 4 + 512 * 8)
 __device__ __forceinline__ void update_rows(int64_t ld, const upd_view &q, int blk, int *s_ix,
                                             double *s_dl, unsigned long long *ust = nullptr)
 {
@@ -240,8 +243,7 @@ __device__ __forceinline__ void update_rows(int64_t ld, const upd_view &q, int b
 // Same sums in the same (marker) order as update_rows: the same residual bit for bit. Groups of at most 2 panels.
 // smem: [0, 8192) the group's changes (<= 1024 doubles), [8192, 8208) flags, [HBU_SLAB, HBU_SLAB + 16384) two chunk buffers.
 #define HBU_SENT(x) (__double_as_longlong(x) == -1ll)
-#define HBU_SLAB 8448
-#define HBU_LDS (HBU_SLAB + 16384)
+// (HBU_SLAB and HBU_LDS: hb_matvecplan.hpp)
 __device__ __forceinline__ void update_rows_dense(int64_t ld, const upd_view &q, int blk, int nblk, char *smem)
 {
     double *s_dl = reinterpret_cast<double *>(smem);

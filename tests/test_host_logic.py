@@ -540,3 +540,132 @@ def test_every_run_plan_equals_the_recorded_decisions(tmp_path):
                                   and mem >= 2 and (model in (3, 4) or (model == 6 and nf <= 4))), k
         else:
             assert (v == "2") == (bits == 2 and own == 1), k
+
+
+_MATVECPLAN_PROGRAM = r"""
+#include "hb_matvecplan.hpp"
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+#define M(ct, g, sc) printf("table k_dotq2m<%d,%d,%d> %d\n", ct, g, sc, q2m_lds(ct, g));
+#define Q(cpl, rs) printf("table k_dotq2<%d,%d> %d\n", cpl, rs, q2_lds(cpl, rs));
+static const char *fake_name, *fake_val;
+static const char *fake_getenv(const char *k) { return fake_name && !strcmp(k, fake_name) ? fake_val : nullptr; }
+
+// one family's rows: its knobs (the key's prefix) over ld x ncols x num_cus x update rows x finalize rows
+static void rows(const char *stage, const char *prefix, int layout, const hb_matvec_knobs &k)
+{
+    std::vector<int> widths;
+    for (int w = 64; w <= 4096; w += 64)
+        for (int P : {64, 128, 256, 512}) if (w % P == 0 && w / P <= 8) { widths.push_back(w); break; }
+    for (long long ld : {256, 512, 768, 1024, 1280, 1536, 2048, 5120, 50176, 131072, 174080, 400384}) for (int ncols : widths) for (int cus : {32, 64, 256})
+    for (int upd = 0; upd < (layout == 8 ? 3 : 2); upd++) for (int fin = 0; fin < 4; fin++) {
+        const int nupd = upd == 0 ? 0 : (int)(ld / (upd == 2 ? 64 : 256)), fin_ncols = fin == 0 ? 0 : fin == 1 ? ncols / 2 : fin == 2 ? ncols : 2 * ncols;
+        const int nfin = (fin_ncols + 63) / 64;
+        const hb_matvec_plan p = plan_matvec(hb_matvec_shape{layout, ld, 128 * ((ld + 511) / 512), ncols, nupd, nfin, upd == 2, cus}, k);
+        char name[64];
+        if (p.family == HB_MV_DOTQ2M) snprintf(name, sizeof name, "k_dotq2m<%d,%d,%d>", p.arg[0], p.arg[1], p.arg[2]);
+        else if (p.family == HB_MV_DOTQ2) snprintf(name, sizeof name, "k_dotq2<%d,%d>", p.arg[0], p.arg[1]);
+        else snprintf(name, sizeof name, p.family == HB_MV_DOTQ2R ? "k_dotq2r" : "k_dotq");
+        // what the record holds | what the arithmetic invariants read
+        printf("%s %s %lld %d %d %d %d | %s %d %d %d %d %d | %d %d %d %d\n", stage, prefix, ld, ncols, cus, upd, fin, name, p.nstages, p.ncg, p.lds, p.NS,
+               p.ncg ? p.tiles / p.ncg : -1, p.tiles, p.blocks, nupd, nfin);
+    }
+}
+
+int main()
+{
+    HB_DOTQ2M_KERNELS(M) HB_DOTQ2_KERNELS(Q)
+    printf("table k_dotq %d\ntable k_dotq2r 0\nneed %d\n", HBQ_LDS, 512 * 4 + 512 * 8); // (need: the update rows' move lists, HBU_ROWS_LDS of hb_update.hpp)
+    char pre[64];
+    for (int t : {256, 768, 2000}) { hb_matvec_knobs k; k.dotq_tiles = t; snprintf(pre, sizeof pre, "%d", t); rows("dotq", pre, 8, k); }
+    for (int cpl : {1, 2}) for (int rs : {128, 256, 512}) for (int t : {400, 1600, 2000}) {
+        hb_matvec_knobs k; k.kind = 0; k.dotq2_cpl = cpl; k.dotq2_rs = rs; k.dotq2_tiles = t; k.dotq2_tiles_set = true;
+        snprintf(pre, sizeof pre, "%d %d %d", cpl, rs, t); rows("dotq2", pre, 2, k);
+    }
+    for (int nc : {4, 8, 12, 16, 32}) { hb_matvec_knobs k; k.kind = 1; k.nc = nc; snprintf(pre, sizeof pre, "%d", nc); rows("dotq2r", pre, 2, k); }
+    for (int sc : {0, 1}) for (int g : {0, 1, 2, 3}) for (int ct : {4, 8, 16}) for (int t : {0, 400, 800, 1600}) { // (t == 0: HB_DOTQ2_TILES not given)
+        hb_matvec_knobs k; k.q2m_sc = sc; k.q2m_g = g; k.q2m_ct = ct;
+        if (t) k.dotq2_tiles = t, k.dotq2_tiles_set = true;
+        snprintf(pre, sizeof pre, "%d %d %d %d", sc, g, ct, t); rows("dotq2m", pre, 2, k);
+    }
+    for (const char *n : {"HB_DOTQ_TILES", "HB_DOTQ2_TILES", "HB_DOTQ2_KIND", "HB_DOTQ2_CPL", "HB_DOTQ2_RS", "HB_DOTQ2_NC", "HB_Q2M_CT", "HB_Q2M_G", "HB_Q2M_SC"})
+    for (const char *r : {"unset", "0", "1", "2", "3", "4", "7", "8", "12", "15", "16", "17", "33", "128", "256", "400", "512", "2000", "-1", "x", "empty"}) {
+        fake_name = strcmp(r, "unset") ? n : nullptr;
+        fake_val = strcmp(r, "empty") ? r : "";
+        const hb_matvec_knobs k = matvec_knobs_from_env(fake_getenv);
+        printf("knobs %s %s | %d %d %d %d %d %d %d %d %d %d\n", n, r, k.dotq_tiles, k.dotq2_tiles, (int)k.dotq2_tiles_set, k.kind, k.dotq2_cpl, k.dotq2_rs, k.nc, k.q2m_ct, k.q2m_g, k.q2m_sc);
+    }
+}
+"""
+
+
+def test_every_matvec_plan_equals_the_recorded_launch_and_names_a_built_kernel(tmp_path):
+    """plan_matvec (hibayes_amd/csrc/hb_matvecplan.hpp: plain C++, compiled here with g++) decides what one launch of the fixed-point panel mat-vec is:
+    kernel and template arguments, stages per tile, tiles, blocks, LDS. Every input of the domain — twelve column lengths from one stage to beyond
+    the int32 bound, every width of one to eight panels, riders, 32 / 64 / 256 compute units, and per kernel family every value its knobs' clamps
+    can produce — against tests/golden/matvec_plan_table.json, which was recorded from the decision as it stood inside launch_dotq2 / launch_dotq
+    and hb_ctx_create before it became this header. Both ways between the plans and the lists hb_kernels.hip builds its launch table from; the
+    LDS of a plan is its listed kernel's and holds the update rows' move lists; the arithmetic every launch relies on; and the rows DESIGN.md
+    quotes, literally (they guard the recording itself)."""
+    import subprocess
+    from run_plan_record import recorded_matvec_plan
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    src, exe = tmp_path / "matvecplan.cpp", tmp_path / "matvecplan"
+    src.write_text(_MATVECPLAN_PROGRAM)
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(root, "hibayes_amd", "csrc"), str(src), "-o", str(exe)])
+    listed, got, extra, need = {}, {}, {}, None
+    for line in subprocess.check_output([str(exe)]).decode().splitlines():
+        if line.startswith("table "):
+            listed[line.split()[1]] = int(line.split()[2])
+        elif line.startswith("need "):
+            need = int(line.split()[1])
+        else:
+            k, v = line.split(" | ", 1)
+            stage, key = k.split(" ", 1)
+            v, _, more = v.partition(" | ")
+            got.setdefault(stage, {})[key] = v
+            if more:
+                extra[(stage, key)] = tuple(int(x) for x in more.split())
+    assert len(listed) == 14 + 5 + 2 and min(v for k, v in listed.items() if k != "k_dotq2r") >= need == 6144
+    want = recorded_matvec_plan()
+    assert {k: len(v) for k, v in want.items()} == {"dotq": 25920, "dotq2": 103680, "dotq2r": 28800, "dotq2m": 552960, "knobs": 189}
+    assert set(got) == set(want)
+    for stage, rows in want.items():
+        assert list(got[stage]) == list(rows), "the domains differ: %s" % stage
+        wrong = ["%s: %s, recorded %s" % (k, got[stage][k], w) for k, w in rows.items() if got[stage][k] != w]
+        assert not wrong, "%d rows of '%s' differ from the record, the first:\n%s" % (len(wrong), stage, "\n".join(wrong[:20]))
+    named = set()
+    for (stage, key), (tiles, blocks, nupd, nfin) in extra.items():
+        kernel, nstages, ncg, lds, NS, trows = got[stage][key].split()
+        nstages, ncg, lds, NS, trows = int(nstages), int(ncg), int(lds), int(NS), int(trows)
+        named.add(kernel)
+        assert tiles == ncg * trows and blocks == nupd + nfin + tiles, (stage, key)
+        if kernel == "k_dotq2r":  # (NS is its columns per tile: every row block a tile row)
+            assert trows == nstages and NS * ncg == int(key.split()[-4]) and lds == 0, (stage, key)
+            continue
+        assert NS * trows >= nstages and (NS - 1) * trows < nstages + trows, (stage, key)
+        if kernel == "k_dotq":
+            assert NS <= 1024, (stage, key)
+            assert lds == (24832 if key.split()[-2] == "2" else listed[kernel]), (stage, key)  # (HBU_LDS where the dense update rows ride)
+        else:
+            stage_rows = 512 if kernel.startswith("k_dotq2m<4,0") or kernel.startswith("k_dotq2m<4,3") else 256 if kernel[7] == "m" else int(kernel[10:-1])
+            assert NS * stage_rows <= 131072 and lds == listed[kernel], (stage, key)
+    assert named <= set(listed), "plans name kernels that are in no launch table: %s" % sorted(named - set(listed))
+    assert set(listed) <= named, "listed kernels that no input of the domain runs: %s" % sorted(set(listed) - named)
+
+    # ---- the literal rows: the knobs' defaults, 256 compute units, update rows ld / 256 and finalize rows ncols / 64 where they ride ----
+    def plan(stage, knobs, ld, ncols, riders):
+        key = "%s %d %d 256 %s" % (knobs, ld, ncols, "1 2" if riders else "0 0")
+        kernel, nstages, ncg, _, NS, _ = got[stage][key].split()
+        return (kernel, int(nstages), int(NS), int(ncg)) + extra[(stage, key)][:2]
+
+    assert plan("dotq2m", "1 0 4 0", 50176, 3584, True) == ("k_dotq2m<4,0,1>", 98, 9, 56, 616, 868)
+    assert plan("dotq2m", "1 0 4 0", 50176, 3584, False)[:5] == ("k_dotq2m<4,0,1>", 98, 7, 56, 784)
+    assert plan("dotq2m", "1 0 4 0", 50176, 1024, True) == ("k_dotq2m<4,0,1>", 98, 5, 16, 320, 532)
+    assert plan("dotq2", "1 256 1600", 50176, 3584, True)[:5] == ("k_dotq2<1,256>", 196, 7, 56, 1568)
+    assert plan("dotq2r", "16", 50176, 3584, True)[:5] == ("k_dotq2r", 13, 16, 224, 2912)
+    assert plan("dotq", "768", 50176, 3584, True) == ("k_dotq", 392, 28, 56, 784, 1036)
+    assert plan("dotq2m", "1 0 4 0", 768, 512, False) == ("k_dotq2m<4,1,1>", 3, 3, 8, 8, 8)      # (768 is no multiple of 512: G falls back to 1)
+    assert plan("dotq2m", "1 0 4 0", 400384, 3584, True)[:5] == ("k_dotq2m<4,0,1>", 782, 196, 56, 224)  # (196 stages of 512: the int32 floor)
