@@ -969,6 +969,25 @@ extern "C" int hb_ctx_debug_get_pre(hb_ctx *c, int32_t *kpad, double *thr, doubl
     return HB_OK;
 }
 
+extern "C" int hb_ctx_debug_get_mirrors(hb_ctx *c, int32_t *slot, int32_t *bound_index, double *r, float *r32, int32_t *ndigits, int8_t *rq,
+                                        int32_t *vexp, double *mb)
+{
+    int rc = check_cols(c, 0, 0, "hb_ctx_debug_get_mirrors");
+    if (rc) return rc;
+    HB_HIP(hipStreamSynchronize(c->stream));
+    const size_t s = (size_t)c->upd_slot, ld = (size_t)c->ld;
+    const bool fx = c->precise == 2;
+    if (slot) *slot = c->upd_slot;
+    if (bound_index) *bound_index = c->upd_mbi;
+    if (ndigits) *ndigits = fx ? HB_ND : 0;
+    if (r) HB_HIP(hipMemcpy(r, c->r + s * ld, sizeof(double) * ld, hipMemcpyDeviceToHost));
+    if (r32) HB_HIP(hipMemcpy(r32, c->r32 + s * ld, sizeof(float) * ld, hipMemcpyDeviceToHost));
+    if (fx && rq) HB_HIP(hipMemcpy(rq, c->rq + s * HB_ND * ld, (size_t)HB_ND * ld, hipMemcpyDeviceToHost));
+    if (fx && vexp) HB_HIP(hipMemcpy(vexp, c->vexp + s, sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (mb) HB_HIP(hipMemcpy2D(mb, sizeof(double), c->mb, sizeof(double) * HB_MBS, sizeof(double), (size_t)c->npanels + 2, hipMemcpyDeviceToHost));
+    return HB_OK;
+}
+
 int hb_ctx_residual_sums(hb_ctx *c, double *sum_r, double *sum_r2)
 {
     int rc = check_cols(c, 0, 0, "hb_ctx_residual_sums");

@@ -87,6 +87,7 @@ struct hb_ctx {
     int *vexp = nullptr;          // [8] exponent of the digits in each residual slot
     int *gexp = nullptr;          // [npanels + 1] exponent the mat-vec launch of each group / panel used (for its finalize)
     double *mb = nullptr;         // [npanels + 2]: mb[0] = max |yadj| at sweep start, mb[1 + h] = bound on max |yadj| after group / panel h
+    int upd_slot = 0, upd_mbi = -1; // the version slot the last enqueued update rows write and the h of their bound mb[1 + h] (hb_ctx_debug_get_mirrors)
     long long *accq = nullptr;    // [HB_ND][m_pad] exact digit-plane sums of the current sweep's mat-vecs
     int32_t *gram = nullptr;
     size_t gram_cap = 0; // ints allocated

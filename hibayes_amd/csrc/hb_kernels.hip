@@ -702,8 +702,14 @@ int hb_sweep_enqueue(hb_ctx *c, const hb_sweep_in *in, bool timed)
     if (int rc = hbk_set_timeout(c)) return rc;
     *c->h_in = *in;
     HB_HIP(hipMemcpyAsync(c->d_in, c->h_in, sizeof(hb_sweep_in), hipMemcpyHostToDevice, c->stream));
+    // (what hb_ctx_debug_get_mirrors reads: the per-panel kernels end in ver_slot(np - 1), a range of the pipeline in slot2(ngroups - 1))
+    c->upd_slot = c->npanels % c->NB, c->upd_mbi = c->npanels - 1;
     if (timed || c->row_reduce) return enqueue_sweep_kernels(c, in->model_index, in->n_fold, true); // (row-sharded mode: host round trips inside the sweep)
     const int pb = c->rng_pe ? c->rng_pb : 0, pe = c->rng_pe ? c->rng_pe : c->npanels;
+    if (c->pipeline) {
+        const int ngroups = (pe - pb + c->D - 1) / c->D;
+        c->upd_slot = ngroups & 1, c->upd_mbi = pb / c->D + ngroups - 1;
+    }
     const bool first = c->rng_pe ? c->rng_first : true, last = c->rng_pe ? c->rng_last : true;
     const bool env_alone = getenv("HB_CHAIN_ALONE") != nullptr; // (tools/chain_timeline.py sets it in the middle of a run)
     auto enqueue = [&]() {

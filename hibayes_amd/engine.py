@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import CtxParams, LaunchStats, SweepIn, SweepOut, SweepTiming, HB_MAX_FOLD, check, lib
+from ._lib import CtxParams, LaunchStats, SweepIn, SweepOut, SweepTiming, HB_MAX_FOLD, HB_ND, check, lib
 
 MODEL_INDEX = {"BayesRR": 1, "BayesA": 2, "BayesB": 3, "BayesBpi": 3, "BayesC": 4, "BayesCpi": 4,
                "BayesL": 5, "BayesR": 6}
@@ -105,6 +105,22 @@ class Context:
         kp = C.c_int32()
         check(self.L.hb_ctx_debug_get_pre(self.h, C.byref(kp), *[x.ctypes.data for x in out]))
         return tuple(x[:kp.value].copy() for x in out)
+
+    def mirrors(self):
+        """Debug read-out: the residual version the last executed update rows wrote and its mirrors, as a dict — slot, bound_index (h of
+        the bound mb[1 + h] behind the exponent; -1 before the first sweep), r (ld doubles, rows [n, ld) included), r32 (ld floats), rq (the
+        HB_ND x ld int8 digit planes) and vexp (both None unless precise = 2), mb (the npanels + 2 bounds on max |yadj|)."""
+        ld = self.ld
+        npan = (self.m + self.panel - 1) // self.panel
+        r, r32 = np.zeros(ld), np.zeros(ld, dtype=np.float32)
+        rq, mb = np.zeros((HB_ND, ld), dtype=np.int8), np.zeros(npan + 2)
+        slot, h, nd, ve = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        check(self.L.hb_ctx_debug_get_mirrors(self.h, C.byref(slot), C.byref(h), r.ctypes.data, r32.ctypes.data, C.byref(nd),
+                                              rq.ctypes.data, C.byref(ve), mb.ctypes.data))
+        if nd.value not in (0, HB_ND):
+            raise RuntimeError("hb_ctx_debug_get_mirrors: %d digit planes, this binding knows %d" % (nd.value, HB_ND))
+        return {"slot": slot.value, "bound_index": h.value, "r": r, "r32": r32, "rq": rq if nd.value else None,
+                "vexp": ve.value if nd.value else None, "mb": mb}
 
     def build_gram(self):
         s = C.c_double()
@@ -258,8 +274,9 @@ class Context:
         return a, b, c
 
     # ---- one marker sweep ----
-    def sweep(self, model, it, vare, varg=0.0, logpi=(0.0, 0.0), fold=(0.0, 0.0), vara_fold=None, s2varg_df=0.0,
-              dfvara=4.0, lam=0.0, lam2=0.0, count_pip=False, store=False):
+    @staticmethod
+    def _sweep_in(model, it, vare, varg=0.0, logpi=(0.0, 0.0), fold=(0.0, 0.0), vara_fold=None, s2varg_df=0.0,
+                  dfvara=4.0, lam=0.0, lam2=0.0, count_pip=False, store=False):
         si = SweepIn()
         si.model_index = MODEL_INDEX[model] if isinstance(model, str) else int(model)
         si.n_fold = len(logpi)
@@ -271,10 +288,28 @@ class Context:
             si.vara_fold[k] = (vara_fold[k] if vara_fold is not None else varg * si.fold[k])
         si.lambda_, si.lambda2 = lam, lam2
         si.count_pip, si.store = int(count_pip), int(store)
-        so = SweepOut()
-        check(self.L.hb_ctx_sweep(self.h, C.byref(si), C.byref(so)))
+        return si
+
+    @staticmethod
+    def _sweep_out(so):
         return {"sum_g2": so.sum_g2, "class_count": np.array(so.class_count[:]), "sum_vargL": so.sum_vargL,
                 "sum_r": so.sum_r, "sum_r2": so.sum_r2, "var_u": so.var_u, "n_events": so.n_events}
+
+    def sweep(self, model, it, vare, *a, **kw):
+        si, so = self._sweep_in(model, it, vare, *a, **kw), SweepOut()
+        check(self.L.hb_ctx_sweep(self.h, C.byref(si), C.byref(so)))
+        return self._sweep_out(so)
+
+    def sweep_range(self, block, nblocks, model, it, vare, *a, **kw):
+        """Enqueue block `block` of a sweep cut into `nblocks` ranges of whole mat-vec groups (hb_ctx_sweep_range; the arguments
+        of sweep() behind the two). sweep_end() after the last block fetches the sums."""
+        si = self._sweep_in(model, it, vare, *a, **kw)
+        check(self.L.hb_ctx_sweep_range(self.h, C.byref(si), int(block), int(nblocks)))
+
+    def sweep_end(self):
+        so = SweepOut()
+        check(self.L.hb_ctx_sweep_end(self.h, C.byref(so)))
+        return self._sweep_out(so)
 
     def time_matvec(self, reps=3):
         ms, nl, nc = C.c_double(), C.c_int32(), C.c_int32()

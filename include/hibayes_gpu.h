@@ -574,6 +574,16 @@ int hb_ctx_debug_inject_abort(hb_ctx *c, int32_t panel, int32_t times);
  * or BayesR's n_fold - 1 rounded up to 3 or 7; rows and columns beyond the model's are (+inf, 0, 0)). Synchronises the context's stream and
  * changes nothing; any of the pointers may be NULL. Fails before the first sweep. */
 int hb_ctx_debug_get_pre(hb_ctx *c, int32_t *kpad, double *thr, double *invv, double *sdz);
+/* Debug read-out for the kernel-level tests (tests/test_gpu_update.py): the residual version that the last executed update rows wrote, with
+ * its mirrors, as they lie on the device (ld = hb_ctx_ld() rows each, rows [n, ld) included). *slot: the version slot read (0 before the
+ * first sweep: the residual between sweeps, which every other writer of the residual keeps in that slot); *bound_index: h of the group
+ * (pipeline) or panel (per-panel kernels) whose moves those rows applied, so that mb[1 + h] is the bound their exponent came from (-1 before
+ * the first sweep); r: the slot's ld doubles; r32: its ld floats; *ndigits: the number of digit planes copied — 7 under precise = 2, else 0
+ * with rq and vexp left untouched; rq: ndigits x ld int8 digits, plane k at rq + k * ld, value = sum_k rq[k][i] 256^k = rint(r[i] 2^vexp);
+ * *vexp: the slot's exponent; mb: the npanels + 2 bounds on max |yadj| (mb[0]: at the start of the last range of panels enqueued, mb[1 + h]:
+ * after group or panel h). Synchronises the context's stream and changes nothing; any of the pointers may be NULL. */
+int hb_ctx_debug_get_mirrors(hb_ctx *c, int32_t *slot, int32_t *bound_index, double *r, float *r32, int32_t *ndigits, int8_t *rq,
+                             int32_t *vexp, double *mb);
 
 #ifdef __cplusplus
 }
