@@ -213,6 +213,7 @@ SYMBOLS = [
     # ldmat(): R/ldm.r:31-112, src/tXXmat.cpp:43-77 (BigStat), :100-206 (tXXmat_Geno), :504-626 (tXXmat_Chr)
     "hb_ldm_build", "hb_ldm_info", "hb_ldm_download_dense", "hb_ldm_download_csc", "hb_ldm_destroy",
     "hb_sbayes_run_ldm",  # ldmat() -> sbrm(), R/ldm.r:88 -> R/sbayes.r:213, from the handle's device copy
+    "hb_ldm_from_csc", "hb_sbayes_run_sparse",  # SBayesS(): src/SBayesS.cpp, from the handle's device CSC
 ]
 
 
@@ -246,6 +247,8 @@ def lib():
     L.hb_bayes_run.argtypes = [C.POINTER(BayesArgs), C.POINTER(BayesOut)]
     L.hb_sbayes_run.argtypes = [C.POINTER(SBayesArgs), C.POINTER(SBayesOut)]
     L.hb_sbayes_run_ldm.argtypes = [C.POINTER(SBayesArgs), C.c_void_p, C.POINTER(SBayesOut)]
+    L.hb_sbayes_run_sparse.argtypes = [C.POINTER(SBayesArgs), C.c_void_p, C.POINTER(SBayesOut)]
+    L.hb_ldm_from_csc.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
     L.hb_ldm_build.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_int64, C.POINTER(C.c_void_p)]
     L.hb_ldm_info.argtypes = [C.c_void_p, C.POINTER(LdmStats)]
     L.hb_ldm_download_dense.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]

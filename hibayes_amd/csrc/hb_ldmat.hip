@@ -491,13 +491,102 @@ int hb_ldm_device_dense(hb_ldm *l, const double **out)
     return HB_OK;
 }
 
+int hb_ldm_device_csc(hb_ldm *l, hb_ldm_csc *out)
+{
+    HB_HIP(hipSetDevice(l->device));
+    if (!l->d_cp) {
+        const int m = l->m;
+        const bool dense = l->kind == HB_LDM_KIND_DENSE;
+        std::vector<int64_t> cp(m + 1, 0), run(m, 0);
+        std::vector<int32_t> cnt(m, 0), runn(m, 0);
+        for (int j = 0; j < m; j++) {
+            int32_t c = 0;
+            if (dense) {
+                const double *col = l->h_dense + (size_t)j * m;
+                for (int r = 0; r < m; r++) c += col[r] != 0.0;
+            } else {
+                c = l->col_cnt[j];
+            }
+            // varediff counts what the matrix STORES (src/SBayesS.cpp:131-141): the genome-wide dense kind stores all m entries of a
+            // column (hb_ldm_stats.nnz = m * m), its exact zeros are left out of the CSC only because walking them changes nothing
+            cnt[j] = dense ? m : c;
+            cp[j + 1] = cp[j] + c;
+        }
+        const int64_t nnz = cp[m];
+        std::vector<int32_t> ri((size_t)std::max<int64_t>(nnz, 1));
+        std::vector<double> va((size_t)std::max<int64_t>(nnz, 1));
+        for (int j = 0; j < m; j++) {
+            int64_t p = cp[j];
+            if (dense) {
+                const double *col = l->h_dense + (size_t)j * m;
+                for (int r = 0; r < m; r++)
+                    if (col[r] != 0.0) {
+                        ri[p] = r;
+                        va[p++] = col[r];
+                    }
+            } else if (cnt[j]) {
+                std::memcpy(ri.data() + p, l->h_idx + l->col_off[j], sizeof(int32_t) * (size_t)l->col_cnt[j]);
+                std::memcpy(va.data() + p, l->h_val + l->col_off[j], sizeof(double) * (size_t)l->col_cnt[j]);
+            }
+        }
+        // per marker: its column's entries inside the rows of its own group; per group: the rows its columns touch
+        const int ng = (m + HB_LDM_GS - 1) / HB_LDM_GS;
+        l->grp_lo.assign(ng, 0);
+        l->grp_hi.assign(ng, 0);
+        for (int g = 0; g < ng; g++) {
+            const int g0 = g * HB_LDM_GS, g1 = std::min(m, g0 + HB_LDM_GS);
+            int32_t lo = m, hi = 0;
+            for (int j = g0; j < g1; j++) {
+                const int32_t *b = ri.data() + cp[j], *e = ri.data() + cp[j + 1];
+                const int32_t *a = std::lower_bound(b, e, (int32_t)g0), *z = std::lower_bound(a, e, (int32_t)g1);
+                run[j] = cp[j] + (a - b);
+                runn[j] = (int32_t)(z - a);
+                if (b != e) {
+                    lo = std::min(lo, *b);
+                    hi = std::max(hi, *(e - 1) + 1);
+                }
+            }
+            if (lo < hi) {
+                l->grp_lo[g] = lo;
+                l->grp_hi[g] = hi;
+            }
+        }
+        dev_bufs D;
+        int64_t *d_cp = nullptr, *d_run = nullptr;
+        int32_t *d_ri = nullptr, *d_cnt = nullptr, *d_runn = nullptr;
+        double *d_va = nullptr;
+        int rc;
+        if ((rc = D.get(&d_cp, m + 1)) || (rc = D.get(&d_run, m)) || (rc = D.get(&d_ri, ri.size())) || (rc = D.get(&d_cnt, m)) ||
+            (rc = D.get(&d_runn, m)) || (rc = D.get(&d_va, va.size())))
+            return rc;
+        HB_HIP(hipMemcpy(d_cp, cp.data(), sizeof(int64_t) * (m + 1), hipMemcpyHostToDevice));
+        HB_HIP(hipMemcpy(d_run, run.data(), sizeof(int64_t) * m, hipMemcpyHostToDevice));
+        HB_HIP(hipMemcpy(d_cnt, cnt.data(), sizeof(int32_t) * m, hipMemcpyHostToDevice));
+        HB_HIP(hipMemcpy(d_runn, runn.data(), sizeof(int32_t) * m, hipMemcpyHostToDevice));
+        HB_HIP(hipMemcpy(d_ri, ri.data(), sizeof(int32_t) * ri.size(), hipMemcpyHostToDevice));
+        HB_HIP(hipMemcpy(d_va, va.data(), sizeof(double) * va.size(), hipMemcpyHostToDevice));
+        D.p.clear(); // kept: the handle owns them from here
+        l->d_run = d_run;
+        l->d_ri = d_ri;
+        l->d_cnt = d_cnt;
+        l->d_runn = d_runn;
+        l->d_va = d_va;
+        l->csc_nnz = nnz;
+        l->d_cp = d_cp;
+    }
+    *out = hb_ldm_csc{l->csc_nnz, l->d_cp, l->d_run, l->d_ri, l->d_cnt, l->d_runn, l->d_va, l->grp_lo.data(), l->grp_hi.data()};
+    return HB_OK;
+}
+
 extern "C" {
 
 void hb_ldm_destroy(hb_ldm *l)
 {
     if (!l) return;
-    if (l->d_dense || l->h_dense || l->h_idx || l->h_val) (void)hipSetDevice(l->device);
+    if (l->d_dense || l->h_dense || l->h_idx || l->h_val || l->d_cp) (void)hipSetDevice(l->device);
     if (l->d_dense) (void)hipFree(l->d_dense);
+    for (void *q : {(void *)l->d_cp, (void *)l->d_ri, (void *)l->d_va, (void *)l->d_cnt, (void *)l->d_run, (void *)l->d_runn})
+        if (q) (void)hipFree(q);
     if (l->h_dense) (void)hipHostFree(l->h_dense);
     if (l->h_idx) (void)hipHostFree(l->h_idx);
     if (l->h_val) (void)hipHostFree(l->h_val);
@@ -531,6 +620,61 @@ int hb_ldm_build(hb_ctx *c, const int32_t *chr, int32_t has_chisq, double chisq,
         (void)hipStreamSynchronize(c->stream);
         hb_ldm_destroy(l);
         return rc;
+    }
+    *out = l;
+    return HB_OK;
+}
+
+int hb_ldm_from_csc(int32_t m, const int64_t *indptr, const int32_t *indices, const double *data, int32_t device, hb_ldm **out)
+{
+    if (!out) return hb_fail(HB_ERR_INVALID, "hb_ldm_from_csc: null argument");
+    *out = nullptr;
+    if (m < 1 || !indptr) return hb_fail(HB_ERR_INVALID, "hb_ldm_from_csc: null argument");
+    if (indptr[0] != 0) return hb_fail(HB_ERR_INVALID, "hb_ldm_from_csc: indptr must start at 0");
+    for (int j = 0; j < m; j++)
+        if (indptr[j + 1] < indptr[j] || indptr[j + 1] - indptr[j] > m) return hb_fail(HB_ERR_INVALID, "hb_ldm_from_csc: indptr must not decrease");
+    const int64_t nnz = indptr[m];
+    if (nnz && (!indices || !data)) return hb_fail(HB_ERR_INVALID, "hb_ldm_from_csc: null argument");
+    for (int j = 0; j < m; j++)
+        for (int64_t p = indptr[j]; p < indptr[j + 1]; p++) {
+            if (indices[p] < 0 || indices[p] >= m) return hb_fail(HB_ERR_INVALID, "hb_ldm_from_csc: row index out of range");
+            if (p > indptr[j] && indices[p] <= indices[p - 1])
+                return hb_fail(HB_ERR_INVALID, "hb_ldm_from_csc: row indices must be sorted and unique inside a column");
+        }
+    for (int j = 0; j < m; j++) // entry (r, j) needs its mirror (j, r) with the same bits
+        for (int64_t p = indptr[j]; p < indptr[j + 1]; p++) {
+            const int r = indices[p];
+            if (r == j) continue;
+            const int32_t *b = indices + indptr[r], *e = indices + indptr[r + 1];
+            const int32_t *it = std::lower_bound(b, e, (int32_t)j);
+            if (it == e || *it != j || std::memcmp(data + (it - indices), data + p, sizeof(double)) != 0)
+                return hb_fail(HB_ERR_INVALID, "hb_ldm_from_csc: the matrix must equal its transpose, in pattern and in value bits");
+        }
+    if (hb_device_count() <= 0) return hb_fail(HB_ERR_NO_DEVICE, "no HIP device available: the hibayes GPU engine has no CPU fallback");
+    if (device < 0 || device >= hb_device_count()) return hb_fail(HB_ERR_INVALID, "hb_ldm_from_csc: no such device");
+    HB_HIP(hipSetDevice(device));
+    hb_ldm *l = new hb_ldm();
+    l->device = device;
+    l->m = m;
+    l->kind = HB_LDM_KIND_SPARSE;
+    const int rc = host_reserve(l, std::max<int64_t>(nnz, 1));
+    if (rc) {
+        hb_ldm_destroy(l);
+        return rc;
+    }
+    if (nnz) {
+        std::memcpy(l->h_idx, indices, sizeof(int32_t) * (size_t)nnz);
+        std::memcpy(l->h_val, data, sizeof(double) * (size_t)nnz);
+    }
+    l->h_used = l->nnz = nnz;
+    l->col_off.assign(indptr, indptr + m);
+    l->col_cnt.resize(m);
+    l->diag.assign(m, 0.0);
+    for (int j = 0; j < m; j++) {
+        l->col_cnt[j] = (int32_t)(indptr[j + 1] - indptr[j]);
+        const int32_t *b = indices + indptr[j], *e = indices + indptr[j + 1];
+        const int32_t *it = std::lower_bound(b, e, (int32_t)j);
+        if (it != e && *it == j) l->diag[j] = data[it - indices];
     }
     *out = l;
     return HB_OK;

@@ -1,9 +1,13 @@
 // hb_sbayes.hip — host side of hb_sbayes_run(): SBayesD() of the reference (src/SBayesD.cpp:5-609) as validation, prior defaults,
 // the outer MCMC loop with its hyper-parameter draws and the posterior assembly; every m-long operation runs on the device
-// (hb_sbayes.hpp). SURVEY §8 f4.
+// (hb_sbayes.hpp). SURVEY §8 f4. hb_sbayes_run_sparse() is SBayesS() (src/SBayesS.cpp:21-640) through the same loop — the two
+// functions of the reference share their validation, priors, hyper-parameter draws, records and assembly line for line — with
+// the sweep of hb_sbayes_sparse.hip: what differs on the host is varediff (:131-141), vara and vary handed to the device every
+// sweep, the sum of squared effects taken from the end-of-sweep reduction, and one console line (:222).
 #include "hb_internal.hpp"
 #include "hb_ldm.hpp"
 #include "hb_rng.hpp"
+#include "hb_sbayes_sparse.hpp"
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -27,7 +31,9 @@ double arma_sum(const double *v, size_t n)
 }
 
 struct sb_run {
-    hb_sb_dev d;
+    hb_ss_dev s;
+    hb_sb_dev &d = s.b;
+    double *h_ex = nullptr;
     std::vector<void *> bufs;
     hipGraph_t graph = nullptr;
     hipGraphExec_t gexec = nullptr;
@@ -41,6 +47,7 @@ struct sb_run {
             if (p) (void)hipFree(p);
         if (h_acc) (void)hipHostFree(h_acc);
         if (h_in) (void)hipHostFree(h_in);
+        if (h_ex) (void)hipHostFree(h_ex);
         if (d.stream) (void)hipStreamDestroy(d.stream);
     }
     template <typename T>
@@ -54,8 +61,9 @@ struct sb_run {
 };
 } // namespace
 
-// hb_sbayes_run (H == nullptr: the matrix is args->ldm on the host) and hb_sbayes_run_ldm (the matrix is the handle's dense device copy)
-static int sbayes_run(const hb_sbayes_args *args, hb_ldm *H, hb_sbayes_out *o)
+// hb_sbayes_run (H == nullptr: the matrix is args->ldm on the host), hb_sbayes_run_ldm (the matrix is the handle's dense device copy)
+// and hb_sbayes_run_sparse (sparse: the handle's device CSC, SBayesS())
+static int sbayes_run(const hb_sbayes_args *args, hb_ldm *H, hb_sbayes_out *o, bool sparse = false)
 {
     if (!args || !o) return hb_fail(HB_ERR_INVALID, "hb_sbayes_run: null argument");
     const auto t_setup = clk::now();
@@ -191,7 +199,20 @@ static int sbayes_run(const hb_sbayes_args *args, hb_ldm *H, hb_sbayes_out *o)
     d.nw = nw;
     int rc;
 #define TRYA(x) do { rc = (x); if (rc) return rc; } while (0)
-    if (H) { // adopted, not owned: the sweep only reads it
+    if (sparse) { // adopted, not owned; nothing m x m exists on this route
+        TRYA(hb_ldm_device_csc(H, &R.s.csc));
+        TRYA(R.alloc(&R.s.varediff, d.m_pad));
+        TRYA(R.alloc(&R.s.varei, d.m_pad));
+        TRYA(R.alloc(&R.s.vxt, d.m_pad));
+        TRYA(R.alloc(&R.s.sgn, d.m_pad));
+        TRYA(R.alloc(&R.s.ex, 2));
+        TRYA(R.alloc(&R.s.gtab, SS_GS));
+        TRYA(R.alloc(&R.s.rd, 2));
+        TRYA(R.alloc(&R.s.cursor, d.m_pad));
+        HB_HIP(hipHostMalloc(reinterpret_cast<void **>(&R.h_ex), sizeof(double) * 2));
+        HB_HIP(hipMemcpyAsync(R.s.vxt, vx.data(), sizeof(double) * m, hipMemcpyHostToDevice, d.stream));
+        TRYA(hbk_ss_varediff(&R.s));
+    } else if (H) { // adopted, not owned: the sweep only reads it
         const double *dl = nullptr;
         TRYA(hb_ldm_device_dense(H, &dl));
         d.ldm = const_cast<double *>(dl);
@@ -241,7 +262,7 @@ static int sbayes_run(const hb_sbayes_args *args, hb_ldm *H, hb_sbayes_out *o)
     // ---- console, :190-246 ----
     line("Prior parameters:");
     line("    Model fitted at [%s]", model == "BayesRR" ? "Bayes Ridge Regression" : model.c_str());
-    line("    Population size %d", n);
+    line(sparse ? "    Number of observations %d" : "    Population size %d", n);
     line("    Number of markers %d", m);
     line("    Number of markers used for analysis %d", count_y);
     line("    Total number of iteration %d", niter);
@@ -284,17 +305,22 @@ static int sbayes_run(const hb_sbayes_args *args, hb_ldm *H, hb_sbayes_out *o)
         in.store = 0;
         *R.h_in = in;
         HB_HIP(hipMemcpyAsync(d.d_in, R.h_in, sizeof(hb_sweep_in), hipMemcpyHostToDevice, d.stream));
+        if (sparse) { // varei = varediff[i] * vara_ + vare_ (:285) and the truncation's bound (:388)
+            R.h_ex[0] = vara_;
+            R.h_ex[1] = vary;
+            HB_HIP(hipMemcpyAsync(R.s.ex, R.h_ex, sizeof(double) * 2, hipMemcpyHostToDevice, d.stream));
+        }
         if (!R.gexec) { // one sweep = 2 ceil(m / 512) + 3 launches: captured once, replayed every iteration
             HB_HIP(hipStreamSynchronize(d.stream));
             HB_HIP(hipStreamBeginCapture(d.stream, hipStreamCaptureModeRelaxed));
-            rc = hbk_sb_enqueue_sweep(&d, model_index, n_fold);
+            rc = sparse ? hbk_ss_enqueue_sweep(&R.s, model_index, n_fold) : hbk_sb_enqueue_sweep(&d, model_index, n_fold);
             hipError_t e = hipStreamEndCapture(d.stream, &R.graph);
             if (rc) return rc;
             if (e != hipSuccess) return hb_fail(HB_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
             HB_HIP(hipGraphInstantiate(&R.gexec, R.graph, nullptr, nullptr, 0));
         }
         HB_HIP(hipGraphLaunch(R.gexec, d.stream));
-        if (in.count_pip && nw) TRYA(hbk_sb_windows(&d));
+        if (in.count_pip && nw) TRYA(sparse ? hbk_ss_windows(&R.s) : hbk_sb_windows(&d));
         HB_HIP(hipMemcpyAsync(R.h_acc, d.acc, sizeof(double) * HB_ACC_N, hipMemcpyDeviceToHost, d.stream));
         HB_HIP(hipStreamSynchronize(d.stream));
         const double *acc = R.h_acc;
@@ -439,4 +465,10 @@ extern "C" int hb_sbayes_run_ldm(const hb_sbayes_args *args, hb_ldm *ldm, hb_sba
 {
     if (!ldm) return hb_fail(HB_ERR_INVALID, "hb_sbayes_run_ldm: null LD matrix handle");
     return sbayes_run(args, ldm, o);
+}
+
+extern "C" int hb_sbayes_run_sparse(const hb_sbayes_args *args, hb_ldm *ldm, hb_sbayes_out *o)
+{
+    if (!ldm) return hb_fail(HB_ERR_INVALID, "hb_sbayes_run_sparse: null LD matrix handle");
+    return sbayes_run(args, ldm, o, true);
 }

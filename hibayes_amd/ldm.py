@@ -13,13 +13,30 @@ KINDS = ("dense", "sparse", "block-dense", "block-sparse")
 
 class LDMatrix:
     """A finished LD matrix kept with the library (hb_ldm): SBayesD() and sbrm() take it as `ldm` and run from its dense device
-    copy, so .bed -> ldmat -> sbrm needs no host matrix. toarray() / tocsc() download it."""
+    copy, SBayesS() and sbrm(sparse_ld=True) from its device CSC, so .bed -> ldmat -> sbrm needs no host matrix. toarray() /
+    tocsc() download it."""
 
     def __init__(self, handle, device=0):
         self.L, self.h, self.device = lib(), handle, device
         st = self.info()
         self.shape = (st["m"], st["m"])
         self.kind, self.nnz = KINDS[st["kind"]], st["nnz"]
+
+    @classmethod
+    def from_scipy(cls, mat, device=0):
+        """A handle (kind "sparse") from a scipy sparse matrix, for SBayesS(): converted to CSC with sorted, summed indices and
+        handed to hb_ldm_from_csc, which refuses a matrix that does not equal its transpose in pattern and in value bits."""
+        import scipy.sparse as sp
+        if not sp.issparse(mat) or mat.ndim != 2 or mat.shape[0] != mat.shape[1]:
+            raise ValueError("from_scipy needs a square scipy sparse matrix")
+        A = sp.csc_matrix(mat, dtype=np.float64, copy=True)
+        A.sum_duplicates()
+        A.sort_indices()
+        indptr, indices = np.ascontiguousarray(A.indptr, dtype=np.int64), np.ascontiguousarray(A.indices, dtype=np.int32)
+        data = np.ascontiguousarray(A.data, dtype=np.float64)
+        h = C.c_void_p()
+        check(lib().hb_ldm_from_csc(A.shape[0], indptr.ctypes.data, indices.ctypes.data, data.ctypes.data, int(device), C.byref(h)))
+        return cls(h, device)
 
     def info(self):
         s = LdmStats()

@@ -1,6 +1,7 @@
-"""Host mirror of the reference's summary-level interface on a dense LD matrix: SBayesD() (src/SBayesD.cpp:5-26, the generated
-wrapper R/RcppExports.R:8-10) and the slice of sbrm() (R/sbayes.r:101-239) that leads to it. Everything computes on the device
-through hb_sbayes_run (include/hibayes_gpu.h); there is no CPU fallback."""
+"""Host mirror of the reference's summary-level interface: SBayesD() on a dense LD matrix (src/SBayesD.cpp:5-26, the generated
+wrapper R/RcppExports.R:8-10), SBayesS() on a sparse one (src/SBayesS.cpp:21-40) and the slice of sbrm() (R/sbayes.r:101-239)
+that leads to them. Everything computes on the device through hb_sbayes_run / hb_sbayes_run_ldm / hb_sbayes_run_sparse
+(include/hibayes_gpu.h); there is no CPU fallback."""
 import ctypes as C
 
 import numpy as np
@@ -14,6 +15,37 @@ def SBayesD(sumstat, ldm, model, Pi, niter=50000, nburn=20000, thin=5, fold=None
     """sumstat: m x 4 (MAF, BETA, SE, NMISS — what sbrm() keeps of the COJO file, R/sbayes.r:207; NaN = NA); ldm: m x m dense,
     or an LDMatrix (ldmat(..., keep_on_device=True)): the run then reads the handle's device copy (hb_sbayes_run_ldm; a sparse
     or per-chromosome handle as the dense matrix with zeros where it stores nothing) on the handle's device."""
+    return _run(False, sumstat, ldm, model, Pi, niter, nburn, thin, fold, windindx, vg, dfvg, s2vg, ve, dfve, s2ve, outfreq, threads,
+                verbose, seed, device, store_alpha, log)
+
+
+def SBayesS(sumstat, ldm, model, Pi, niter=50000, nburn=20000, thin=5, fold=None, windindx=None, vg=None, dfvg=None, s2vg=None,
+            ve=None, dfve=None, s2ve=None, outfreq=100, threads=0, verbose=True, *, seed=666666, device=0, store_alpha=True, log=None):
+    """SBayesS() of the reference (src/SBayesS.cpp): the sampler on a sparse LD matrix, SBayesD()'s arguments and results. ldm: an
+    LDMatrix of any kind (ldmat(..., chisq=..., keep_on_device=True)) or a scipy sparse matrix, which must equal its transpose and
+    is handed over as CSC with sorted indices (LDMatrix.from_scipy). The run walks the stored entries from the handle's device CSC
+    (hb_sbayes_run_sparse): no m x m array exists on either side. Not SBayesD() with zeros — every marker has its own residual
+    variance varediff[i] * Vg + Ve, varediff[i] the share of column i that is not stored, and BayesC / BayesCpi / BayesR effects
+    with g^2 * vx > var(y) are redrawn."""
+    own = None
+    if not isinstance(ldm, LDMatrix):
+        try:
+            import scipy.sparse as sp
+        except ImportError:
+            sp = None
+        if sp is None or not sp.issparse(ldm):
+            raise ValueError("SBayesS needs an LDMatrix or a scipy sparse ldm (a dense array goes to SBayesD)")
+        ldm = own = LDMatrix.from_scipy(ldm, device=device)
+    try:
+        return _run(True, sumstat, ldm, model, Pi, niter, nburn, thin, fold, windindx, vg, dfvg, s2vg, ve, dfve, s2ve, outfreq,
+                    threads, verbose, seed, device, store_alpha, log)
+    finally:
+        if own is not None:
+            own.close()
+
+
+def _run(sparse, sumstat, ldm, model, Pi, niter, nburn, thin, fold, windindx, vg, dfvg, s2vg, ve, dfve, s2ve, outfreq, threads,
+         verbose, seed, device, store_alpha, log):
     L = lib()
     ss = np.asfortranarray(sumstat, dtype=np.float64)
     handle = ldm if isinstance(ldm, LDMatrix) else None
@@ -69,7 +101,7 @@ def SBayesD(sumstat, ldm, model, Pi, niter=50000, nburn=20000, thin=5, fold=None
     o.s_pi = buf(mc, "pi", (pv.size, nrec))
     o.r_hat, o.g_last = buf(res, "r_hat", mm), buf(res, "g_last", mm)
     if handle is not None:
-        check(L.hb_sbayes_run_ldm(C.byref(a), handle._handle(), C.byref(o)))
+        check((L.hb_sbayes_run_sparse if sparse else L.hb_sbayes_run_ldm)(C.byref(a), handle._handle(), C.byref(o)))
     else:
         check(L.hb_sbayes_run(C.byref(a), C.byref(o)))
     for k in ("Vg", "Ve", "h2", "n_records", "nzct", "nw", "n", "count_y"):
@@ -81,18 +113,25 @@ def SBayesD(sumstat, ldm, model, Pi, niter=50000, nburn=20000, thin=5, fold=None
 
 
 def sbrm(sumstat, ldm, method="BayesB", map=None, Pi=None, fold=None, niter=None, nburn=None, thin=5, windsize=None, windnum=None,
-         windindx=None, vg=None, dfvg=None, s2vg=None, ve=None, dfve=None, s2ve=None, printfreq=100, seed=666666, threads=4, verbose=True, **kw):
-    """The dense-LD slice of sbrm() (R/sbayes.r:101-239): the ldm type check (:126-132), GWAS windows cut from `map` by windsize /
+         windindx=None, vg=None, dfvg=None, s2vg=None, ve=None, dfve=None, s2ve=None, printfreq=100, seed=666666, threads=4, verbose=True,
+         sparse_ld=False, **kw):
+    """sbrm() of the reference (R/sbayes.r:101-239): the ldm type check (:126-132), GWAS windows cut from `map` by windsize /
     windnum (:135-187; res["gwas"] then carries WIND / CHR / NUM / START / END / WPPA like the reference's data frame, :231-234),
-    defaults (:189-203), the column selection sumstat[, c(4, 5, 6, 8)] of the 8-column COJO table (:207), then SBayesD().
-    Sparse LD matrices (dgCMatrix -> SBayesS) and method = "CG" are outside the GPU path and refused."""
+    defaults (:189-203), the column selection sumstat[, c(4, 5, 6, 8)] of the 8-column COJO table (:207), then SBayesD() — or, with
+    sparse_ld=True and a scipy sparse `ldm` or an LDMatrix, SBayesS(), as :213 does for a dgCMatrix: .bed -> ldmat(chisq=...,
+    keep_on_device=True) -> sbrm(sparse_ld=True) with no dense matrix on either side. Without sparse_ld a scipy sparse `ldm` is
+    refused, and an LDMatrix runs through SBayesD() as the dense matrix. method = "CG" is outside the GPU path and refused."""
+    is_sparse = False
     try:
         import scipy.sparse as sp
-        if sp.issparse(ldm):
-            raise NotImplementedError("a sparse ldm (dgCMatrix: SBayesS, src/SBayesS.cpp) is outside the GPU path; pass the dense LD matrix")
+        is_sparse = sp.issparse(ldm)
     except ImportError:
         pass
-    if not (isinstance(ldm, (np.ndarray, LDMatrix)) or hasattr(ldm, "__array__")):
+    if is_sparse and not sparse_ld:
+        raise NotImplementedError("a sparse ldm (dgCMatrix: SBayesS, src/SBayesS.cpp) runs with sparse_ld=True; without it pass the dense LD matrix")
+    if sparse_ld and not (is_sparse or isinstance(ldm, LDMatrix)):
+        raise ValueError("sparse_ld=True needs a scipy sparse ldm or an LDMatrix")
+    if not (is_sparse or isinstance(ldm, (np.ndarray, LDMatrix)) or hasattr(ldm, "__array__")):
         raise ValueError("Unrecognized type of ldm.")
     if method == "CG":
         raise NotImplementedError("method = 'CG' (conjgt_den / conjgt_spa) is outside the GPU path")
@@ -137,7 +176,7 @@ def sbrm(sumstat, ldm, method="BayesB", map=None, Pi=None, fold=None, niter=None
     ss = np.asarray(sumstat, dtype=np.float64)
     if ss.ndim == 2 and ss.shape[1] >= 8:      # the COJO table (:207); a 4-column matrix is taken as MAF, BETA, SE, NMISS already
         ss = ss[:, [3, 4, 5, 7]]
-    res = SBayesD(ss, ldm, method, Pi, niter=niter, nburn=nburn, thin=thin, fold=fold, windindx=windindx, vg=vg, dfvg=dfvg, s2vg=s2vg,
+    res = (SBayesS if sparse_ld else SBayesD)(ss, ldm, method, Pi, niter=niter, nburn=nburn, thin=thin, fold=fold, windindx=windindx, vg=vg, dfvg=dfvg, s2vg=s2vg,
                   ve=ve, dfve=dfve, s2ve=s2ve, outfreq=printfreq, threads=threads, verbose=verbose, seed=seed, **kw)
     if windinfo is not None:
         res["gwas"] = dict(windinfo, WPPA=res["gwas"])

@@ -371,6 +371,21 @@ void hb_ldm_destroy(hb_ldm *ldm);
  * stored entries if the build kept none): ldmat() -> sbrm() (R/ldm.r:88 -> R/sbayes.r:213) with no host matrix in between. */
 int hb_sbayes_run_ldm(const hb_sbayes_args *args, hb_ldm *ldm, hb_sbayes_out *out);
 
+/* A handle (HB_LDM_KIND_SPARSE) from a host CSC matrix, e.g. a scipy csc_matrix or a dgCMatrix: indptr m + 1, indices and data
+ * indptr[m] long. Refused with HB_ERR_INVALID and a text: rows not sorted or not unique inside a column, an index outside
+ * [0, m), and a matrix that does not equal its transpose in pattern and in value bits. The reference's SBayesS() does not need
+ * symmetry; the sparse sweep here reads row j of the matrix as column j, and every LD matrix has it (hb_ldm_build's are
+ * symmetric by construction: each pair is computed once). Stored zeros are kept and count as entries, as in a dgCMatrix. */
+int hb_ldm_from_csc(int32_t m, const int64_t *indptr, const int32_t *indices, const double *data, int32_t device, hb_ldm **out);
+
+/* SBayesS() of the reference (src/SBayesS.cpp:21-40, sbrm() on a dgCMatrix, R/sbayes.r:128, :213): the summary-level sampler
+ * on a sparse LD matrix, from the handle's device CSC (any kind of handle; the genome-wide dense kind with its exact zeros
+ * dropped). It is not hb_sbayes_run_ldm with zeros: every marker has its own residual variance
+ * varediff[i] * vara + vare with varediff[i] = (m - nnz(column i)) / m (:131-141, :285), BayesC / BayesCpi / BayesR effects with
+ * g^2 * vx > vary are redrawn, at most 101 times (:388-398, :489-499), and a move walks the stored entries of its column only.
+ * Nothing m x m is allocated. args->ldm must be NULL; arguments, priors, records and results are hb_sbayes_run's. */
+int hb_sbayes_run_sparse(const hb_sbayes_args *args, hb_ldm *ldm, hb_sbayes_out *out);
+
 /* ====================================================================================
  * Fine-grained engine API.  hb_bayes_run() is built on it; the parity tests and bench.py
  * drive the device pieces through it one at a time.  A context owns all device state of
