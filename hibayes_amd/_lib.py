@@ -136,6 +136,24 @@ class SBayesOut(C.Structure):
     ]
 
 
+class CGArgs(C.Structure):
+    """hb_cg_args"""
+    _fields_ = [
+        ("m", C.c_int32), ("sumstat", C.c_void_p), ("ld_sumstat", C.c_int64), ("ldm", C.c_void_p), ("ld_ldm", C.c_int64),
+        ("lambda_", C.c_void_p), ("esp", C.c_double), ("outfreq", C.c_int32), ("verbose", C.c_int32), ("device", C.c_int32),
+        ("interrupt", INTERRUPT_FN), ("interrupt_user", C.c_void_p), ("log", LOG_FN), ("log_user", C.c_void_p),
+    ]
+
+
+class CGOut(C.Structure):
+    """hb_cg_out"""
+    _fields_ = [
+        ("vg", C.c_double), ("ve", C.c_double), ("n", C.c_int32), ("count_y", C.c_int32), ("iterations", C.c_int32),
+        ("converged", C.c_int32), ("err", C.c_double), ("g", C.c_void_p), ("err_hist", C.c_void_p),
+        ("setup_seconds", C.c_double), ("loop_seconds", C.c_double),
+    ]
+
+
 class LdmStats(C.Structure):
     """hb_ldm_stats"""
     _fields_ = [
@@ -214,6 +232,7 @@ SYMBOLS = [
     "hb_ldm_build", "hb_ldm_info", "hb_ldm_download_dense", "hb_ldm_download_csc", "hb_ldm_destroy",
     "hb_sbayes_run_ldm",  # ldmat() -> sbrm(), R/ldm.r:88 -> R/sbayes.r:213, from the handle's device copy
     "hb_ldm_from_csc", "hb_sbayes_run_sparse",  # SBayesS(): src/SBayesS.cpp, from the handle's device CSC
+    "hb_cg_run", "hb_cg_run_ldm", "hb_cg_run_sparse",  # conjgt_den / conjgt_spa: src/cg.cpp, CG() src/solver.cpp:54-115
 ]
 
 
@@ -248,6 +267,9 @@ def lib():
     L.hb_sbayes_run.argtypes = [C.POINTER(SBayesArgs), C.POINTER(SBayesOut)]
     L.hb_sbayes_run_ldm.argtypes = [C.POINTER(SBayesArgs), C.c_void_p, C.POINTER(SBayesOut)]
     L.hb_sbayes_run_sparse.argtypes = [C.POINTER(SBayesArgs), C.c_void_p, C.POINTER(SBayesOut)]
+    L.hb_cg_run.argtypes = [C.POINTER(CGArgs), C.POINTER(CGOut)]
+    L.hb_cg_run_ldm.argtypes = [C.POINTER(CGArgs), C.c_void_p, C.POINTER(CGOut)]
+    L.hb_cg_run_sparse.argtypes = [C.POINTER(CGArgs), C.c_void_p, C.POINTER(CGOut)]
     L.hb_ldm_from_csc.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
     L.hb_ldm_build.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_int64, C.POINTER(C.c_void_p)]
     L.hb_ldm_info.argtypes = [C.c_void_p, C.POINTER(LdmStats)]

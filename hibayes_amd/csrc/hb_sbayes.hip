@@ -5,6 +5,7 @@
 // the sweep of hb_sbayes_sparse.hip: what differs on the host is varediff (:131-141), vara and vary handed to the device every
 // sweep, the sum of squared effects taken from the end-of-sweep reduction, and one console line (:222).
 #include "hb_internal.hpp"
+#include "hb_armasum.hpp"
 #include "hb_ldm.hpp"
 #include "hb_rng.hpp"
 #include "hb_sbayes_sparse.hpp"
@@ -17,18 +18,6 @@
 
 namespace {
 using clk = std::chrono::steady_clock;
-
-double arma_sum(const double *v, size_t n)
-{
-    double a1 = 0.0, a2 = 0.0;
-    size_t j;
-    for (j = 1; j < n; j += 2) {
-        a1 += v[j - 1];
-        a2 += v[j];
-    }
-    if ((j - 1) < n) a1 += v[j - 1];
-    return a1 + a2;
-}
 
 struct sb_run {
     hb_ss_dev s;

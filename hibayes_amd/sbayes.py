@@ -120,7 +120,8 @@ def sbrm(sumstat, ldm, method="BayesB", map=None, Pi=None, fold=None, niter=None
     defaults (:189-203), the column selection sumstat[, c(4, 5, 6, 8)] of the 8-column COJO table (:207), then SBayesD() — or, with
     sparse_ld=True and a scipy sparse `ldm` or an LDMatrix, SBayesS(), as :213 does for a dgCMatrix: .bed -> ldmat(chisq=...,
     keep_on_device=True) -> sbrm(sparse_ld=True) with no dense matrix on either side. Without sparse_ld a scipy sparse `ldm` is
-    refused, and an LDMatrix runs through SBayesD() as the dense matrix. method = "CG" is outside the GPU path and refused."""
+    refused, and an LDMatrix runs through SBayesD() as the dense matrix. method = "CG" is refused here: its arm of sbrm() is
+    sbrm_cg() (hibayes_amd/cg.py)."""
     is_sparse = False
     try:
         import scipy.sparse as sp
@@ -134,7 +135,7 @@ def sbrm(sumstat, ldm, method="BayesB", map=None, Pi=None, fold=None, niter=None
     if not (is_sparse or isinstance(ldm, (np.ndarray, LDMatrix)) or hasattr(ldm, "__array__")):
         raise ValueError("Unrecognized type of ldm.")
     if method == "CG":
-        raise NotImplementedError("method = 'CG' (conjgt_den / conjgt_spa) is outside the GPU path")
+        raise NotImplementedError("method = 'CG' (conjgt_den / conjgt_spa) is not routed through sbrm(): call sbrm_cg()")
     windinfo = None
     if windsize is not None or windnum is not None:
         if method in ("BayesA", "BayesRR", "BayesL"):

@@ -386,6 +386,52 @@ int hb_ldm_from_csc(int32_t m, const int64_t *indptr, const int32_t *indices, co
  * Nothing m x m is allocated. args->ldm must be NULL; arguments, priors, records and results are hb_sbayes_run's. */
 int hb_sbayes_run_sparse(const hb_sbayes_args *args, hb_ldm *ldm, hb_sbayes_out *out);
 
+/* ------------------------------------------------------------------------------------
+ * sbrm()'s method = "CG" (R/sbayes.r:217-229): the conjugate-gradient ridge solve (V + diag(lambda)) g = b on the LD matrix,
+ * replaces conjgt_den / conjgt_spa (reference src/cg.cpp:4-129) and CG() (src/solver.cpp:54-115). Set-up, exception texts and
+ * console lines are the reference's; the loop runs on the device (hb_cg.hip): an fp64 symmetric mat-vec and two vector kernels
+ * per iteration, stopped by a device word the host reads once per chunk of min(outfreq, 64) iterations, so g is exactly the
+ * state at the reference's `break`. Every sum is formed in one fixed order: two runs agree bit for bit. The order of summation
+ * is not the reference's BLAS's, which is unpinned there too.
+ * ------------------------------------------------------------------------------------ */
+typedef struct hb_cg_args {
+    int32_t m;               /* ldm.n_rows == sumstat.n_rows (src/cg.cpp:15, :79)                          */
+    const double *sumstat;   /* m x 4 column-major: MAF, BETA, SE, NMISS (R/sbayes.r:207); NaN = NA. A NaN BETA is not
+                                filtered: it propagates, as in the reference                               */
+    int64_t ld_sumstat;      /* leading dimension (>= m)                                                   */
+    const double *ldm;       /* hb_cg_run: m x m column-major, must equal its transpose in value bits; NULL for the handle forms */
+    int64_t ld_ldm;
+    const double *lambda;    /* Nullable<NumericVector> lambda (:7, :71): NULL or m values                 */
+    double esp;              /* (:8) default 1e-6 */
+    int32_t outfreq, verbose; /* (:9-10) */
+    /* ---- additions without a reference counterpart ---- */
+    int32_t device;
+    hb_interrupt_fn interrupt; /* polled once per chunk of iterations */
+    void *interrupt_user;
+    hb_log_fn log;
+    void *log_user;
+} hb_cg_args;
+
+typedef struct hb_cg_out {
+    double vg, ve;           /* src/cg.cpp:52-53, :115-116 */
+    int32_t n;               /* (int) mean of the finite NMISS (:13) */
+    int32_t count_y;         /* markers whose SE is not NA (:35) */
+    int32_t iterations;      /* passes of CG()'s loop: i + 1 at its `break`, m without one */
+    int32_t converged;       /* err < esp (src/solver.cpp:109) */
+    double err;              /* err of the last pass */
+    double *g;               /* m, caller-allocated */
+    double *err_hist;        /* m or NULL: err of pass i, zero from `iterations` on */
+    double setup_seconds, loop_seconds;
+} hb_cg_out;
+
+/* conjgt_den (src/cg.cpp:68-129) on a host dense matrix. A matrix that differs from its transpose is refused with
+ * HB_ERR_INVALID and a text that names the first differing pair (checked on the device, about one iteration's cost). */
+int hb_cg_run(const hb_cg_args *args, hb_cg_out *out);
+/* conjgt_den (src/cg.cpp:68-129) with args->ldm == NULL, on the handle's dense device copy: ldmat() -> CG with no host matrix. */
+int hb_cg_run_ldm(const hb_cg_args *args, hb_ldm *ldm, hb_cg_out *out);
+/* conjgt_spa (src/cg.cpp:4-65) with args->ldm == NULL, on the handle's device CSC; nothing m x m is allocated. */
+int hb_cg_run_sparse(const hb_cg_args *args, hb_ldm *ldm, hb_cg_out *out);
+
 /* ====================================================================================
  * Fine-grained engine API.  hb_bayes_run() is built on it; the parity tests and bench.py
  * drive the device pieces through it one at a time.  A context owns all device state of
