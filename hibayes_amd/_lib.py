@@ -111,6 +111,14 @@ class BayesOut(C.Structure):
     ]
 
 
+class PolyOut(C.Structure):
+    """hb_poly_out: what BSLMM's polygenic block adds to the result"""
+    _fields_ = [
+        ("Va", C.c_double), ("Vb", C.c_double), ("Va_sd", C.c_double), ("Vb_sd", C.c_double),
+        ("s_Va", C.c_void_p), ("s_Vb", C.c_void_p), ("k_mean", C.c_void_p), ("ghat", C.c_void_p),
+    ]
+
+
 class SBayesArgs(C.Structure):
     _fields_ = [
         ("m", C.c_int32), ("sumstat", C.c_void_p), ("ld_sumstat", C.c_int64), ("ldm", C.c_void_p), ("ld_ldm", C.c_int64),
@@ -233,6 +241,9 @@ SYMBOLS = [
     "hb_sbayes_run_ldm",  # ldmat() -> sbrm(), R/ldm.r:88 -> R/sbayes.r:213, from the handle's device copy
     "hb_ldm_from_csc", "hb_sbayes_run_sparse",  # SBayesS(): src/SBayesS.cpp, from the handle's device CSC
     "hb_cg_run", "hb_cg_run_ldm", "hb_cg_run_sparse",  # conjgt_den / conjgt_spa: src/cg.cpp, CG() src/solver.cpp:54-115
+    # BSLMM: make_grm() src/rm.cpp:5-53, the polygenic block src/Bayes.cpp:518-552
+    "hb_grm_build", "hb_grm_free", "hb_ctx_poly_setup", "hb_ctx_poly_step", "hb_ctx_poly_state", "hb_ctx_poly_debug_get",
+    "hb_bayes_run_poly", "hb_run_poly",
 ]
 
 
@@ -348,6 +359,15 @@ def lib():
     L.hb_run_ctx.restype = vp
     L.hb_run_finish.argtypes = [vp, C.POINTER(BayesOut)]
     L.hb_run_destroy.argtypes = [vp]
+    L.hb_bayes_run_poly.argtypes = [C.POINTER(BayesArgs), C.POINTER(BayesOut), C.POINTER(PolyOut)]
+    L.hb_run_poly.argtypes = [vp, C.POINTER(PolyOut)]
+    L.hb_grm_build.argtypes = [vp, dbl, i32, vp, C.POINTER(vp)]
+    L.hb_grm_free.argtypes = [vp]
+    L.hb_grm_free.restype = None
+    L.hb_ctx_poly_setup.argtypes = [vp, vp, vp, i64, i32]
+    L.hb_ctx_poly_step.argtypes = [vp, dbl, dbl, C.c_uint64, i64, dbl, dbl]
+    L.hb_ctx_poly_state.argtypes = [vp, vp, C.POINTER(dbl), C.POINTER(dbl), C.POINTER(i32)]
+    L.hb_ctx_poly_debug_get.argtypes = [vp, vp, vp, vp, vp]
     L.hb_run_destroy.restype = None
     _lib = L
     return L

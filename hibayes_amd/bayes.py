@@ -15,7 +15,7 @@ import re
 import numpy as np
 
 from . import _lib
-from ._lib import BayesArgs, BayesOut, HibayesError, check, lib
+from ._lib import BayesArgs, BayesOut, HibayesError, PolyOut, check, lib
 
 METHODS = ("BayesCpi", "BayesA", "BayesL", "BSLMM", "BayesR", "BayesB", "BayesC", "BayesBpi", "BayesRR")
 
@@ -44,6 +44,9 @@ def Bayes(y, X, model, Pi, Kival=None, Ki=None, C_=None, R=None, fold=None, nite
     The chain is the same bit for bit; the result's "resident_bits" reports what ran.
     `warm` (a dict mu / vare / varg / pi / lambda2 / vargL, or a _lib.WarmState) with `g_init` continues a chain from a reported
     state instead of the prior defaults (hb_warm_state, include/hibayes_gpu.h).
+    `Kival` / `Ki` (model "BSLMM"): the n eigenvalues and n x n eigenvectors of the relationship matrix, make_grm(eigen=True). The result
+    then also holds Va, Vb, MCMCsamples["Va"] / ["Vb"], k (the mean polygenic vector) and ghat (its back-projection onto the markers,
+    already part of alpha) — extensions: the reference only prints Va and Vb.
     """
     if C is not None and C_ is None:
         C_ = C
@@ -79,10 +82,21 @@ def Bayes(y, X, model, Pi, Kival=None, Ki=None, C_=None, R=None, fold=None, nite
     a.model = str(model).encode()
     Pi = _f64(Pi).ravel()
     a.Pi, a.n_pi = Pi.ctypes.data, Pi.size
-    if Kival is not None:
-        Kival = _f64(Kival); a.Kival = Kival.ctypes.data
     if Ki is not None:
-        Ki = _f64(Ki); a.Ki = Ki.ctypes.data
+        Ki = np.asarray(Ki)
+        if Ki.ndim != 2 or Ki.shape[0] != Ki.shape[1]:
+            raise HibayesError(1, "variance-covariance matrix should be in square.")
+        if Ki.shape[0] != n:
+            raise HibayesError(1, "Number of individuals not equals.")
+        Ki = np.asfortranarray(Ki, dtype=np.float64)
+        a.Ki = Ki.ctypes.data
+    if Kival is not None:
+        Kival = _f64(Kival).ravel()
+        if Ki is not None and Kival.size != n:
+            raise HibayesError(1, "Kival should hold one eigenvalue per individual.")
+        a.Kival = Kival.ctypes.data
+    # (a context prepared by Context.poly_setup carries the pair itself; the library refuses BSLMM on one that is not)
+    has_poly = (Ki is not None and Kival is not None) or (model == "BSLMM" and ctx is not None and Ki is None and Kival is None)
     nc = 0
     if C_ is not None:
         Cm = np.asfortranarray(np.asarray(C_, dtype=np.float64).reshape(n, -1, order="F"))
@@ -185,7 +199,12 @@ def Bayes(y, X, model, Pi, Kival=None, Ki=None, C_=None, R=None, fold=None, nite
     if model == "BayesL":
         o.vargL_last = buf("vargL_last", m)
 
-    check(L.hb_bayes_run(ct.byref(a), ct.byref(o)))
+    if has_poly:
+        po = PolyOut()
+        po.s_Va, po.s_Vb, po.k_mean, po.ghat = buf("s_Va", nrec), buf("s_Vb", nrec), buf("k_mean", n), buf("ghat", m)
+        check(L.hb_bayes_run_poly(ct.byref(a), ct.byref(o), ct.byref(po)))
+    else:
+        check(L.hb_bayes_run(ct.byref(a), ct.byref(o)))
 
     res = {}
     mc = {}
@@ -197,6 +216,10 @@ def Bayes(y, X, model, Pi, Kival=None, Ki=None, C_=None, R=None, fold=None, nite
                                     bufs["s_h2"].reshape(1, -1))
     res["mu"] = o.mu
     mc["mu"] = bufs["s_mu"].reshape(1, -1)
+    if has_poly:
+        res["Va"], res["Vb"], res["Va_sd"], res["Vb_sd"] = po.Va, po.Vb, po.Va_sd, po.Vb_sd
+        mc["Va"], mc["Vb"] = bufs["s_Va"].reshape(1, -1), bufs["s_Vb"].reshape(1, -1)
+        res["k"], res["ghat"] = bufs["k_mean"], bufs["ghat"]
     if nc:
         res["beta"] = bufs["beta"]
         mc["beta"] = bufs["s_beta"]
@@ -336,7 +359,7 @@ def ibrm(formula, data=None, M=None, M_id=None, method="BayesCpi", map=None, Pi=
          niter=None, nburn=None, thin=5, windsize=None, windnum=None, dfvr=None, s2vr=None, vg=None,
          dfvg=None, s2vg=None, ve=None, dfve=None, s2ve=None, printfreq=100, seed=666666,
          threads=4, verbose=True, *, windindx=None, device=0, panel=0, precise=2,
-         store_alpha=True, comm=None, m_global=None, m_offset=0, gebv_samples=None):
+         store_alpha=True, comm=None, m_global=None, m_offset=0, gebv_samples=None, lambda_=0.0):
     """Mirror of ibrm() (reference R/bayes.r:121-320). `formula` is a string such as
     "T1 ~ 1" or "T1 ~ season + bwt + (1 | loc) + (1 | dam)"; `data` a dict of columns or a
     pandas DataFrame whose first column holds the individual ids; `M` the n_all x m genotype
@@ -345,7 +368,9 @@ def ibrm(formula, data=None, M=None, M_id=None, method="BayesCpi", map=None, Pi=
     m_global markers (hibayes_amd.dist.shard_range); `map` / `windindx` likewise cover the local markers only, and the GEBV
     partial products of the shards are summed over the ranks.
     `gebv_samples` (default: store_alpha): also return MCMCsamples["g"] = M %*% MCMCsamples$alpha (n_all x n_records,
-    R/bayes.r:303-305), computed on the device."""
+    R/bayes.r:303-305), computed on the device.
+    `lambda_` (the reference's `lambda`, R/bayes.r:144): method "BSLMM" only — added to the diagonal of the relationship matrix of the
+    individuals in the fit before its eigen-decomposition (make_grm(M[rows], lambda, eigen = TRUE), :292-294)."""
     if data is None:
         raise ValueError("no data assigned.")
     if M is None:
@@ -432,7 +457,11 @@ def ibrm(formula, data=None, M=None, M_id=None, method="BayesCpi", map=None, Pi=
             windindx = cutwind_by_bp(chrom, bp, windsize)
     y = np.array([float(cols[lhs][i]) for i in rows])
     Mfit = M[rows, :]
-    res = Bayes(y=y, X=Mfit, model=method, Pi=Pi, fold=fold, C_=Xfix, R=R, niter=niter, nburn=nburn,
+    Kival = Ki = None
+    if method == "BSLMM":  # R/bayes.r:292-294
+        from .grm import make_grm
+        Kival, Ki = make_grm(Mfit, lambda_, eigen=True, verbose=verbose, device=device)
+    res = Bayes(y=y, X=Mfit, model=method, Pi=Pi, Kival=Kival, Ki=Ki, fold=fold, C_=Xfix, R=R, niter=niter, nburn=nburn,
                 thin=thin, windindx=windindx, dfvr=dfvr, s2vr=s2vr, vg=vg, dfvg=dfvg, s2vg=s2vg, ve=ve,
                 dfve=dfve, s2ve=s2ve, outfreq=printfreq, threads=threads, verbose=verbose, seed=seed,
                 device=device, panel=panel, precise=precise, store_alpha=store_alpha, comm=comm,

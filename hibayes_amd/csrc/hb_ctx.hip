@@ -326,6 +326,7 @@ void hb_ctx_destroy(hb_ctx *c)
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     blocks_free(c);
+    hb_poly_free(c);
     if (c->h_acc) (void)hipHostFree(c->h_acc);
     if (c->h_in) (void)hipHostFree(c->h_in);
     if (c->h_flags) (void)hipHostFree(c->h_flags);
@@ -858,6 +859,10 @@ static int fetch_acc(hb_ctx *c)
     HB_HIP(hipMemcpyAsync(c->h_acc, c->acc, sizeof(double) * HB_ACC_N, hipMemcpyDeviceToHost, c->stream));
     HB_HIP(hipMemcpyAsync(c->h_flags, c->flags, 256, hipMemcpyDeviceToHost, c->stream));
     if (c->blk_n) HB_HIP(hipMemcpyAsync(c->h_blk, c->blk, sizeof(double) * c->blk_n, hipMemcpyDeviceToHost, c->stream));
+    if (c->poly) { // (the polygenic block's vb, q and flag come back the same way)
+        const int prc = hb_poly_fetch_enqueue(c);
+        if (prc) return prc;
+    }
     HB_HIP(hipStreamSynchronize(c->stream));
     c->aborted = false;
     if (getenv("HB_DEBUG_STARTS") && c->h_flags[13]) { // (development aid: how long after the dense chain its fold workgroups started)

@@ -171,6 +171,8 @@ struct hb_ctx {
     hb_sweep_timing timing{};
     std::vector<hipEvent_t> ev_pool;
 
+    struct hb_poly *poly = nullptr; // BSLMM's polygenic block (hb_ctx_poly_setup; hb_grm.hip owns it)
+
     // ---- an aborted sweep is replayed ----
     // Every wait of the persistent pipeline is bounded; a waiter that gives up raises the abort flag, all kernels of the sweep
     // leave, and fetch_acc() reports HB_ERR_ABORTED. The state a sweep changes (effects, residual, u, the posterior counters) is
@@ -206,6 +208,13 @@ extern "C" int hb_ctx_sweep_begin(hb_ctx *c, const hb_sweep_in *in);
 extern "C" int hb_ctx_sweep_end(hb_ctx *c, hb_sweep_out *out);
 int hb_comm_allreduce_f64(hb_comm *c, double *buf, size_t count, hipStream_t st);
 int hb_build_gram_impl(hb_ctx *c);
+// the polygenic block (hb_grm.hip)
+void hb_poly_free(hb_ctx *c);
+int hb_poly_fetch_enqueue(hb_ctx *c);                 // vb, q, flag -> the pinned mirror, on the context's stream (rides on fetch_acc)
+const double *hb_poly_host_state(const hb_ctx *c);    // that mirror: [0] vb, [1] q, [2] flag; NULL without a block
+int hb_poly_reset(hb_ctx *c);                         // k = 0, no records: a run starts (:228-230)
+int hbk_poly_accumulate(hb_ctx *c);                   // k_sum += k
+int hbk_poly_backproject(hb_ctx *c, double sumvx, int count, double *k_mean, double *v);
 int hb_build_gcert(hb_ctx *c);
 
 // device buffers of one summary-level run (hb_sbayes.hip owns them; the kernels are in hb_sbayes.hpp)

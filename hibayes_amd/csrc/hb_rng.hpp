@@ -14,6 +14,8 @@
 //     purpose 3, synthetic genotypes
 //     purpose 4, the sparse summary-level sampler's truncation (src/SBayesS.cpp:388-398, :489-499): blk = marker * 128 + k is the
 //         normal of redraw k = 1 .. 101 of that marker in sweep `iter` (hb_sbayes_sparse.hip)
+//     purpose 5, BSLMM's polygenic block (src/Bayes.cpp:535, randn(nk)): blk = j is the normal of eigenvector j in iteration `iter`
+//         (hb_grm.hip)
 // The reference draws the same quantities from R's global Mersenne-Twister (src/stats.cpp:3-24).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -25,6 +27,7 @@
 #define HB_PURPOSE_HOST 2ull
 #define HB_PURPOSE_DATA 3ull
 #define HB_PURPOSE_REDRAW 4ull
+#define HB_PURPOSE_POLY 5ull
 #define HB_BLK_PER_MARKER 64ull
 
 __host__ __device__ inline uint4 hb_block(uint64_t seed, uint64_t sub, uint64_t blk)

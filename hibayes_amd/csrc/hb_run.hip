@@ -5,7 +5,8 @@
 // (:479-516), the hyper-parameter draws after the marker sweep (:603, :666-669, :710-716, :738-741,
 // :803-814, :819-823), the thinned store (:848-882) and the posterior assembly (:919-1040).
 // What runs on the device: everything that touches an n- or m-long vector (hb_kernels.hip).
-// BSLMM (nk) and the single-step epsilon block (ne) are refused with HB_ERR_UNSUPPORTED.
+// BSLMM's polygenic block (nk, :518-552) runs on the device too (hb_grm.hip) when Kival / Ki are given; the single-step epsilon
+// block (ne) is refused with HB_ERR_UNSUPPORTED.
 //
 // hb_bayes_run() == hb_run_create() + hb_run_step(niter) + hb_run_finish(); bench.py drives the
 // three separately so that exactly K iterations sit between its barriers.
@@ -109,6 +110,10 @@ struct hb_run {
     // MCMC sample stores kept inside the run (copied out by finish)
     std::vector<double> zb_, zl_, ch_; // this iteration's pre-drawn deviates for the covariate / random-effect blocks
     std::vector<double> s_mu, s_Vg, s_Ve, s_h2, s_pi, s_beta, s_Vr, s_r, s_alpha;
+    // ---- BSLMM's polygenic block (:518-552): the state lives on the context (hb_ctx_poly_*), the records here ----
+    bool poly = false, poly_finished = false;
+    double va = 0, vb = 0;     // :715, :550
+    std::vector<double> s_Va, s_Vb, k_mean, ghat;
 
     ~hb_run()
     {
@@ -341,7 +346,10 @@ int hb_run::take_args()
     }
     if ((int)fold_.size() != n_pi) return hb_fail(HB_ERR_INVALID, "length of Pi and fold not equals.");
     n_fold = (int)fold_.size();
-    if (a.Ki || a.Kival || model == "BSLMM") return hb_fail(HB_ERR_UNSUPPORTED, "BSLMM (Ki/Kival) is not part of the GPU path");
+    // BSLMM runs with both Kival and Ki, or on a context prepared by hb_ctx_poly_setup; anything else about them keeps the refusal (and its
+    // text, which tests pin) from before the block existed
+    poly = model == "BSLMM" && ((a.Ki && a.Kival) || (!a.Ki && !a.Kival && a.ctx && a.ctx->poly));
+    if (!poly && (a.Ki || a.Kival || model == "BSLMM")) return hb_fail(HB_ERR_UNSUPPORTED, "BSLMM (Ki/Kival) is not part of the GPU path");
     if (a.epsl_index || a.epsl_Gi || a.epsl_y_J)
         return hb_fail(HB_ERR_UNSUPPORTED, "the single-step epsilon block is not part of the GPU path");
 
@@ -364,6 +372,10 @@ int hb_run::take_args()
     }
     if (a.genotype_bits != 0 && a.genotype_bits != 8 && a.genotype_bits != 2)
         return hb_fail(HB_ERR_INVALID, "hb_bayes_run: genotype_bits must be 0 (auto), 8 or 2");
+    if (poly && (sharded || world > 1))
+        return hb_fail(HB_ERR_UNSUPPORTED, "BSLMM: the polygenic block is not sharded — it runs on one GPU only (comm / world > 1)");
+    if (poly && rowmode) return hb_fail(HB_ERR_UNSUPPORTED, "BSLMM: the polygenic block is not available with shard_rows");
+    if (poly && a.warm) return hb_fail(HB_ERR_UNSUPPORTED, "BSLMM: a warm start (hb_warm_state) does not carry the polygenic state (k, vb)");
     sync_blocks = std::max(1, std::min(64, (int)a.sync_blocks));
     m_global = (!rowmode && (world > 1 || a.m_global > 0)) ? a.m_global : m;
     if (!rowmode && world > 1 && ((!a.allreduce && !a.comm) || m_global < m))
@@ -546,6 +558,11 @@ int hb_run::configure_device()
     a.X_i8 = nullptr;
     a.X_f64 = nullptr;
     HB_HIP(hipSetDevice(c->device));
+    if (poly && a.Ki) { // nk = n: K is read as n x n (:222)
+        rc = hb_ctx_poly_setup(c, a.Kival, a.Ki, n, 0);
+        if (rc) return rc;
+    }
+    a.Ki = a.Kival = nullptr; // consumed
 
     rc = open_exchange();
     if (!rc) rc = marker_statistics();
@@ -804,6 +821,12 @@ int hb_run::start_chain()
     s_Vr.assign((size_t)n_records * nr, 0.0);
     s_r.assign((size_t)n_records * n_levels, 0.0);
     if (a.store_alpha) s_alpha.assign((size_t)n_records * m, 0.0);
+    if (poly) {
+        rc = hb_poly_reset(c); // k = 0 (:228-230)
+        if (rc) return rc;
+        s_Va.assign(n_records, 0.0);
+        s_Vb.assign(n_records, 0.0);
+    }
     return HB_OK;
 }
 
@@ -840,6 +863,14 @@ int hb_run::step()
             ch_[t] = hs.chisq(nlev[t] + dfr);
         }
         rc = hb_ctx_blocks_step(c, vare_, zb_.data(), zl_.data(), ch_.data(), dfr, s2r);
+        if (rc) return rc;
+    }
+    // BSLMM's polygenic block (:518-552), enqueued like the blocks above: its normals are drawn on the device, its chisq (:547) here, at the
+    // reference's place in the host stream; vb and the check of :533 come back with the sweep's fetch. Before the snapshot below: a replayed
+    // sweep restarts from the residual this block left.
+    if (poly) {
+        const double chis = hs.chisq(dfvara_ + (double)n);
+        rc = hb_ctx_poly_step(c, vare_, iter == 0 ? vara_ : -1.0, a.seed, iter, chis, s2vara_ * dfvara_); // (vbtmp = vara_, :333)
         if (rc) return rc;
     }
 
@@ -982,6 +1013,13 @@ int hb_run::step()
         std::copy(h + nc + n_levels + nr, h + nc + n_levels + 2 * nr, vr.begin());
     }
 
+    if (poly) {
+        const double *ps = hb_poly_host_state(c);
+        if (ps[2] != 0.0)
+            return hb_fail(HB_ERR_INVALID, "matrix is not positive definite, try to specify parameter 'lambda' with a small value, eg: 0.001 or bigger"); // :533
+        vb = ps[0];
+    }
+
     // hyper-parameters after the sweep
     auto draw_pi = [&]() { // rdirichlet_sample, src/stats.cpp:69-76
         std::vector<double> xn(n_fold);
@@ -1005,6 +1043,7 @@ int hb_run::step()
         fold_snp_num[0] = (double)m_global - nvar0 - fold_snp_num[1];
         NnzSnp = (long long)fold_snp_num[1];
         varg = (so.sum_g2 + s2varg_ * dfvara_) / hs.chisq(dfvara_ + (double)NnzSnp);
+        if (poly) va = varg; // :715
         if (!fixpi) draw_pi();
         break;
     case 5: { // :738-741
@@ -1043,6 +1082,12 @@ int hb_run::step()
             }
         s_Vg[count] = vara_;
         s_Ve[count] = vare_;
+        if (poly) { // :854-858
+            s_Va[count] = va;
+            s_Vb[count] = vb;
+            rc = hbk_poly_accumulate(c);
+            if (rc) return rc;
+        }
         vara_sum += vara_;
         vare_sum += vare_;
         if (a.store_alpha) {
@@ -1080,6 +1125,7 @@ int hb_run::step()
         for (int j = 0; j < n_fold && off < sizeof(pis) - 16; j++) off += snprintf(pis + off, sizeof(pis) - off, "%.4f ", pc[j]);
         char lam[32] = {0};
         if (model == "BayesL") snprintf(lam, sizeof(lam), "%.4f ", lambda);
+        if (poly) snprintf(lam, sizeof(lam), "%.4f %.4f ", va, vb); // :901
         line(" %d %lld %s%s%.4f %.4f %.4f %02dh%02dm%02ds", iter + 1, NnzSnp, pis, lam, vara_, vare_, vara_ / vt, tt / 3600,
              tt % 3600 / 60, tt % 3600 % 60);
     }
@@ -1116,6 +1162,27 @@ int hb_run::finish(hb_bayes_out *o)
         const double mean = asum[i] / Rn;
         if (o->alpha_sd) o->alpha_sd[i] = n_records > 1 ? std::sqrt(std::max(0.0, (asq[i] - Rn * mean * mean) / (Rn - 1))) : 0.0;
         asum[i] = mean;
+    }
+    if (poly) { // :955-964: the polygenic vector's back-projection onto the markers joins alpha and every stored alpha column
+        if (!poly_finished) {
+            std::vector<double> v(n), r_keep(n);
+            k_mean.assign(n, 0.0);
+            ghat.assign(m, 0.0);
+            rc = hbk_poly_backproject(c, sumvx, count, k_mean.data(), v.data());
+            if (rc) return rc;
+            // X'v through the panel mat-vec with v in the residual's place (the chain is over; the residual is put back)
+            rc = hb_ctx_get_residual(c, r_keep.data(), nullptr);
+            if (!rc) rc = hb_ctx_set_residual(c, v.data(), nullptr);
+            if (!rc) rc = hb_ctx_dot(c, 0, m, ghat.data());
+            if (!rc) rc = hb_ctx_set_residual(c, r_keep.data(), nullptr);
+            if (rc) return rc;
+            const double gm = arma_sum(ghat.data(), ghat.size()) / (double)m;
+            for (double &gv : ghat) gv -= gm;
+            for (size_t rr = 0; rr < s_alpha.size() / (size_t)m; rr++)
+                for (int i = 0; i < m; i++) s_alpha[rr * m + i] += ghat[i];
+            poly_finished = true;
+        }
+        for (int i = 0; i < m; i++) asum[i] += ghat[i];
     }
     if (o->alpha) std::memcpy(o->alpha, asum.data(), sizeof(double) * m);
     { // e -= X * alpha (:971): one device mat-vec; shards sum their partial products
@@ -1262,6 +1329,25 @@ int hb_run_state(hb_run *r, hb_run_info *info)
 
 hb_ctx *hb_run_ctx(hb_run *r) { return r ? r->c : nullptr; }
 
+int hb_run_poly(hb_run *r, hb_poly_out *po)
+{
+    if (!r || !po) return hb_fail(HB_ERR_INVALID, "hb_run_poly: null argument");
+    if (!r->poly) return hb_fail(HB_ERR_INVALID, "hb_run_poly: the run has no polygenic block (model \"BSLMM\" with Kival / Ki)");
+    if (!r->poly_finished) return hb_fail(HB_ERR_INVALID, "hb_run_poly: call hb_run_finish first");
+    const int R = r->n_records;
+    auto mean_sd = [&](const std::vector<double> &v, double *mean, double *sd) { // arma::mean / stddev (N - 1), :965-968
+        *mean = R > 0 ? arma_sum(v.data(), v.size()) / R : 0.0;
+        *sd = std::sqrt(var_n1(v.data(), v.size()));
+    };
+    mean_sd(r->s_Va, &po->Va, &po->Va_sd);
+    mean_sd(r->s_Vb, &po->Vb, &po->Vb_sd);
+    if (po->s_Va && R) std::memcpy(po->s_Va, r->s_Va.data(), sizeof(double) * R);
+    if (po->s_Vb && R) std::memcpy(po->s_Vb, r->s_Vb.data(), sizeof(double) * R);
+    if (po->k_mean) std::memcpy(po->k_mean, r->k_mean.data(), sizeof(double) * r->n);
+    if (po->ghat) std::memcpy(po->ghat, r->ghat.data(), sizeof(double) * r->m);
+    return HB_OK;
+}
+
 int hb_run_finish(hb_run *r, hb_bayes_out *out)
 {
     if (!r || !out) return hb_fail(HB_ERR_INVALID, "hb_run_finish: null argument");
@@ -1270,7 +1356,9 @@ int hb_run_finish(hb_run *r, hb_bayes_out *out)
 
 void hb_run_destroy(hb_run *r) { delete r; }
 
-int hb_bayes_run(const hb_bayes_args *args, hb_bayes_out *out)
+int hb_bayes_run(const hb_bayes_args *args, hb_bayes_out *out) { return hb_bayes_run_poly(args, out, nullptr); }
+
+int hb_bayes_run_poly(const hb_bayes_args *args, hb_bayes_out *out, hb_poly_out *poly_out)
 {
     if (!args || !out) return hb_fail(HB_ERR_INVALID, "hb_bayes_run: null argument");
     hb_run *r = nullptr;
@@ -1281,6 +1369,7 @@ int hb_bayes_run(const hb_bayes_args *args, hb_bayes_out *out)
         if (rc) break;
     }
     if (!rc) rc = r->finish(out);
+    if (!rc && poly_out) rc = hb_run_poly(r, poly_out);
     delete r;
     return rc;
 }

@@ -48,10 +48,11 @@ class Context:
         X = np.asarray(X)
         if X.dtype == np.int8:
             Xa = np.asfortranarray(X)
-            check(self.L.hb_ctx_upload_genotype_i8(self.h, Xa.ctypes.data, Xa.strides[1], col0, Xa.shape[1]))
+            # (the stride numpy reports for a single column is arbitrary: at least a column's length)
+            check(self.L.hb_ctx_upload_genotype_i8(self.h, Xa.ctypes.data, max(Xa.strides[1], Xa.shape[0]), col0, Xa.shape[1]))
         else:
             Xa = np.asfortranarray(X, dtype=np.float64)
-            check(self.L.hb_ctx_upload_genotype_f64(self.h, Xa.ctypes.data, Xa.strides[1] // 8, col0, Xa.shape[1]))
+            check(self.L.hb_ctx_upload_genotype_f64(self.h, Xa.ctypes.data, max(Xa.strides[1] // 8, Xa.shape[0]), col0, Xa.shape[1]))
 
     def upload_bed(self, raw, nind, rows=None, col0=0, ncols=None):
         raw = np.frombuffer(raw, dtype=np.uint8)
@@ -257,6 +258,42 @@ class Context:
         out = [np.zeros(nc), np.zeros(nl), np.zeros(nr), np.zeros(nr)]
         check(self.L.hb_ctx_blocks_state(self.h, *[x.ctypes.data for x in out]))
         return out
+
+    # ---- BSLMM's polygenic block (reference src/Bayes.cpp:518-552) ----
+    def poly_setup(self, Kival, Ki, on_device=False):
+        """Eigenvalues (n) and eigenvectors (n x n) of the relationship matrix. Ki: a host array, or with on_device=True a CUDA/HIP torch
+        tensor (float64, row j = column j of K, an even row stride) that the context borrows and this object keeps alive."""
+        kv = np.ascontiguousarray(Kival, dtype=np.float64)
+        if on_device:
+            if Ki is None or Ki.dim() != 2 or Ki.shape[0] != self.n or Ki.shape[1] < self.n or Ki.stride(1) != 1:
+                raise ValueError("poly_setup: a device K is a tensor of n rows, row j holding column j of K (n values, then padding)")
+            self._poly_keep = Ki
+            check(self.L.hb_ctx_poly_setup(self.h, kv.ctypes.data, Ki.data_ptr(), Ki.stride(0), 1))
+        else:
+            K = np.asfortranarray(Ki, dtype=np.float64)
+            check(self.L.hb_ctx_poly_setup(self.h, kv.ctypes.data, K.ctypes.data, K.strides[1] // 8, 0))
+
+    def poly_step(self, vare, vb_in, seed, it, chis, s2_df):
+        """Enqueue one iteration of the block (no host sync): vb_in < 0 keeps the device's vb."""
+        check(self.L.hb_ctx_poly_step(self.h, float(vare), float(vb_in), int(seed), int(it), float(chis), float(s2_df)))
+
+    def poly_state(self):
+        """(k, vb, q, flag) after the last step; flag: the matrix failed the reference's positive-definiteness check (:533)."""
+        k = np.zeros(self.n)
+        vb, q, fl = C.c_double(), C.c_double(), C.c_int32()
+        check(self.L.hb_ctx_poly_state(self.h, k.ctypes.data, C.byref(vb), C.byref(q), C.byref(fl)))
+        return k, vb.value, q.value, bool(fl.value)
+
+    def poly_debug(self):
+        """Debug read-out of the last step: t = K'(yadj + k_old), w, eval, Kg = K' k_new."""
+        out = [np.zeros(self.n) for _ in range(4)]
+        check(self.L.hb_ctx_poly_debug_get(self.h, *[x.ctypes.data for x in out]))
+        return dict(zip(("t", "w", "eval", "Kg"), out))
+
+    def grm(self, lambda_=0.0, raw=False):
+        """The genomic relationship matrix of the resident int8 genotypes (hb_grm_build; make_grm() of the reference, src/rm.cpp:5-53)."""
+        from .grm import grm_build
+        return grm_build(self, lambda_, raw)
 
     def set_windows(self, windindx):
         w = np.ascontiguousarray(windindx, dtype=np.uint32)

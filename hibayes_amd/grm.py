@@ -1,0 +1,54 @@
+"""make_grm(): the genomic relationship matrix of the reference (src/rm.cpp:5-53) from genotypes resident on the device.
+
+The n x n matrix G = Z Z' / mean(diag(Z Z')), Z the column-centred genotypes, is built by hb_grm_build (hand-written gfx950 kernels:
+exact int8 cross-products on the matrix cores, one fixed fp64 expression per entry). The eigen-decomposition
+ibrm()'s BSLMM needs (R/bayes.r:292-294) is numpy.linalg.eigh — LAPACK's dsyevd, the routine the reference calls (eigen_sym_dc).
+"""
+import ctypes as C
+
+import numpy as np
+
+from ._lib import check, lib
+
+HB_GRM_RAW = 1
+
+
+def grm_build(ctx, lambda_=0.0, raw=False):
+    """hb_grm_build on an engine.Context that holds int8 columns: the n x n matrix as a Fortran-ordered array."""
+    G = np.zeros((ctx.n, ctx.n), order="F")
+    check(lib().hb_grm_build(ctx.h, float(lambda_), HB_GRM_RAW if raw else 0, G.ctypes.data, None))
+    return G
+
+
+def make_grm(M, lambda_=0.0, inverse=False, eigen=False, verbose=True, *, device=0):
+    """Mirror of make_grm() (reference src/rm.cpp:5-53). `M` is the n x m genotype matrix (int8 preferred, or integer-valued floats)
+    or an engine.Context with the genotypes already resident. Returns G, or with eigen=True the pair (eigenvalues, eigenvectors) in
+    numpy.linalg.eigh's ascending order. As in the reference, `lambda_` is added to the diagonal before the decomposition (:46) and
+    is not part of the plain G. inverse=True (solve(), :39-42) is not implemented."""
+    if inverse:
+        raise NotImplementedError("make_grm(inverse=True) is not implemented: only G and its eigen-decomposition are")
+    from .engine import Context
+    own = not isinstance(M, Context)
+    if own:
+        M = np.asarray(M)
+        if M.ndim != 2:
+            raise ValueError("make_grm: M must be an n x m matrix")
+        ctx = Context(M.shape[0], M.shape[1], device=device)
+    else:
+        ctx = M
+    try:
+        if own:
+            ctx.upload(M)
+        if verbose:
+            print("Start construct G matrix for %d individuals using %d markers" % (ctx.n, ctx.m))
+            print("Compute Z * Z'")
+        G = grm_build(ctx, lambda_ if eigen else 0.0)
+    finally:
+        if own:
+            ctx.close()
+    if not eigen:
+        return G
+    if verbose:
+        print("Eigen decomposition on G matrix")
+    ev, K = np.linalg.eigh(G)
+    return ev, np.asfortranarray(K)

@@ -35,7 +35,7 @@ typedef enum {
     HB_ERR_INVALID = 1,     /* argument validation (reference exception text in hb_last_error) */
     HB_ERR_NO_DEVICE = 2,   /* no usable HIP device / runtime */
     HB_ERR_HIP = 3,         /* a HIP call or kernel failed */
-    HB_ERR_UNSUPPORTED = 4, /* argument outside the GPU path (BSLMM, epsilon block, non-integer X) */
+    HB_ERR_UNSUPPORTED = 4, /* argument outside the GPU path (BSLMM without Kival / Ki, or sharded / warm; epsilon block; non-integer X) */
     HB_ERR_COMM = 5,        /* the multi-GPU all-reduce callback failed */
     HB_ERR_INTERRUPT = 6,   /* interrupt callback asked to stop */
     HB_ERR_ABORTED = 7      /* a wait inside the device pipeline timed out and the sweep was abandoned (hb_ctx_sweep_end); the
@@ -114,8 +114,9 @@ typedef struct hb_bayes_args {
     const char *model;       /* std::string model                                    (:63) */
     const double *Pi;        /* arma::vec Pi                                         (:64) */
     int32_t n_pi;
-    const double *Kival;     /* BSLMM only (:65) — must be NULL (HB_ERR_UNSUPPORTED)        */
-    const double *Ki;        /* BSLMM only (:66) — must be NULL                             */
+    const double *Kival;     /* BSLMM only (:65): the n eigenvalues of the relationship matrix (make_grm(eigen = TRUE), R/bayes.r:292-294) */
+    const double *Ki;        /* BSLMM only (:66): its n x n eigenvectors, column-major, leading dimension n. Both or neither; with another
+                                model, or model "BSLMM" without them (and without a ctx prepared by hb_ctx_poly_setup): HB_ERR_UNSUPPORTED */
     const double *C;         /* Nullable<arma::mat> C, n x nc column-major           (:67) */
     int32_t nc;
     const char *const *R;    /* Nullable<CharacterMatrix> R, n x nr column-major      (:68) */
@@ -244,6 +245,18 @@ typedef struct hb_bayes_out {
 /* The whole sampler: replaces Bayes() (reference src/Bayes.cpp:60-1094). */
 int hb_bayes_run(const hb_bayes_args *args, hb_bayes_out *out);
 
+/* BSLMM (src/Bayes.cpp:518-552, :854-858, :955-969): what the polygenic block adds to the result. The reference only prints Va / Vb
+ * (:901, :1074); the records, the mean polygenic vector and the back-projection are extensions. Caller-allocated arrays, NULL = not wanted. */
+typedef struct hb_poly_out {
+    double Va, Vb, Va_sd, Vb_sd; /* mean and sd (N - 1) of the records (:965-968) */
+    double *s_Va, *s_Vb;     /* R each: va = varg (:715) and vb (:550) at the thinned records (:855-856) */
+    double *k_mean;          /* n: k_estR_store / count (:956) */
+    double *ghat;            /* m: X'(K ((K' k_mean) / Kval / sumvx)), centred (:957-962); already added to alpha and to every s_alpha column (:964) */
+} hb_poly_out;
+/* hb_bayes_run that also reports the polygenic block; hb_bayes_run(args, out) is hb_bayes_run_poly(args, out, NULL). poly_out with a run
+ * that has no polygenic block is HB_ERR_INVALID. */
+int hb_bayes_run_poly(const hb_bayes_args *args, hb_bayes_out *out, hb_poly_out *poly_out);
+
 /* The same sampler, stepwise: create (validation, upload, marker statistics, Gram, priors) ->
  * step (iterations of the loop at src/Bayes.cpp:477) -> finish (posterior assembly, :919-1040).
  * hb_bayes_run() is exactly create + step-until-finished + finish. The caller's arrays are copied
@@ -268,6 +281,8 @@ int hb_run_step(hb_run *r, int32_t nsteps, int32_t *finished);
 int hb_run_state(hb_run *r, hb_run_info *info);
 hb_ctx *hb_run_ctx(hb_run *r);
 int hb_run_finish(hb_run *r, hb_bayes_out *out);
+/* after hb_run_finish of a BSLMM run: the polygenic block's results */
+int hb_run_poly(hb_run *r, hb_poly_out *poly_out);
 void hb_run_destroy(hb_run *r);
 
 /* ------------------------------------------------------------------------------------
@@ -432,6 +447,19 @@ int hb_cg_run_ldm(const hb_cg_args *args, hb_ldm *ldm, hb_cg_out *out);
 /* conjgt_spa (src/cg.cpp:4-65) with args->ldm == NULL, on the handle's device CSC; nothing m x m is allocated. */
 int hb_cg_run_sparse(const hb_cg_args *args, hb_ldm *ldm, hb_cg_out *out);
 
+/* ------------------------------------------------------------------------------------
+ * make_grm() of the reference (src/rm.cpp:5-53) from a context's resident int8 genotypes: G = Z Z' / mean(diag(Z Z')) with Z the
+ * column-centred genotypes, then diag += lambda (:37, :46). The cross-products are exact integers on the matrix cores, one fixed fp64
+ * expression per entry follows, one triangle is computed and mirrored: G equals its transpose bit for bit and
+ * two builds agree bit for bit. G_host: n x n column-major or NULL; G_dev: NULL, or receives a device copy (leading dimension n) that
+ * the caller releases with hb_grm_free. flags: HB_GRM_RAW = the centred cross-product Z Z' itself, no scaling and no lambda.
+ * All markers monomorphic (mean diagonal 0; the reference returns NaN): HB_ERR_INVALID. The n x n matrix not fitting on the device:
+ * HB_ERR_HIP with "out of memory" in the text. The inverse and the eigen-decomposition are not part of the library.
+ * ------------------------------------------------------------------------------------ */
+#define HB_GRM_RAW 1
+int hb_grm_build(hb_ctx *c, double lambda, int32_t flags, double *G_host, double **G_dev);
+void hb_grm_free(double *G_dev);
+
 /* ====================================================================================
  * Fine-grained engine API.  hb_bayes_run() is built on it; the parity tests and bench.py
  * drive the device pieces through it one at a time.  A context owns all device state of
@@ -548,6 +576,23 @@ int hb_ctx_level_axpy(hb_ctx *c, int32_t term, const double *delta);  /* yadj +=
 int hb_ctx_blocks_setup(hb_ctx *c, const double *cpc /* nc */, const double *zz /* levels */, const double *vrtmp0 /* nr */);
 int hb_ctx_blocks_step(hb_ctx *c, double vare, const double *z_beta, const double *z_levels, const double *chisq, double dfr, double s2r);
 int hb_ctx_blocks_state(hb_ctx *c, double *beta, double *estR, double *vrtmp, double *vr);
+
+/* BSLMM's polygenic block of one iteration (src/Bayes.cpp:518-552) as device kernels with no host synchronisation, on the eigenvectors
+ * Ki (n x n column-major, leading dimension ld >= n) and eigenvalues Kival (n, host) of the relationship matrix.
+ * setup: on_device != 0 — Ki is a DEVICE pointer the context borrows (16-byte aligned, ld even; a torch tensor's data_ptr()); else a host
+ * matrix that is uploaded (n * n * 8 bytes of device memory). Kival = Ki = NULL drops the block.
+ * step: k_new = K ((eval / vare) o K'(yadj + k_old) + sqrt(max(eval, 0)) o z), eval = Kival vare / (Kival + vare / vb) (:531-535), z_j drawn on
+ * the device (Philox purpose 5: sub = (5 << 56) | iter, blk = j); yadj += k_old - k_new, u -= k_old - k_new (:537-540);
+ * vb = (sum_j (K' k_new)_j^2 / Kival_j + s2_df) / chis (:543-547) with chis = chisq_sample(dfvara + n) drawn by the caller and
+ * s2_df = s2vara * dfvara. vb_in < 0 uses the vb the previous step left on the device (the first step needs vb_in = vara, :333).
+ * state: synchronises; k (n) = the polygenic vector, *flag != 0 = the check of :533 failed in the last step (the sampler then fails with the
+ * reference's text). Inside hb_run_step vb, q and the flag come back with the sweep's fetch. */
+int hb_ctx_poly_setup(hb_ctx *c, const double *Kival, const double *Ki, int64_t ld, int32_t on_device);
+int hb_ctx_poly_step(hb_ctx *c, double vare, double vb_in, uint64_t seed, int64_t iter, double chis, double s2_df);
+int hb_ctx_poly_state(hb_ctx *c, double *k, double *vb, double *q, int32_t *flag);
+/* Debug read-out for the kernel-level tests (tests/test_gpu_bslmm.py): what the last step left, n doubles each, any pointer may be NULL —
+ * t = K'(yadj + k_old), w (the vector K multiplies), eval, Kg = K' k_new. Synchronises and changes nothing. */
+int hb_ctx_poly_debug_get(hb_ctx *c, double *t, double *w, double *eval, double *Kg);
 
 /* One marker sweep (reference src/Bayes.cpp:586-816) plus the two reductions behind
  * :819 and :823.  Hyper-parameters come from the host, per-SNP draws happen on device. */

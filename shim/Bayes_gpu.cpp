@@ -58,8 +58,9 @@ Rcpp::List Bayes(arma::vec &y, arma::mat &X, std::string model, arma::vec Pi,
         for (int j = 0; j < R_.ncol(); j++) for (int i = 0; i < R_.nrow(); i++) rs.push_back(as<std::string>(R_(i, j)));
         for (auto &s : rs) rp.push_back(s.c_str());
         a.R = rp.data();  a.nr = R_.ncol(); }
-    // BSLMM and the single-step epsilon block are outside the GPU path: ANY non-NULL value reaches the library, which answers
-    // HB_ERR_UNSUPPORTED with a text (-> an R error), never a silent fit without the block
+    // BSLMM's Kival / Ki and the single-step epsilon block: ANY non-NULL value reaches the library. With both Kival and Ki and model "BSLMM" the
+    // polygenic block runs on the device; an incomplete pair, either of them under another model, and the epsilon block are answered with
+    // HB_ERR_UNSUPPORTED and a text (-> an R error), never with a silent fit without the block
     arma::vec Kival_; if (Kival.isNotNull()) { Kival_ = as<arma::vec>(Kival); a.Kival = Kival_.memptr(); }
     arma::mat Ki_;    if (Ki.isNotNull())    { Ki_ = as<arma::mat>(Ki);       a.Ki = Ki_.memptr(); }
     arma::vec ey_;    if (epsl_y_J.isNotNull())   { ey_ = as<arma::vec>(epsl_y_J); a.epsl_y_J = ey_.memptr(); }
