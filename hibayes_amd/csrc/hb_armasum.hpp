@@ -1,5 +1,6 @@
-// hb_armasum.hpp — arma::sum of a vector as Armadillo's accumulate forms it: two interleaved accumulators. Host code; shared by the
-// summary-level units (hb_sbayes.hip, hb_cg.hip), whose set-ups must sum yyi exactly as the reference does.
+// hb_armasum.hpp — arma::sum of a vector as Armadillo's arrayops::accumulate forms it: two interleaved accumulators. Host code.
+// The order is the point: sumvx (src/Bayes.cpp:316), yy of the summary-level set-ups and the normalisation of a drawn Pi then
+// agree with the reference's to the last bit when their terms do.
 #pragma once
 #include <stddef.h>
 

@@ -1,6 +1,6 @@
 // hb_cg.hip — sbrm()'s method = "CG": the conjugate-gradient ridge solve (V + diag(lambda)) g = b of the reference (CG(),
 // src/solver.cpp:54-115, called by conjgt_den / conjgt_spa, src/cg.cpp:4-129) on the device. A unit of its own: it shares
-// nothing with the chain kernels' unit. DESIGN.md §14.
+// nothing with the chain kernels' unit but hb_wave.hpp. DESIGN.md §14.
 //
 // The LD matrix is symmetric (hb_ldm_from_csc checks it, hb_ldm_build's are by construction, k_cg_symcheck checks a host dense
 // matrix), so row i of V is column i: in the column-major dense matrix and in the CSC alike (V p)[i] is ONE contiguous dot
@@ -17,27 +17,17 @@
 // holds the number of iterations run at the reference's `break` (0: none yet); a kernel of iteration i returns at once when it
 // is in 1..i. The host enqueues iterations in chunks and looks at the word once per chunk (cg_run).
 #include "hb_internal.hpp"
-#include "hb_armasum.hpp"
 #include "hb_ldm.hpp"
+#include "hb_model.hpp"
+#include "hb_wave.hpp"
 #include <algorithm>
-#include <chrono>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 
 namespace {
-using clk = std::chrono::steady_clock;
-typedef double d2 __attribute__((ext_vector_type(2)));
 constexpr int CG_T = 256;            // threads per workgroup, every kernel of this unit
 constexpr int CG_W = CG_T / 64;      // waves per workgroup = dense columns per workgroup
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // workgroup-wide sum in a fixed order, the result in every thread; red holds CG_W entries
 __device__ __forceinline__ double block_sum(double v, double *red)
@@ -258,25 +248,16 @@ __global__ __launch_bounds__(256) void k_cg_symcheck(const double *__restrict__ 
 
 struct cg_dev {
     hipStream_t stream = nullptr;
-    std::vector<void *> bufs;
+    hb_bufs mem;
     int *h_stop = nullptr;
     double *h_err = nullptr;
     ~cg_dev()
     {
         if (stream) (void)hipStreamSynchronize(stream);
-        for (void *q : bufs)
-            if (q) (void)hipFree(q);
-        if (h_stop) (void)hipHostFree(h_stop);
-        if (h_err) (void)hipHostFree(h_err);
+        mem.clear();
         if (stream) (void)hipStreamDestroy(stream);
     }
-    template <typename T> int alloc(T **q, size_t count)
-    {
-        HB_HIP(hipMalloc(reinterpret_cast<void **>(q), std::max<size_t>(count, 1) * sizeof(T)));
-        bufs.push_back(*q);
-        HB_HIP(hipMemsetAsync(*q, 0, std::max<size_t>(count, 1) * sizeof(T), stream));
-        return HB_OK;
-    }
+    template <typename T> int alloc(T **q, size_t count) { return mem.zeroed(q, count, stream); }
 };
 
 // what one run's mat-vec reads: the dense matrix or the CSC
@@ -306,32 +287,16 @@ struct cg_mat {
 int cg_run(const hb_cg_args *args, hb_ldm *H, hb_cg_out *o, bool sparse)
 {
     if (!args || !o) return hb_fail(HB_ERR_INVALID, "hb_cg_run: null argument");
-    const auto t_setup = clk::now();
+    const auto t_setup = hb_clk::now();
     const hb_cg_args &a = *args;
     const int m = a.m;
     if (H ? (m < 1 || !a.sumstat || a.ldm || a.ld_sumstat < m || H->m != m)
           : (m < 1 || !a.sumstat || !a.ldm || a.ld_sumstat < m || a.ld_ldm < m)) return hb_fail(HB_ERR_INVALID, "Number of SNPs not equals."); // src/cg.cpp:15-17, :79-81
-    auto line = [&](const char *fmt, ...) {
-        if (!a.verbose) return;
-        char buf[256];
-        va_list ap;
-        va_start(ap, fmt);
-        vsnprintf(buf, sizeof(buf), fmt, ap);
-        va_end(ap);
-        if (a.log) a.log(buf, a.log_user);
-        else { fputs(buf, stdout); fputc('\n', stdout); fflush(stdout); }
-    };
+    auto line = [&](const char *fmt, auto... xs) { hb_line(a.verbose, a.log, a.log_user, fmt, xs...); };
     // ---- src/cg.cpp:12-41, :77-103 ----
     const double *ss = a.sumstat;
     const int64_t lds = a.ld_sumstat;
-    int n;
-    {
-        double s = 0;
-        int c = 0;
-        for (int k = 0; k < m; k++)
-            if (std::isfinite(ss[3 * lds + k])) { s += ss[3 * lds + k]; c++; }
-        n = (int)(s / std::max(1, c)); // :13 int n = mean(na_omit(NMISS))
-    }
+    const int n = hb_sumstat_n(ss, lds, m); // :13 int n = mean(na_omit(NMISS))
     std::vector<double> xpx(m), b(m), yyi(m, 0.0);
     int count_y = 0;
     for (int k = 0; k < m; k++) {
@@ -355,22 +320,20 @@ int cg_run(const hb_cg_args *args, hb_ldm *H, hb_cg_out *o, bool sparse)
     HB_HIP(hipSetDevice(a.device));
     cg_dev D;
     HB_HIP(hipStreamCreateWithFlags(&D.stream, hipStreamNonBlocking));
-    int rc;
-#define TRYA(x) do { rc = (x); if (rc) return rc; } while (0)
     cg_mat M;
     M.m = m;
     if (sparse) { // adopted, not owned; nothing m x m exists on this route
-        TRYA(hb_ldm_device_csc(H, &M.csc));
+        HB_TRY(hb_ldm_device_csc(H, &M.csc));
         const double mean = (double)M.csc.nnz / m;
         M.lpc = mean < 16.0 ? 4 : mean < 256.0 ? 16 : 64;
     } else if (H) {
-        TRYA(hb_ldm_device_dense(H, &M.V));
+        HB_TRY(hb_ldm_device_dense(H, &M.V));
         M.ld = m;
     } else { // uploaded without its padding rows: the run is then the handle's, bit for bit
         double *dv = nullptr;
         unsigned long long *d_first = nullptr, h_first = 0;
-        TRYA(D.alloc(&dv, (size_t)m * m));
-        TRYA(D.alloc(&d_first, 1));
+        HB_TRY(D.alloc(&dv, (size_t)m * m));
+        HB_TRY(D.alloc(&d_first, 1));
         HB_HIP(hipMemcpy2DAsync(dv, sizeof(double) * m, a.ldm, sizeof(double) * a.ld_ldm, sizeof(double) * m, m, hipMemcpyHostToDevice, D.stream));
         HB_HIP(hipMemsetAsync(d_first, 0xff, sizeof(unsigned long long), D.stream));
         const unsigned nt = (unsigned)((m + 31) / 32);
@@ -390,30 +353,30 @@ int cg_run(const hb_cg_args *args, hb_ldm *H, hb_cg_out *o, bool sparse)
     const int na = M.blocks(), nb = (m + CG_T - 1) / CG_T;
     double *d_b, *d_lam = nullptr, *d_x, *d_r, *d_p, *d_ap, *d_pap, *d_rr, *d_err, *d_s;
     int *d_stop;
-    TRYA(D.alloc(&d_b, m));
+    HB_TRY(D.alloc(&d_b, m));
     const size_t vlen = (size_t)m + 2; // x and p are mat-vec operands: one pair of zeros behind the end (load_p, cg_mat::launch)
-    TRYA(D.alloc(&d_x, vlen));
-    TRYA(D.alloc(&d_r, m));
-    TRYA(D.alloc(&d_p, vlen));
-    TRYA(D.alloc(&d_ap, m));
-    TRYA(D.alloc(&d_pap, na));
-    TRYA(D.alloc(&d_rr, (size_t)2 * nb));
-    TRYA(D.alloc(&d_err, m));
-    TRYA(D.alloc(&d_s, 1));
-    TRYA(D.alloc(&d_stop, 1));
+    HB_TRY(D.alloc(&d_x, vlen));
+    HB_TRY(D.alloc(&d_r, m));
+    HB_TRY(D.alloc(&d_p, vlen));
+    HB_TRY(D.alloc(&d_ap, m));
+    HB_TRY(D.alloc(&d_pap, na));
+    HB_TRY(D.alloc(&d_rr, (size_t)2 * nb));
+    HB_TRY(D.alloc(&d_err, m));
+    HB_TRY(D.alloc(&d_s, 1));
+    HB_TRY(D.alloc(&d_stop, 1));
     if (a.lambda) {
-        TRYA(D.alloc(&d_lam, m));
+        HB_TRY(D.alloc(&d_lam, m));
         HB_HIP(hipMemcpyAsync(d_lam, a.lambda, sizeof(double) * m, hipMemcpyHostToDevice, D.stream));
     }
-    HB_HIP(hipHostMalloc(reinterpret_cast<void **>(&D.h_stop), sizeof(int)));
-    HB_HIP(hipHostMalloc(reinterpret_cast<void **>(&D.h_err), sizeof(double) * m));
+    HB_TRY(D.mem.pin(&D.h_stop, 1));
+    HB_TRY(D.mem.pin(&D.h_err, m));
     HB_HIP(hipMemcpyAsync(d_b, b.data(), sizeof(double) * m, hipMemcpyHostToDevice, D.stream));
     hipLaunchKernelGGL(k_cg_init, dim3(nb), dim3(CG_T), 0, D.stream, m, d_b, d_lam, d_x, d_r, d_p, d_rr);
     HB_HIP(hipGetLastError());
     HB_HIP(hipStreamSynchronize(D.stream));
     o->n = n;
     o->count_y = count_y;
-    const double setup_seconds = std::chrono::duration<double>(clk::now() - t_setup).count();
+    const double setup_seconds = hb_since(t_setup);
 
     line("Prior parameters:");
     line("    Model fitted at [Conjugate Gradient]");
@@ -421,7 +384,7 @@ int cg_run(const hb_cg_args *args, hb_ldm *H, hb_cg_out *o, bool sparse)
     line("    Phenotypic var %.4f", vary);
 
     // ---- CG(), src/solver.cpp:88-113: iterations in chunks, one look at the stop word per chunk ----
-    const auto t_loop = clk::now();
+    const auto t_loop = hb_clk::now();
     const int chunk = std::min(64, a.outfreq > 0 ? a.outfreq : 64);
     auto enqueue = [&](int it) -> int {
         const int e = M.launch(D.stream, d_p, vlen, d_lam, d_ap, d_pap, d_stop, it);
@@ -437,7 +400,7 @@ int cg_run(const hb_cg_args *args, hb_ldm *H, hb_cg_out *o, bool sparse)
     bool nan = false;
     for (int it0 = 0; it0 < m && !converged && !nan;) {
         const int c = std::min(chunk, m - it0);
-        for (int k = 0; k < c; k++) TRYA(enqueue(it0 + k));
+        for (int k = 0; k < c; k++) HB_TRY(enqueue(it0 + k));
         HB_HIP(hipGetLastError());
         HB_HIP(hipMemcpyAsync(D.h_stop, d_stop, sizeof(int), hipMemcpyDeviceToHost, D.stream));
         HB_HIP(hipMemcpyAsync(D.h_err + it0, d_err + it0, sizeof(double) * c, hipMemcpyDeviceToHost, D.stream));
@@ -457,7 +420,7 @@ int cg_run(const hb_cg_args *args, hb_ldm *H, hb_cg_out *o, bool sparse)
             // nothing finite can follow: the reference runs on to m with alpha NaN, which makes x NaN everywhere one iteration
             // after err at the latest — that iteration is run if the chunk ended on the first NaN
             if (it0 < m) {
-                TRYA(enqueue(it0));
+                HB_TRY(enqueue(it0));
                 HB_HIP(hipGetLastError());
                 HB_HIP(hipStreamSynchronize(D.stream));
             }
@@ -467,12 +430,12 @@ int cg_run(const hb_cg_args *args, hb_ldm *H, hb_cg_out *o, bool sparse)
             }
         }
     }
-    const double loop_seconds = std::chrono::duration<double>(clk::now() - t_loop).count();
+    const double loop_seconds = hb_since(t_loop);
     const double err = D.h_err[iterations - 1];
     line(converged ? "Convergence: YES" : "Convergence: NO[try to adjust lambda]"); // :109-113
 
     // ---- src/cg.cpp:52-53, :115-116: one more mat-vec, without lambda ----
-    TRYA(M.launch(D.stream, d_x, vlen, nullptr, d_ap, d_pap, nullptr, 0));
+    HB_TRY(M.launch(D.stream, d_x, vlen, nullptr, d_ap, d_pap, nullptr, 0));
     hipLaunchKernelGGL(k_cg_sum, dim3(1), dim3(CG_T), 0, D.stream, d_pap, na, d_s);
     HB_HIP(hipGetLastError());
     double gVg = 0.0;
@@ -494,7 +457,6 @@ int cg_run(const hb_cg_args *args, hb_ldm *H, hb_cg_out *o, bool sparse)
     line("    Genetic var %.4f", o->vg);
     line("    Residual var %.4f", o->ve);
     return HB_OK;
-#undef TRYA
 }
 } // namespace
 

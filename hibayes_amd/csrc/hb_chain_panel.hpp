@@ -2,6 +2,7 @@
 // Part of the one translation unit hb_kernels.hip (the kernels share device globals and the views defined before them);
 // included there in this order, not compiled on its own.
 #pragma once
+#include "hb_wave.hpp"
 
 // ---------------------------------------------------------------------------------------------
 // k_chain: one workgroup of P threads (thread = marker of the panel, wave = 64-marker sub-block).
@@ -44,13 +45,6 @@ struct chain_view {
 #define HB_STAMP(i) do { } while (0)
 #define HB_STAMP_VAL(i, x) do { } while (0)
 #endif
-
-__device__ __forceinline__ double readlane_f64(double v, int k)
-{
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), k);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), k);
-    return __hiloint2double(hi, lo);
-}
 
 // v of the lane N below within the lane's row of 16 (DPP row_shr: a modifier of the move, no LDS round trip); 0 where there is none
 template <int N>

@@ -1,9 +1,10 @@
 // hb_ctx.hip — device context of one genotype shard and the fine-grained C ABI on top of it.
 #include "hb_internal.hpp"
+#include "hb_armasum.hpp"
 #include "hb_runplan.hpp"
 #include <algorithm>
-#include <chrono>
 #include <cmath>
+#include <cstdarg>
 #include <cstring>
 #include <cstdlib>
 #include <cstdio>
@@ -52,6 +53,18 @@ int hb_fail(int status, const std::string &msg)
 {
     g_err = msg;
     return status;
+}
+
+void hb_line(int verbose, hb_log_fn log, void *log_user, const char *fmt, ...)
+{
+    if (!verbose) return;
+    char buf[1024];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    if (log) log(buf, log_user);
+    else { fputs(buf, stdout); fputc('\n', stdout); fflush(stdout); }
 }
 
 template <typename T>
@@ -486,20 +499,6 @@ int hb_ctx_download_genotype(hb_ctx *c, int8_t *X, int64_t ld, int32_t col0, int
     return HB_OK;
 }
 
-// Armadillo's arrayops::accumulate order (two interleaved accumulators) so that sumvx agrees
-// with sum(vx) of reference src/Bayes.cpp:316 to the last bit when vx does
-static double arma_sum(const double *v, size_t n)
-{
-    double a1 = 0.0, a2 = 0.0;
-    size_t j;
-    for (j = 1; j < n; j += 2) {
-        a1 += v[j - 1];
-        a2 += v[j];
-    }
-    if ((j - 1) < n) a1 += v[j - 1];
-    return a1 + a2;
-}
-
 int hb_ctx_marker_stats(hb_ctx *c, double *xpx, double *vx, double *sumvx, int32_t *nvar0)
 {
     int rc = check_cols(c, 0, 0, "hb_ctx_marker_stats");
@@ -630,13 +629,13 @@ int hb_ctx_build_gram(hb_ctx *c, double *seconds)
     const double amax = std::max(std::abs((double)c->xmin), std::abs((double)c->xmax));
     if (amax * amax * (double)c->n >= 2147483647.0)
         return hb_fail(HB_ERR_UNSUPPORTED, "genotype codes too large for the exact int32 Gram matrix at this n");
-    const auto t0 = std::chrono::steady_clock::now();
+    const auto t0 = hb_clk::now();
     rc = hb_build_gram_impl(c);
     if (rc) return rc;
     rc = hb_build_gcert(c); // (the rank-one part of the band and the bound on the rest: the group chain's certificate)
     if (rc) return rc;
     HB_HIP(hipStreamSynchronize(c->stream));
-    if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (seconds) *seconds = hb_since(t0);
     c->gram_ready = true;
     return HB_OK;
 }

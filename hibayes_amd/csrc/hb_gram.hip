@@ -7,10 +7,8 @@
 // v_mfma_i32_32x32x32_i8 straight from one 16-byte global load, no LDS transpose.
 // One wave = one 64x64 block of the panel's P x P matrix (2x2 MFMA tiles of 32x32).
 #include "hb_internal.hpp"
+#include "hb_wave.hpp"
 #include <cstdlib>
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
 
 // Band layout: gram[(p * (L+1) + l) * P*P + row * P + col] = x_{(p-l)P + row} . x_{pP + col}, l = 0..L
 // (l = 0: the panel's own Gram; l >= 1: the panels the look-ahead pipeline has not yet folded into

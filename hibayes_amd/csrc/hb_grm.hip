@@ -1,6 +1,6 @@
 // hb_grm.hip — BSLMM's dense side on the device: make_grm() of the reference (src/rm.cpp:5-53) from the resident int8
 // genotypes, and the polygenic block of one iteration of Bayes() (src/Bayes.cpp:518-552) on the eigenvectors K of that matrix.
-// A unit of its own: it shares nothing with the chain kernels' unit.
+// A unit of its own: it shares nothing with the chain kernels' unit but hb_wave.hpp.
 //
 // GRM. G = Z Z' with Z = M - 1 c'/n (c: the markers' column sums). With S = M M', a_i = sum_k c_k M_ik and C = sum_k c_k^2 — all exact
 // integers — the centred cross-product is
@@ -20,6 +20,7 @@
 // No floating-point atomic anywhere: every sum has one fixed order and two runs agree bit for bit.
 #include "hb_internal.hpp"
 #include "hb_rng.hpp"
+#include "hb_wave.hpp"
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -41,10 +42,6 @@ struct hb_poly {
 };
 
 namespace {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
-typedef double d2 __attribute__((ext_vector_type(2)));
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // GRM
@@ -219,13 +216,6 @@ __global__ __launch_bounds__(256) void k_grm_combine(double *__restrict__ G, int
 // polygenic block
 // ---------------------------------------------------------------------------------------------------------------------------------
 constexpr int PT = 256;
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 __device__ __forceinline__ d2 ld_p(const d2 *__restrict__ a, const d2 *__restrict__ b, int k)
 {
@@ -506,25 +496,17 @@ int hb_grm_build(hb_ctx *c, double lambda, int32_t flags, double *G_host, double
     }
     const double cn2 = (double)C / (nd * nd);
 
-    struct bufs {
-        double *G = nullptr, *d = nullptr;
-        long long *a = nullptr;
-        ~bufs()
-        {
-            if (G) (void)hipFree(G);
-            if (d) (void)hipFree(d);
-            if (a) (void)hipFree(a);
-        }
-    } B;
+    hb_bufs mem;
+    struct { double *G = nullptr, *d = nullptr; long long *a = nullptr; } B;
     if (hipMalloc(reinterpret_cast<void **>(&B.G), sizeof(double) * (size_t)n * (size_t)n) != hipSuccess) {
         (void)hipGetLastError();
         char msg[160];
         snprintf(msg, sizeof msg, "hb_grm_build: hipMalloc: out of memory — the %d x %d matrix needs %.1f GB on the device", n, n, 8e-9 * (double)n * (double)n);
         return hb_fail(HB_ERR_HIP, msg);
     }
-    HB_HIP(hipMalloc(reinterpret_cast<void **>(&B.d), sizeof(double) * (size_t)(n + 1)));
-    HB_HIP(hipMalloc(reinterpret_cast<void **>(&B.a), sizeof(long long) * (size_t)n));
-    HB_HIP(hipMemsetAsync(B.a, 0, sizeof(long long) * (size_t)n, c->stream));
+    mem.dev.push_back(B.G);
+    HB_TRY(mem.get(&B.d, (size_t)(n + 1)));
+    HB_TRY(mem.zeroed(&B.a, (size_t)n, c->stream));
     long long *S = reinterpret_cast<long long *>(B.G);
     const int nt = (n + GT - 1) / GT;
     const unsigned ntri = (unsigned)((long long)nt * (nt + 1) / 2);
@@ -557,7 +539,7 @@ int hb_grm_build(hb_ctx *c, double lambda, int32_t flags, double *G_host, double
     HB_HIP(hipStreamSynchronize(c->stream));
     if (G_dev) {
         *G_dev = B.G;
-        B.G = nullptr;
+        mem.release(B.G); // the caller's from here (hb_grm_free)
     }
     return HB_OK;
 }

@@ -2,6 +2,7 @@
 // Part of the one translation unit hb_kernels.hip (the kernels share device globals and the views defined before them);
 // included there in this order, not compiled on its own.
 #pragma once
+#include "hb_wave.hpp"
 
 // ---- device-side flags of the persistent pipeline ----
 // Every shared word is accessed with relaxed agent-scope atomics (sc1); payloads are written with 4/8-byte
@@ -108,25 +109,6 @@ __device__ __forceinline__ bool wait_ge(unsigned *flags, int word, unsigned want
 // ---------------------------------------------------------------------------------------------
 // reductions
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ long long wave_sum(long long v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // block-wide sum, result valid in every thread; red must hold blockDim.x/64 entries
 template <typename T>
 __device__ __forceinline__ T block_sum(T v, T *red)

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
+#include <chrono>
 #include <string>
 #include <vector>
 #include "../../include/hibayes_gpu.h"
@@ -17,6 +19,55 @@ int hb_fail(int status, const std::string &msg);
         if (_e != hipSuccess)                                                                \
             return hb_fail(HB_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));   \
     } while (0)
+
+// a call that has already reported its failure (hb_fail): pass its status on
+#define HB_TRY(x)             \
+    do {                      \
+        const int _rc = (x);  \
+        if (_rc) return _rc;  \
+    } while (0)
+
+// one line of a verbose run: to the caller's callback, or to stdout
+void hb_line(int verbose, hb_log_fn log, void *log_user, const char *fmt, ...);
+
+using hb_clk = std::chrono::steady_clock;
+inline double hb_since(hb_clk::time_point t0) { return std::chrono::duration<double>(hb_clk::now() - t0).count(); }
+
+// the device and pinned allocations of one call or run, freed on every way out. An owner that also holds a graph or a stream
+// destroys the graph, calls clear() and destroys the stream, in that order.
+struct hb_bufs {
+    std::vector<void *> dev, pinned;
+    hb_bufs() = default;
+    hb_bufs(const hb_bufs &) = delete;
+    hb_bufs &operator=(const hb_bufs &) = delete;
+    ~hb_bufs() { clear(); }
+    void clear()
+    {
+        for (void *q : dev) (void)hipFree(q);
+        for (void *q : pinned) (void)hipHostFree(q);
+        dev.clear();
+        pinned.clear();
+    }
+    template <typename T> int get(T **p, size_t count) // device memory, as hipMalloc leaves it
+    {
+        HB_HIP(hipMalloc(reinterpret_cast<void **>(p), std::max<size_t>(count, 1) * sizeof(T)));
+        dev.push_back(*p);
+        return HB_OK;
+    }
+    template <typename T> int zeroed(T **p, size_t count, hipStream_t s) // device memory, zeroed on stream s
+    {
+        HB_TRY(get(p, count));
+        HB_HIP(hipMemsetAsync(*p, 0, std::max<size_t>(count, 1) * sizeof(T), s));
+        return HB_OK;
+    }
+    template <typename T> int pin(T **p, size_t count) // pinned host memory
+    {
+        HB_HIP(hipHostMalloc(reinterpret_cast<void **>(p), std::max<size_t>(count, 1) * sizeof(T)));
+        pinned.push_back(*p);
+        return HB_OK;
+    }
+    void release(void *q) { dev.erase(std::remove(dev.begin(), dev.end(), q), dev.end()); } // the caller keeps q
+};
 
 // layout of the per-sweep scalar block the kernels accumulate into / the host reads back
 // Words that one workgroup writes through and others read behind a flag — the panels' move counts, the groups' bounds on max |yadj| —

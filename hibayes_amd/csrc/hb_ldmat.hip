@@ -14,8 +14,8 @@
 // row-sorted (row, value) lists per column (k_ld_compact: every other kind, the reference returns sp_mat there).
 // This whole unit is compiled with floating-point contraction off (Makefile and the pragma below): hipcc fuses by default.
 #include "hb_ldm.hpp"
+#include "hb_wave.hpp"
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -23,15 +23,10 @@
 
 #pragma clang fp contract(off)
 
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
-
 int hbk_stats(hb_ctx *c);
 int hbk_unpack2(hb_ctx *c, int col0, int ncols, int8_t *dst);
 
 namespace {
-using clk = std::chrono::steady_clock;
-
 // ---- BigStat (src/tXXmat.cpp:43-77): mean = sum / ind, xx = sqrt(sum_k (x_k - mean)^2), the squares added in row order ----
 // One lane per column (set-up work: m lanes x n dependent adds). X points at column col0; the column sums are k_stats' exact
 // integers (hb_ctx::s1), which is what the reference's fp64 running sum of small integers holds too.
@@ -218,22 +213,6 @@ __global__ __launch_bounds__(256) void k_ld_densify(const int64_t *__restrict__ 
     for (int t = threadIdx.x; t < cnt[j]; t += 256) dense[(size_t)(j0 + j) * (size_t)m + idx[o + t]] = val[o + t];
 }
 
-struct dev_bufs { // freed on every way out of the build
-    std::vector<void *> p;
-    ~dev_bufs()
-    {
-        for (void *q : p)
-            if (q) (void)hipFree(q);
-    }
-    template <typename T>
-    int get(T **out, size_t count)
-    {
-        HB_HIP(hipMalloc(reinterpret_cast<void **>(out), std::max<size_t>(count, 1) * sizeof(T)));
-        p.push_back(*out);
-        return HB_OK;
-    }
-};
-
 int host_reserve(hb_ldm *l, int64_t need)
 {
     if (need <= l->h_cap) return HB_OK;
@@ -257,45 +236,41 @@ int host_reserve(hb_ldm *l, int64_t need)
     return HB_OK;
 }
 
-double since(clk::time_point t0) { return std::chrono::duration<double>(clk::now() - t0).count(); }
-
 int build(hb_ctx *c, const int32_t *chr, bool sparse, double chisq, int64_t strip_bytes, hb_ldm *l)
 {
     const int m = c->m;
     const int64_t ld = c->ld;
     const bool use_chr = chr != nullptr;
-    const auto t_all = clk::now();
-    dev_bufs D;
-    int rc;
-#define TRYB(x) do { rc = (x); if (rc) return rc; } while (0)
+    const auto t_all = hb_clk::now();
+    hb_bufs D; // freed on every way out of the build
     // ---- where the int8 columns are: resident, or unpacked from the 2-bit layout (whole if small, else a window at a time) ----
     int64_t wincols = std::max<int64_t>(LD_T, ((int64_t)1 << 30) / ld / LD_T * LD_T);
     if (const char *ev = getenv("HB_LDM_WINDOW_COLS")) wincols = std::max<int64_t>(LD_T, (int64_t)atoi(ev) / LD_T * LD_T); // (tests: force the windowed path)
     const int8_t *Xfull = c->X;
     int8_t *winA = nullptr, *winB = nullptr;
     if (!Xfull && wincols >= m) {
-        TRYB(D.get(&winA, (size_t)ld * m));
-        TRYB(hbk_unpack2(c, 0, m, winA));
+        HB_TRY(D.get(&winA, (size_t)ld * m));
+        HB_TRY(hbk_unpack2(c, 0, m, winA));
         Xfull = winA;
     }
     // ---- BigStat ----
-    auto t0 = clk::now();
+    auto t0 = hb_clk::now();
     double *d_mean = nullptr, *d_xx = nullptr;
-    TRYB(D.get(&d_mean, m));
-    TRYB(D.get(&d_xx, m));
+    HB_TRY(D.get(&d_mean, m));
+    HB_TRY(D.get(&d_xx, m));
     if (Xfull) {
         hipLaunchKernelGGL(k_ld_stats, dim3((m + 63) / 64), dim3(64), 0, c->stream, Xfull, ld, c->n, 0, m, c->s1, d_mean, d_xx);
     } else {
-        TRYB(D.get(&winB, (size_t)ld * wincols));
+        HB_TRY(D.get(&winB, (size_t)ld * wincols));
         for (int r0 = 0; r0 < m; r0 += (int)wincols) {
             const int nr = (int)std::min<int64_t>(wincols, m - r0);
-            TRYB(hbk_unpack2(c, r0, nr, winB));
+            HB_TRY(hbk_unpack2(c, r0, nr, winB));
             hipLaunchKernelGGL(k_ld_stats, dim3((nr + 63) / 64), dim3(64), 0, c->stream, winB, ld, c->n, r0, nr, c->s1, d_mean, d_xx);
         }
     }
     HB_HIP(hipGetLastError());
     HB_HIP(hipStreamSynchronize(c->stream));
-    l->t_stats = since(t0);
+    l->t_stats = hb_since(t0);
     // ---- column order: by chromosome (stable: a chromosome's markers stay in marker order, so a column's entries, which all
     // lie in its own chromosome, come out row-sorted) where whole columns can be gathered; marker order otherwise ----
     std::vector<int32_t> perm(m);
@@ -303,7 +278,7 @@ int build(hb_ctx *c, const int32_t *chr, bool sparse, double chisq, int64_t stri
     if (use_chr && Xfull) std::stable_sort(perm.begin(), perm.end(), [&](int32_t x, int32_t y) { return chr[x] < chr[y]; });
     const int ntile = (m + LD_T - 1) / LD_T;
     int32_t *d_perm = nullptr, *d_chr = nullptr, *d_tchr = nullptr;
-    TRYB(D.get(&d_perm, m));
+    HB_TRY(D.get(&d_perm, m));
     HB_HIP(hipMemcpy(d_perm, perm.data(), sizeof(int32_t) * m, hipMemcpyHostToDevice));
     if (use_chr) {
         std::vector<int32_t> tc(2 * (size_t)ntile);
@@ -316,8 +291,8 @@ int build(hb_ctx *c, const int32_t *chr, bool sparse, double chisq, int64_t stri
             tc[2 * t] = lo;
             tc[2 * t + 1] = hi;
         }
-        TRYB(D.get(&d_chr, m));
-        TRYB(D.get(&d_tchr, 2 * (size_t)ntile));
+        HB_TRY(D.get(&d_chr, m));
+        HB_TRY(D.get(&d_tchr, 2 * (size_t)ntile));
         HB_HIP(hipMemcpy(d_chr, chr, sizeof(int32_t) * m, hipMemcpyHostToDevice));
         HB_HIP(hipMemcpy(d_tchr, tc.data(), sizeof(int32_t) * tc.size(), hipMemcpyHostToDevice));
     }
@@ -331,18 +306,18 @@ int build(hb_ctx *c, const int32_t *chr, bool sparse, double chisq, int64_t stri
     double *d_strip = nullptr, *d_val = nullptr;
     int32_t *d_idx = nullptr, *d_cnt = nullptr;
     int64_t *d_off = nullptr;
-    TRYB(D.get(&d_strip, scount));
+    HB_TRY(D.get(&d_strip, scount));
     if (compacted) {
-        TRYB(D.get(&d_val, scount));
-        TRYB(D.get(&d_idx, scount));
-        TRYB(D.get(&d_cnt, w));
-        TRYB(D.get(&d_off, w));
+        HB_TRY(D.get(&d_val, scount));
+        HB_TRY(D.get(&d_idx, scount));
+        HB_TRY(D.get(&d_cnt, w));
+        HB_TRY(D.get(&d_off, w));
         l->col_off.assign(m, 0);
         l->col_cnt.assign(m, 0);
     } else {
         HB_HIP(hipHostMalloc(reinterpret_cast<void **>(&l->h_dense), sizeof(double) * (size_t)m * (size_t)m));
     }
-    if (!Xfull && !winA) TRYB(D.get(&winA, (size_t)ld * (size_t)std::min(w, m)));
+    if (!Xfull && !winA) HB_TRY(D.get(&winA, (size_t)ld * (size_t)std::min(w, m)));
     // a dense device copy for the sampler is kept when it fits beside the context and the staging with room to spare
     {
         size_t fr = 0, tot = 0;
@@ -358,36 +333,36 @@ int build(hb_ctx *c, const int32_t *chr, bool sparse, double chisq, int64_t stri
     std::vector<int64_t> off(w);
     for (int c0 = 0; c0 < m; c0 += w) {
         const int ws = std::min(w, m - c0), ntc = (ws + LD_T - 1) / LD_T;
-        t0 = clk::now();
+        t0 = hb_clk::now();
         if (use_chr) HB_HIP(hipMemsetAsync(d_strip, 0, sizeof(double) * (size_t)m * ws, c->stream)); // (tiles across chromosomes are skipped)
         if (Xfull) {
             hipLaunchKernelGGL(kstrip, dim3((unsigned)(ntile * ntc)), dim3(1024), 0, c->stream, Xfull, Xfull, ld, m, d_perm, c0, ws, 0,
                                ntile, d_tchr, e, d_strip);
         } else { // perm is the identity here: position = marker
-            TRYB(hbk_unpack2(c, c0, ws, winA));
+            HB_TRY(hbk_unpack2(c, c0, ws, winA));
             for (int r0 = 0; r0 < m; r0 += (int)wincols) {
                 const int nr = (int)std::min<int64_t>(wincols, m - r0), nrt = (nr + LD_T - 1) / LD_T;
-                TRYB(hbk_unpack2(c, r0, nr, winB));
+                HB_TRY(hbk_unpack2(c, r0, nr, winB));
                 hipLaunchKernelGGL(kstrip, dim3((unsigned)(nrt * ntc)), dim3(1024), 0, c->stream, winA - (int64_t)c0 * ld,
                                    winB - (int64_t)r0 * ld, ld, m, d_perm, c0, ws, r0 / LD_T, nrt, d_tchr, e, d_strip);
             }
         }
         HB_HIP(hipGetLastError());
         HB_HIP(hipStreamSynchronize(c->stream));
-        l->t_strips += since(t0);
+        l->t_strips += hb_since(t0);
         l->n_strips++;
         if (l->d_dense) {
             hipLaunchKernelGGL(k_ld_scatter, dim3((m + 255) / 256, ws), dim3(256), 0, c->stream, d_strip, m, d_perm, c0, l->d_dense);
             HB_HIP(hipGetLastError());
         }
         if (!compacted) {
-            t0 = clk::now();
+            t0 = hb_clk::now();
             HB_HIP(hipMemcpyAsync(l->h_dense + (size_t)c0 * m, d_strip, sizeof(double) * (size_t)m * ws, hipMemcpyDeviceToHost, c->stream));
             HB_HIP(hipStreamSynchronize(c->stream));
-            l->t_xfer += since(t0);
+            l->t_xfer += hb_since(t0);
             continue;
         }
-        t0 = clk::now();
+        t0 = hb_clk::now();
         hipLaunchKernelGGL(k_ld_compact, dim3((ws + 3) / 4), dim3(256), 0, c->stream, d_strip, m, ws, (const int64_t *)nullptr, d_cnt, d_idx, d_val);
         HB_HIP(hipGetLastError());
         HB_HIP(hipMemcpyAsync(cnt.data(), d_cnt, sizeof(int32_t) * ws, hipMemcpyDeviceToHost, c->stream));
@@ -401,9 +376,9 @@ int build(hb_ctx *c, const int32_t *chr, bool sparse, double chisq, int64_t stri
         hipLaunchKernelGGL(k_ld_compact, dim3((ws + 3) / 4), dim3(256), 0, c->stream, d_strip, m, ws, (const int64_t *)d_off, d_cnt, d_idx, d_val);
         HB_HIP(hipGetLastError());
         HB_HIP(hipStreamSynchronize(c->stream));
-        l->t_compact += since(t0);
-        t0 = clk::now();
-        TRYB(host_reserve(l, l->h_used + tot));
+        l->t_compact += hb_since(t0);
+        t0 = hb_clk::now();
+        HB_TRY(host_reserve(l, l->h_used + tot));
         if (tot) {
             HB_HIP(hipMemcpyAsync(l->h_idx + l->h_used, d_idx, sizeof(int32_t) * (size_t)tot, hipMemcpyDeviceToHost, c->stream));
             HB_HIP(hipMemcpyAsync(l->h_val + l->h_used, d_val, sizeof(double) * (size_t)tot, hipMemcpyDeviceToHost, c->stream));
@@ -414,7 +389,7 @@ int build(hb_ctx *c, const int32_t *chr, bool sparse, double chisq, int64_t stri
             l->col_cnt[perm[c0 + k]] = cnt[k];
         }
         l->h_used += tot;
-        l->t_xfer += since(t0);
+        l->t_xfer += hb_since(t0);
     }
     HB_HIP(hipStreamSynchronize(c->stream));
     // ---- the diagonal, for SBayesD()'s first lines ----
@@ -430,9 +405,8 @@ int build(hb_ctx *c, const int32_t *chr, bool sparse, double chisq, int64_t stri
         }
         l->nnz = l->h_used;
     }
-    l->seconds = since(t_all);
+    l->seconds = hb_since(t_all);
     return HB_OK;
-#undef TRYB
 }
 } // namespace
 
@@ -442,9 +416,8 @@ int hb_ldm_device_dense(hb_ldm *l, const double **out)
     if (!l->d_dense) {
         const int m = l->m;
         double *d = nullptr;
-        HB_HIP(hipMalloc(reinterpret_cast<void **>(&d), sizeof(double) * (size_t)m * (size_t)m));
-        dev_bufs D;
-        D.p.push_back(d); // (released below once the copy is complete)
+        hb_bufs D;
+        HB_TRY(D.get(&d, (size_t)m * (size_t)m)); // (released below once the copy is complete)
         if (l->kind == HB_LDM_KIND_DENSE) {
             HB_HIP(hipMemcpy(d, l->h_dense, sizeof(double) * (size_t)m * (size_t)m, hipMemcpyHostToDevice));
         } else {
@@ -484,7 +457,7 @@ int hb_ldm_device_dense(hb_ldm *l, const double **out)
                 j0 = j1;
             }
         }
-        D.p[0] = nullptr;
+        D.release(d);
         l->d_dense = d;
     }
     *out = l->d_dense;
@@ -551,7 +524,7 @@ int hb_ldm_device_csc(hb_ldm *l, hb_ldm_csc *out)
                 l->grp_hi[g] = hi;
             }
         }
-        dev_bufs D;
+        hb_bufs D;
         int64_t *d_cp = nullptr, *d_run = nullptr;
         int32_t *d_ri = nullptr, *d_cnt = nullptr, *d_runn = nullptr;
         double *d_va = nullptr;
@@ -565,7 +538,7 @@ int hb_ldm_device_csc(hb_ldm *l, hb_ldm_csc *out)
         HB_HIP(hipMemcpy(d_runn, runn.data(), sizeof(int32_t) * m, hipMemcpyHostToDevice));
         HB_HIP(hipMemcpy(d_ri, ri.data(), sizeof(int32_t) * ri.size(), hipMemcpyHostToDevice));
         HB_HIP(hipMemcpy(d_va, va.data(), sizeof(double) * va.size(), hipMemcpyHostToDevice));
-        D.p.clear(); // kept: the handle owns them from here
+        D.dev.clear(); // kept: the handle owns them from here
         l->d_run = d_run;
         l->d_ri = d_ri;
         l->d_cnt = d_cnt;

@@ -11,12 +11,11 @@
 // hb_bayes_run() == hb_run_create() + hb_run_step(niter) + hb_run_finish(); bench.py drives the
 // three separately so that exactly K iterations sit between its barriers.
 #include "hb_internal.hpp"
+#include "hb_model.hpp"
 #include "hb_rng.hpp"
 #include "hb_runplan.hpp"
 #include <algorithm>
-#include <chrono>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <map>
@@ -30,20 +29,6 @@ extern "C" int hb_comm_world(const hb_comm *c);
 extern "C" int hb_comm_rank(const hb_comm *c);
 
 namespace {
-
-using clk = std::chrono::steady_clock;
-
-double arma_sum(const double *v, size_t n)
-{
-    double a1 = 0.0, a2 = 0.0;
-    size_t j;
-    for (j = 1; j < n; j += 2) {
-        a1 += v[j - 1];
-        a2 += v[j];
-    }
-    if ((j - 1) < n) a1 += v[j - 1];
-    return a1 + a2;
-}
 
 // arma::var, N-1 (two-pass)
 double var_n1(const double *v, size_t n)
@@ -123,17 +108,7 @@ struct hb_run {
         if (c && own_ctx) hb_ctx_destroy(c);
     }
 
-    void line(const char *fmt, ...) const
-    {
-        if (!a.verbose) return;
-        char buf[1024];
-        va_list ap;
-        va_start(ap, fmt);
-        vsnprintf(buf, sizeof(buf), fmt, ap);
-        va_end(ap);
-        if (a.log) a.log(buf, a.log_user);
-        else { fputs(buf, stdout); fputc('\n', stdout); fflush(stdout); }
-    }
+    template <typename... A> void line(const char *fmt, A... xs) const { hb_line(a.verbose, a.log, a.log_user, fmt, xs...); }
 
     // sum over ranks of xbuf[0 .. xcount), on the sweep stream: RCCL inside the library when a communicator was given
     // (nothing but an enqueue), else the host language's callback (needs the stream quiesced on both sides)
@@ -288,7 +263,7 @@ int hb_run::row_sums(double *sr, double *sr2, double *varu)
 
 int hb_run::setup(const hb_bayes_args *args)
 {
-    const auto t0 = clk::now();
+    const auto t0 = hb_clk::now();
     a = *args;
     // the environment's switches, each read here and nowhere else
     if (const char *e = getenv("HB_RECOVER")) recover_on = atoi(e) != 0;
@@ -304,7 +279,7 @@ int hb_run::setup(const hb_bayes_args *args)
     console();
     rc = start_chain();
     if (rc) return rc;
-    setup_seconds = std::chrono::duration<double>(clk::now() - t0).count();
+    setup_seconds = hb_since(t0);
     return HB_OK;
 }
 
@@ -328,24 +303,10 @@ int hb_run::take_args()
     if (have_x && a.ctx) return hb_fail(HB_ERR_INVALID, "hb_bayes_run: a pre-loaded ctx excludes X_f64 / X_i8");
     if ((a.X_f64 && a.ld_f64 < n) || (a.X_i8 && a.ld_i8 < n)) return hb_fail(HB_ERR_INVALID, "Number of individuals not equals.");
     if (a.ctx && (a.ctx->n != n || a.ctx->m != m)) return hb_fail(HB_ERR_INVALID, "Number of individuals not equals.");
-    model_index = model == "BayesRR" ? 1 : model == "BayesA" ? 2 : (model == "BayesB" || model == "BayesBpi") ? 3
-                : (model == "BayesC" || model == "BayesCpi" || model == "BSLMM") ? 4 : model == "BayesL" ? 5 : 6;
-    fixpi = (model == "BayesB" || model == "BayesC");
-    if (a.n_pi < 2 || !a.Pi) return hb_fail(HB_ERR_INVALID, "Pi should be a vector.");
-    if (a.n_pi > HB_MAX_FOLD) return hb_fail(HB_ERR_UNSUPPORTED, "more mixture classes than HB_MAX_FOLD");
-    Pi.assign(a.Pi, a.Pi + a.n_pi);
-    n_pi = a.n_pi;
-    if (arma_sum(Pi.data(), Pi.size()) != 1) return hb_fail(HB_ERR_INVALID, "sum of Pi should be 1.");
-    if (Pi[0] == 1) return hb_fail(HB_ERR_INVALID, "all markers have no effect size.");
-    for (double p : Pi)
-        if (p < 0 || p > 1) return hb_fail(HB_ERR_INVALID, "elements of Pi should be at the range of [0, 1]");
-    if (a.fold) fold_.assign(a.fold, a.fold + a.n_fold);
-    else {
-        if (model == "BayesR") return hb_fail(HB_ERR_INVALID, "'fold' should be provided for BayesR model.");
-        fold_.assign(2, 0.0);
-    }
-    if ((int)fold_.size() != n_pi) return hb_fail(HB_ERR_INVALID, "length of Pi and fold not equals.");
-    n_fold = (int)fold_.size();
+    model_index = model == "BSLMM" ? 4 : hb_model_index(model);
+    std::string err;
+    if (int rc = hb_mixture_take(model, a.Pi, a.n_pi, a.fold, a.n_fold, Pi, fold_, err)) return hb_fail(rc, err);
+    n_pi = n_fold = a.n_pi;
     // BSLMM runs with both Kival and Ki, or on a context prepared by hb_ctx_poly_setup; anything else about them keeps the refusal (and its
     // text, which tests pin) from before the block existed
     poly = model == "BSLMM" && ((a.Ki && a.Kival) || (!a.Ki && !a.Kival && a.ctx && a.ctx->poly));
@@ -455,35 +416,13 @@ int hb_run::encode_random_effects()
 int hb_run::take_model_args()
 {
     // ---- :288-296 ----
-    always_in = (model_index == 1 || model_index == 2 || model_index == 5);
-    if (always_in) {
-        Pi[0] = 0;
-        Pi[1] = 1;
-        fixpi = true;
-    } else if (model != "BayesR" && n_pi != 2) {
-        return hb_fail(HB_ERR_INVALID, "length of Pi should be 2, the first value is the proportion of non-effect markers.");
-    }
+    std::string err;
+    if (int rc = hb_mixture_always_in(model, model_index, Pi, fixpi, always_in, err)) return hb_fail(rc, err);
     dfvara_ = a.has_dfvg ? a.dfvg : 4; // :319-326
     if (dfvara_ <= 2) return hb_fail(HB_ERR_INVALID, "dfvg should not be less than 2.");
     if (niter < nburn) return hb_fail(HB_ERR_INVALID, "Number of total iteration ('niter') shold be larger than burn-in ('nburn').");
-    // BayesR: the device evaluates the class boundaries as nested thresholds on q = rhs^2, which needs the non-null classes in
-    // order of increasing variance (P(class <= c | q) is then decreasing in q for every c). The reference takes `fold` in any
-    // order (src/Bayes.cpp:743-815) and walks the classes as given (:773-781) — with another order the same uniform picks another
-    // class, so no formulation can be that walk draw for draw AND monotone. The run is therefore the reference's chain for the
-    // classes SORTED by fold (the same posterior: the mixture does not depend on how its components are numbered); cls_of[]
-    // maps the internal class index back to the caller's for everything reported: pi, MCMCsamples$pi, the progress line.
-    cls_of.resize(n_fold);
-    for (int k = 0; k < n_fold; k++) cls_of[k] = k;
-    if (model_index == 6) {
-        std::stable_sort(cls_of.begin() + 1, cls_of.end(), [&](int x, int z) { return fold_[x] < fold_[z]; }); // class 0 is the null class (:759)
-        std::vector<double> f2(n_fold), p2(n_fold);
-        for (int k = 0; k < n_fold; k++) { f2[k] = fold_[cls_of[k]]; p2[k] = Pi[cls_of[k]]; }
-        fold_ = f2;
-        Pi = p2;
-        for (int k = 2; k < n_fold; k++)
-            if (!(fold_[k] > fold_[k - 1]))
-                return hb_fail(HB_ERR_UNSUPPORTED, "BayesR on the GPU path needs distinct 'fold' values for the non-null classes");
-    }
+    // BayesR runs as the chain of its classes sorted by fold; cls_of[] maps a class back to the caller's index (hb_model.hpp)
+    if (int rc = hb_mixture_order(model_index, Pi, fold_, cls_of, err)) return hb_fail(rc, err);
     if (a.windindx) wind.assign(a.windindx, a.windindx + m);
     if (a.g_init) {
         g_init.assign(a.g_init, a.g_init + m);
@@ -837,7 +776,7 @@ int hb_run::step()
         done = true;
         return HB_OK;
     }
-    const auto t0 = clk::now();
+    const auto t0 = hb_clk::now();
     int rc;
     HB_HIP(hipSetDevice(c->device));
     if (a.interrupt && a.interrupt(a.interrupt_user)) return hb_fail(HB_ERR_INTERRUPT, "interrupted");
@@ -1020,50 +959,11 @@ int hb_run::step()
         vb = ps[0];
     }
 
-    // hyper-parameters after the sweep
-    auto draw_pi = [&]() { // rdirichlet_sample, src/stats.cpp:69-76
-        std::vector<double> xn(n_fold);
-        for (int j = 0; j < n_fold; j++) xn[j] = hs.gamma(fold_snp_num[j] + 1, 1.0);
-        const double sx = arma_sum(xn.data(), xn.size());
-        for (int j = 0; j < n_fold; j++) Pi[j] = xn[j] / sx;
-    };
-    switch (model_index) {
-    case 1: // :603
-        varg = (so.sum_g2 + s2varg_ * dfvara_) / hs.chisq(dfvara_ + (double)m_global - nvar0);
-        break;
-    case 2: break;
-    case 3: // :666-669
-        fold_snp_num[1] = so.class_count[1];
-        fold_snp_num[0] = (double)m_global - nvar0 - fold_snp_num[1];
-        NnzSnp = (long long)fold_snp_num[1];
-        if (!fixpi) draw_pi();
-        break;
-    case 4: // :710-716
-        fold_snp_num[1] = so.class_count[1];
-        fold_snp_num[0] = (double)m_global - nvar0 - fold_snp_num[1];
-        NnzSnp = (long long)fold_snp_num[1];
-        varg = (so.sum_g2 + s2varg_ * dfvara_) / hs.chisq(dfvara_ + (double)NnzSnp);
-        if (poly) va = varg; // :715
-        if (!fixpi) draw_pi();
-        break;
-    case 5: { // :738-741
-        const double shape = shape0 + (double)m_global - nvar0;
-        const double rate = rate0 + so.sum_vargL / 2;
-        lambda2 = hs.gamma(shape, 1 / rate);
-        lambda = std::sqrt(lambda2);
-        break;
-    }
-    case 6: { // :803-814
-        double nz = 0;
-        for (int j = 0; j < n_fold; j++) fold_snp_num[j] = so.class_count[j];
-        for (int j = 1; j < n_fold; j++) nz += fold_snp_num[j];
-        NnzSnp = (long long)nz;
-        varg = (so.sum_g2 + s2varg_ * dfvara_) / hs.chisq(dfvara_ + (double)NnzSnp);
-        for (int j = 0; j < n_fold; j++) vara_fold[j] = varg * fold_[j];
-        if (!fixpi) draw_pi(); // class_count[0] already excludes the nvar0 monomorphic markers (:813)
-        break;
-    }
-    }
+    // hyper-parameters after the sweep (hb_model.hpp)
+    hb_draw_hyper(hs, hb_hyper_prior{model_index, n_fold, fixpi, dfvara_, s2varg_, shape0, rate0, fold_.data()},
+                  hb_hyper_sums{so.sum_g2, so.sum_vargL, so.class_count, (double)m_global, (double)nvar0},
+                  hb_hyper_state{varg, lambda, lambda2, NnzSnp, Pi.data(), vara_fold.data(), fold_snp_num.data()});
+    if (poly) va = varg; // :715
     vara_ = so.var_u;                                                       // :819
     vare_ = (sum_r2 + s2vare_ * dfvare_) / hs.chisq(ng + dfvare_);  // :823
 
@@ -1112,7 +1012,7 @@ int hb_run::step()
         hsq_sum += vara_ / vt;
         count++;
     }
-    loop_seconds += std::chrono::duration<double>(clk::now() - t0).count();
+    loop_seconds += hb_since(t0);
 
     if (a.verbose && a.outfreq > 0 && (iter + 1) % a.outfreq == 0) { // :884-914
         const int tt = (int)std::floor(loop_seconds / (iter + 1) * (niter - iter));
@@ -1232,11 +1132,7 @@ int hb_run::finish(hb_bayes_out *o)
     if (o->e) std::memcpy(o->e, e.data(), sizeof(double) * n);
     if (o->pip) {
         if (always_in) for (int i = 0; i < m; i++) o->pip[i] = 1.0; // :1026-1027
-        else for (int i = 0; i < m; i++) {
-            double p = nz[i] / nzct;
-            if (p == 1) p = (nzct - 1) / (double)nzct; // :1030
-            o->pip[i] = p;
-        }
+        else for (int i = 0; i < m; i++) o->pip[i] = hb_pip(nz[i], nzct); // :1030
     }
     if (nw && o->gwas) { // :1034-1038; windows must not straddle shards (hibayes_amd/dist.py checks)
         std::vector<double> w(nw);
@@ -1246,11 +1142,7 @@ int hb_run::finish(hb_bayes_out *o)
             rc = allreduce_chunks(w.data(), w.size());
             if (rc) return rc;
         }
-        for (int k = 0; k < nw; k++) {
-            double p = w[k] / nzct;
-            if (p == 1) p = (nzct - 1) / (double)nzct;
-            o->gwas[k] = p;
-        }
+        for (int k = 0; k < nw; k++) o->gwas[k] = hb_pip(w[k], nzct);
     }
     o->nzct = nzct;
     auto cp = [](double *dst, const std::vector<double> &src) { if (dst && !src.empty()) std::memcpy(dst, src.data(), sizeof(double) * src.size()); };

@@ -5,25 +5,21 @@
 // the sweep of hb_sbayes_sparse.hip: what differs on the host is varediff (:131-141), vara and vary handed to the device every
 // sweep, the sum of squared effects taken from the end-of-sweep reduction, and one console line (:222).
 #include "hb_internal.hpp"
-#include "hb_armasum.hpp"
 #include "hb_ldm.hpp"
+#include "hb_model.hpp"
 #include "hb_rng.hpp"
 #include "hb_sbayes_sparse.hpp"
 #include <algorithm>
-#include <chrono>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 
 namespace {
-using clk = std::chrono::steady_clock;
-
 struct sb_run {
     hb_ss_dev s;
     hb_sb_dev &d = s.b;
     double *h_ex = nullptr;
-    std::vector<void *> bufs;
+    hb_bufs mem;
     hipGraph_t graph = nullptr;
     hipGraphExec_t gexec = nullptr;
     double *h_acc = nullptr;
@@ -32,21 +28,10 @@ struct sb_run {
     {
         if (gexec) (void)hipGraphExecDestroy(gexec);
         if (graph) (void)hipGraphDestroy(graph);
-        for (void *p : bufs)
-            if (p) (void)hipFree(p);
-        if (h_acc) (void)hipHostFree(h_acc);
-        if (h_in) (void)hipHostFree(h_in);
-        if (h_ex) (void)hipHostFree(h_ex);
+        mem.clear();
         if (d.stream) (void)hipStreamDestroy(d.stream);
     }
-    template <typename T>
-    int alloc(T **p, size_t count)
-    {
-        HB_HIP(hipMalloc(reinterpret_cast<void **>(p), std::max<size_t>(count, 1) * sizeof(T)));
-        bufs.push_back(*p);
-        HB_HIP(hipMemsetAsync(*p, 0, std::max<size_t>(count, 1) * sizeof(T), d.stream));
-        return HB_OK;
-    }
+    template <typename T> int alloc(T **p, size_t count) { return mem.zeroed(p, count, d.stream); }
 };
 } // namespace
 
@@ -55,91 +40,44 @@ struct sb_run {
 static int sbayes_run(const hb_sbayes_args *args, hb_ldm *H, hb_sbayes_out *o, bool sparse = false)
 {
     if (!args || !o) return hb_fail(HB_ERR_INVALID, "hb_sbayes_run: null argument");
-    const auto t_setup = clk::now();
+    const auto t_setup = hb_clk::now();
     const hb_sbayes_args &a = *args;
     const int m = a.m;
     if (H ? (m < 1 || !a.sumstat || a.ldm || a.ld_sumstat < m || H->m != m)
           : (m < 1 || !a.sumstat || !a.ldm || a.ld_sumstat < m || a.ld_ldm < m)) return hb_fail(HB_ERR_INVALID, "Number of SNPs not equals."); // :29-31
     if (!a.model) return hb_fail(HB_ERR_INVALID, "hb_sbayes_run: model is NULL");
     const std::string model = a.model;
-    auto line = [&](const char *fmt, ...) {
-        if (!a.verbose) return;
-        char buf[1024];
-        va_list ap;
-        va_start(ap, fmt);
-        vsnprintf(buf, sizeof(buf), fmt, ap);
-        va_end(ap);
-        if (a.log) a.log(buf, a.log_user);
-        else { fputs(buf, stdout); fputc('\n', stdout); fflush(stdout); }
-    };
-    // ---- validation and sizes, :28-74, same order and texts ----
-    const int model_index = model == "BayesRR" ? 1 : model == "BayesA" ? 2 : (model == "BayesB" || model == "BayesBpi") ? 3
-                          : (model == "BayesC" || model == "BayesCpi") ? 4 : model == "BayesL" ? 5 : 6;
+    auto line = [&](const char *fmt, auto... xs) { hb_line(a.verbose, a.log, a.log_user, fmt, xs...); };
+    // ---- validation and sizes, :28-74, same order and texts (hb_model.hpp) ----
+    const int model_index = hb_model_index(model);
     const double *ss = a.sumstat;
     const int64_t lds = a.ld_sumstat;
-    int n;
-    {
-        double s = 0;
-        int c = 0;
-        for (int k = 0; k < m; k++)
-            if (std::isfinite(ss[3 * lds + k])) { s += ss[3 * lds + k]; c++; }
-        n = (int)(s / std::max(1, c)); // :33-34 int n = mean(finite N)
-    }
-    bool fixpi = (model == "BayesB" || model == "BayesC");
-    if (a.n_pi < 2 || !a.Pi) return hb_fail(HB_ERR_INVALID, "Pi should be a vector.");
-    if (a.n_pi > HB_MAX_FOLD) return hb_fail(HB_ERR_UNSUPPORTED, "more mixture classes than HB_MAX_FOLD");
-    std::vector<double> Pi(a.Pi, a.Pi + a.n_pi);
+    const int n = hb_sumstat_n(ss, lds, m); // :33-34
+    std::string err;
+    std::vector<double> Pi, fold_;
+    std::vector<int> cls_of;
+    bool fixpi = false, always_in = false;
+    int rc = hb_mixture_take(model, a.Pi, a.n_pi, a.fold, a.n_fold, Pi, fold_, err);
+    if (rc) return hb_fail(rc, err);
     const int n_fold = a.n_pi;
-    if (arma_sum(Pi.data(), Pi.size()) != 1) return hb_fail(HB_ERR_INVALID, "sum of Pi should be 1.");
-    if (Pi[0] == 1) return hb_fail(HB_ERR_INVALID, "all markers have no effect size.");
-    for (double p : Pi)
-        if (p < 0 || p > 1) return hb_fail(HB_ERR_INVALID, "elements of Pi should be at the range of [0, 1]");
-    std::vector<double> fold_(n_fold, 0.0);
-    if (a.fold) {
-        if (a.n_fold != n_fold) return hb_fail(HB_ERR_INVALID, "length of Pi and fold not equals.");
-        fold_.assign(a.fold, a.fold + n_fold);
-    } else {
-        if (model == "BayesR") return hb_fail(HB_ERR_INVALID, "'fold' should be provided for BayesR model.");
-        if (n_fold != 2) return hb_fail(HB_ERR_INVALID, "length of Pi and fold not equals.");
-    }
     const int niter = a.niter, nburn = a.nburn, thin = a.thin;
     if (thin < 1) return hb_fail(HB_ERR_INVALID, "hb_sbayes_run: thin must be >= 1");
     const int n_records = std::max(0, (niter - nburn) / thin);
-    const bool always_in = (model_index == 1 || model_index == 2 || model_index == 5);
-    long long NnzSnp = 0;
-    if (always_in) {
-        NnzSnp = m;
-        Pi[0] = 0;
-        Pi[1] = 1;
-        fixpi = true;
-    } else if (model != "BayesR" && n_fold != 2) {
-        return hb_fail(HB_ERR_INVALID, "length of Pi should be 2, the first value is the proportion of non-effect markers.");
-    }
-    // BayesR with `fold` in any order: the run is the chain of the classes sorted by fold, reported in the caller's order (see hb_run.hip)
-    std::vector<int> cls_of(n_fold);
-    for (int k = 0; k < n_fold; k++) cls_of[k] = k;
-    if (model_index == 6) {
-        std::stable_sort(cls_of.begin() + 1, cls_of.end(), [&](int x, int z) { return fold_[x] < fold_[z]; });
-        std::vector<double> f2(n_fold), p2(n_fold);
-        for (int k = 0; k < n_fold; k++) { f2[k] = fold_[cls_of[k]]; p2[k] = Pi[cls_of[k]]; }
-        fold_ = f2;
-        Pi = p2;
-        for (int k = 2; k < n_fold; k++)
-            if (!(fold_[k] > fold_[k - 1]))
-                return hb_fail(HB_ERR_UNSUPPORTED, "BayesR on the GPU path needs distinct 'fold' values for the non-null classes");
-    }
+    rc = hb_mixture_always_in(model, model_index, Pi, fixpi, always_in, err);
+    if (!rc) rc = hb_mixture_order(model_index, Pi, fold_, cls_of, err);
+    if (rc) return hb_fail(rc, err);
+    long long NnzSnp = always_in ? m : 0;
     // ---- :95-115 ----
     std::vector<double> vx(m), xpx(m), xy(m, 0.0), yyi(m, 0.0), ifest(m, 1.0);
     for (int i = 0; i < m; i++) {
         vx[i] = H ? H->diag[i] : a.ldm[(size_t)i * a.ld_ldm + i];
         xpx[i] = vx[i] * n;
     }
-    int count_y = 0, nvar0 = 0;
+    int count_y = 0;
     for (int k = 0; k < m; k++) {
         const double b = ss[1 * lds + k], se = ss[2 * lds + k], N = ss[3 * lds + k];
         if (std::isnan(b) || std::isnan(se) || std::isnan(N)) {
             ifest[k] = 0.0;
-            nvar0++;
         } else {
             xy[k] = xpx[k] * b;
             yyi[k] = xpx[k] * (b * b + (N - 2) * se * se);
@@ -186,52 +124,50 @@ static int sbayes_run(const hb_sbayes_args *args, hb_ldm *H, hb_sbayes_out *o, b
     d.n = n;
     d.seed = a.seed;
     d.nw = nw;
-    int rc;
-#define TRYA(x) do { rc = (x); if (rc) return rc; } while (0)
     if (sparse) { // adopted, not owned; nothing m x m exists on this route
-        TRYA(hb_ldm_device_csc(H, &R.s.csc));
-        TRYA(R.alloc(&R.s.varediff, d.m_pad));
-        TRYA(R.alloc(&R.s.varei, d.m_pad));
-        TRYA(R.alloc(&R.s.vxt, d.m_pad));
-        TRYA(R.alloc(&R.s.sgn, d.m_pad));
-        TRYA(R.alloc(&R.s.ex, 2));
-        TRYA(R.alloc(&R.s.gtab, SS_GS));
-        TRYA(R.alloc(&R.s.rd, 2));
-        TRYA(R.alloc(&R.s.cursor, d.m_pad));
-        HB_HIP(hipHostMalloc(reinterpret_cast<void **>(&R.h_ex), sizeof(double) * 2));
+        HB_TRY(hb_ldm_device_csc(H, &R.s.csc));
+        HB_TRY(R.alloc(&R.s.varediff, d.m_pad));
+        HB_TRY(R.alloc(&R.s.varei, d.m_pad));
+        HB_TRY(R.alloc(&R.s.vxt, d.m_pad));
+        HB_TRY(R.alloc(&R.s.sgn, d.m_pad));
+        HB_TRY(R.alloc(&R.s.ex, 2));
+        HB_TRY(R.alloc(&R.s.gtab, SS_GS));
+        HB_TRY(R.alloc(&R.s.rd, 2));
+        HB_TRY(R.alloc(&R.s.cursor, d.m_pad));
+        HB_TRY(R.mem.pin(&R.h_ex, 2));
         HB_HIP(hipMemcpyAsync(R.s.vxt, vx.data(), sizeof(double) * m, hipMemcpyHostToDevice, d.stream));
-        TRYA(hbk_ss_varediff(&R.s));
+        HB_TRY(hbk_ss_varediff(&R.s));
     } else if (H) { // adopted, not owned: the sweep only reads it
         const double *dl = nullptr;
-        TRYA(hb_ldm_device_dense(H, &dl));
+        HB_TRY(hb_ldm_device_dense(H, &dl));
         d.ldm = const_cast<double *>(dl);
     } else {
-        TRYA(R.alloc(&d.ldm, (size_t)m * m));
+        HB_TRY(R.alloc(&d.ldm, (size_t)m * m));
     }
-    TRYA(R.alloc(&d.r_hat, d.m_pad));
-    TRYA(R.alloc(&d.xy, d.m_pad));
-    TRYA(R.alloc(&d.g, d.m_pad));
-    TRYA(R.alloc(&d.xpx, d.m_pad));
-    TRYA(R.alloc(&d.vx, d.m_pad));
-    TRYA(R.alloc(&d.vargL, d.m_pad));
-    TRYA(R.alloc(&d.thr, (size_t)d.m_pad * (HB_MAX_FOLD - 1)));
-    TRYA(R.alloc(&d.invv, (size_t)d.m_pad * (HB_MAX_FOLD - 1)));
-    TRYA(R.alloc(&d.sdz, (size_t)d.m_pad * (HB_MAX_FOLD - 1)));
-    TRYA(R.alloc(&d.acc, HB_ACC_N));
-    TRYA(R.alloc(&d.ev_gi, 512)); // SB_GS (hb_sbayes.hpp): the moves of one group
-    TRYA(R.alloc(&d.ev_col, 512));
-    TRYA(R.alloc(&d.ev_n, 1));
-    TRYA(R.alloc(&d.tracker, d.m_pad));
-    TRYA(R.alloc(&d.nzrate, d.m_pad));
-    TRYA(R.alloc(&d.d_in, 1));
+    HB_TRY(R.alloc(&d.r_hat, d.m_pad));
+    HB_TRY(R.alloc(&d.xy, d.m_pad));
+    HB_TRY(R.alloc(&d.g, d.m_pad));
+    HB_TRY(R.alloc(&d.xpx, d.m_pad));
+    HB_TRY(R.alloc(&d.vx, d.m_pad));
+    HB_TRY(R.alloc(&d.vargL, d.m_pad));
+    HB_TRY(R.alloc(&d.thr, (size_t)d.m_pad * (HB_MAX_FOLD - 1)));
+    HB_TRY(R.alloc(&d.invv, (size_t)d.m_pad * (HB_MAX_FOLD - 1)));
+    HB_TRY(R.alloc(&d.sdz, (size_t)d.m_pad * (HB_MAX_FOLD - 1)));
+    HB_TRY(R.alloc(&d.acc, HB_ACC_N));
+    HB_TRY(R.alloc(&d.ev_gi, 512)); // SB_GS (hb_sbayes.hpp): the moves of one group
+    HB_TRY(R.alloc(&d.ev_col, 512));
+    HB_TRY(R.alloc(&d.ev_n, 1));
+    HB_TRY(R.alloc(&d.tracker, d.m_pad));
+    HB_TRY(R.alloc(&d.nzrate, d.m_pad));
+    HB_TRY(R.alloc(&d.d_in, 1));
     if (nw) {
-        TRYA(R.alloc(&d.wind, d.m_pad));
-        TRYA(R.alloc(&d.wflag, nw));
-        TRYA(R.alloc(&d.wppa, nw));
+        HB_TRY(R.alloc(&d.wind, d.m_pad));
+        HB_TRY(R.alloc(&d.wflag, nw));
+        HB_TRY(R.alloc(&d.wppa, nw));
         HB_HIP(hipMemcpyAsync(d.wind, a.windindx, sizeof(uint32_t) * m, hipMemcpyHostToDevice, d.stream));
     }
-    HB_HIP(hipHostMalloc(reinterpret_cast<void **>(&R.h_acc), sizeof(double) * HB_ACC_N));
-    HB_HIP(hipHostMalloc(reinterpret_cast<void **>(&R.h_in), sizeof(hb_sweep_in)));
+    HB_TRY(R.mem.pin(&R.h_acc, HB_ACC_N));
+    HB_TRY(R.mem.pin(&R.h_in, 1));
     if (!H) HB_HIP(hipMemcpy2DAsync(d.ldm, sizeof(double) * m, a.ldm, sizeof(double) * a.ld_ldm, sizeof(double) * m, m, hipMemcpyHostToDevice, d.stream));
     HB_HIP(hipMemcpyAsync(d.xy, xy.data(), sizeof(double) * m, hipMemcpyHostToDevice, d.stream));
     HB_HIP(hipMemcpyAsync(d.r_hat, xy.data(), sizeof(double) * m, hipMemcpyHostToDevice, d.stream)); // :108 r_hat = xy
@@ -246,7 +182,7 @@ static int sbayes_run(const hb_sbayes_args *args, hb_ldm *H, hb_sbayes_out *o, b
     o->count_y = count_y;
     o->nw = nw;
     o->n_records = n_records;
-    const double setup_seconds = std::chrono::duration<double>(clk::now() - t_setup).count();
+    const double setup_seconds = hb_since(t_setup);
 
     // ---- console, :190-246 ----
     line("Prior parameters:");
@@ -271,7 +207,7 @@ static int sbayes_run(const hb_sbayes_args *args, hb_ldm *H, hb_sbayes_out *o, b
     if (a.store_alpha) s_alpha.assign((size_t)n_records * m, 0.0);
     double vara_sum = 0, vare_sum = 0, hsq_sum = 0, events_sum = 0;
     int count = 0, nzct = 0, iter = 0;
-    const auto t_loop = clk::now();
+    const auto t_loop = hb_clk::now();
     for (iter = 0; iter < niter; iter++) {
         if (a.interrupt && a.interrupt(a.interrupt_user)) return hb_fail(HB_ERR_INTERRUPT, "interrupted");
         hb_stream hs(a.seed, hb_sub(HB_PURPOSE_HOST, (uint64_t)iter), 0);
@@ -309,50 +245,15 @@ static int sbayes_run(const hb_sbayes_args *args, hb_ldm *H, hb_sbayes_out *o, b
             HB_HIP(hipGraphInstantiate(&R.gexec, R.graph, nullptr, nullptr, 0));
         }
         HB_HIP(hipGraphLaunch(R.gexec, d.stream));
-        if (in.count_pip && nw) TRYA(sparse ? hbk_ss_windows(&R.s) : hbk_sb_windows(&d));
+        if (in.count_pip && nw) HB_TRY(sparse ? hbk_ss_windows(&R.s) : hbk_sb_windows(&d));
         HB_HIP(hipMemcpyAsync(R.h_acc, d.acc, sizeof(double) * HB_ACC_N, hipMemcpyDeviceToHost, d.stream));
         HB_HIP(hipStreamSynchronize(d.stream));
         const double *acc = R.h_acc;
         events_sum += acc[HB_ACC_EVENTS];
-        auto draw_pi = [&]() { // rdirichlet_sample, src/stats.cpp:69-76
-            std::vector<double> xn(n_fold);
-            for (int j = 0; j < n_fold; j++) xn[j] = hs.gamma(fold_snp_num[j] + 1, 1.0);
-            const double sx = arma_sum(xn.data(), xn.size());
-            for (int j = 0; j < n_fold; j++) Pi[j] = xn[j] / sx;
-        };
-        switch (model_index) {
-        case 1: varg = (acc[HB_ACC_SUMG2] + s2varg_ * dfvara_) / hs.chisq(dfvara_ + count_y); break; // :269
-        case 2: break;
-        case 3: // :321-324
-            fold_snp_num[1] = acc[HB_ACC_COUNT0 + 1];
-            fold_snp_num[0] = (double)m - nvar0 - fold_snp_num[1];
-            NnzSnp = (long long)fold_snp_num[1];
-            if (!fixpi) draw_pi();
-            break;
-        case 4: // :360-365
-            fold_snp_num[1] = acc[HB_ACC_COUNT0 + 1];
-            fold_snp_num[0] = (double)m - nvar0 - fold_snp_num[1];
-            NnzSnp = (long long)fold_snp_num[1];
-            varg = (acc[HB_ACC_SUMG2] + s2varg_ * dfvara_) / hs.chisq(dfvara_ + (double)NnzSnp);
-            if (!fixpi) draw_pi();
-            break;
-        case 5: { // :386-389
-            const double shape = shape0 + count_y, rate = rate0 + acc[HB_ACC_SUMVARGL] / 2;
-            lambda2 = hs.gamma(shape, 1 / rate);
-            lambda = std::sqrt(lambda2);
-            break;
-        }
-        case 6: { // :448-460 (class 0 of the device counts already excludes the markers without statistics)
-            double nz = 0;
-            for (int j = 0; j < n_fold; j++) fold_snp_num[j] = acc[HB_ACC_COUNT0 + j];
-            for (int j = 1; j < n_fold; j++) nz += fold_snp_num[j];
-            NnzSnp = (long long)nz;
-            varg = (acc[HB_ACC_SUMG2] + s2varg_ * dfvara_) / hs.chisq(dfvara_ + (double)NnzSnp);
-            for (int j = 0; j < n_fold; j++) vara_fold[j] = varg * fold_[j];
-            if (!fixpi) draw_pi();
-            break;
-        }
-        }
+        // :269-460; the sampled markers are the count_y with statistics (= m - nvar0: every marker is in one of the two counts)
+        hb_draw_hyper(hs, hb_hyper_prior{model_index, n_fold, fixpi, dfvara_, s2varg_, shape0, rate0, fold_.data()},
+                      hb_hyper_sums{acc[HB_ACC_SUMG2], acc[HB_ACC_SUMVARGL], acc + HB_ACC_COUNT0, (double)count_y, 0.0},
+                      hb_hyper_state{varg, lambda, lambda2, NnzSnp, Pi.data(), vara_fold.data(), fold_snp_num.data()});
         vara_ = (acc[HB_ACC_SUMR] + s2vara_ * dfvara_) / hs.chisq(n + dfvara_);        // :468
         vare_ = (yy - acc[HB_ACC_SUMR2] + s2vare_ * dfvare_) / hs.chisq(n + dfvare_);  // :473
         if (vare_ < 0) vare_ = vara_ * 0.5;                                            // :474
@@ -375,7 +276,7 @@ static int sbayes_run(const hb_sbayes_args *args, hb_ldm *H, hb_sbayes_out *o, b
             count++;
         }
         if (a.verbose && a.outfreq > 0 && (iter + 1) % a.outfreq == 0) { // :514-537
-            const double el = std::chrono::duration<double>(clk::now() - t_loop).count();
+            const double el = hb_since(t_loop);
             const int tt = (int)std::floor(el / (iter + 1) * (niter - iter));
             char pis[256] = {0};
             size_t off = 0;
@@ -392,7 +293,7 @@ static int sbayes_run(const hb_sbayes_args *args, hb_ldm *H, hb_sbayes_out *o, b
             break;
         }
     }
-    const double loop_seconds = std::chrono::duration<double>(clk::now() - t_loop).count();
+    const double loop_seconds = hb_since(t_loop);
     // ---- posterior assembly, :541-580 ----
     const double Rn = (double)n_records;
     o->Vg = vara_sum / Rn;
@@ -416,21 +317,13 @@ static int sbayes_run(const hb_sbayes_args *args, hb_ldm *H, hb_sbayes_out *o, b
         else {
             std::vector<uint32_t> nz(m);
             HB_HIP(hipMemcpy(nz.data(), d.nzrate, sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
-            for (int i = 0; i < m; i++) {
-                double p = (double)nz[i] / nzct;
-                if (p == 1) p = (nzct - 1) / (double)nzct; // :574
-                o->pip[i] = p;
-            }
+            for (int i = 0; i < m; i++) o->pip[i] = hb_pip((double)nz[i], nzct); // :574
         }
     }
     if (nw && o->gwas) {
         std::vector<double> w(nw);
         HB_HIP(hipMemcpy(w.data(), d.wppa, sizeof(double) * nw, hipMemcpyDeviceToHost));
-        for (int k = 0; k < nw; k++) {
-            double p = w[k] / nzct;
-            if (p == 1) p = (nzct - 1) / (double)nzct;
-            o->gwas[k] = p;
-        }
+        for (int k = 0; k < nw; k++) o->gwas[k] = hb_pip(w[k], nzct);
     }
     if (o->r_hat) HB_HIP(hipMemcpy(o->r_hat, d.r_hat, sizeof(double) * m, hipMemcpyDeviceToHost));
     if (o->g_last) HB_HIP(hipMemcpy(o->g_last, d.g, sizeof(double) * m, hipMemcpyDeviceToHost));
@@ -445,7 +338,6 @@ static int sbayes_run(const hb_sbayes_args *args, hb_ldm *H, hb_sbayes_out *o, b
     line("    Estimated h2 %f", o->h2);
     line("Finished: set-up %.2fs, MCMC %.2fs, %.1f sweeps/s", setup_seconds, loop_seconds, loop_seconds > 0 ? iter / loop_seconds : 0.0);
     return HB_OK;
-#undef TRYA
 }
 
 extern "C" int hb_sbayes_run(const hb_sbayes_args *args, hb_sbayes_out *o) { return sbayes_run(args, nullptr, o); }

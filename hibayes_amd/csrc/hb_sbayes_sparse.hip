@@ -1,8 +1,8 @@
 // hb_sbayes_sparse.hip — device side of the summary-level sampler on a SPARSE LD matrix: SBayesS() of the reference
 // (src/SBayesS.cpp:277-600) from the handle's device CSC (hb_ldm_device_csc: int64 column pointers, int32 rows sorted inside a
-// column, fp64 values). The host loop is hb_sbayes.hip (hb_sbayes_run_sparse). A unit of its own: it brings its own copies of what
-// it shares with hb_kernels.hip (k_pre's thresholds, k_bayesl_post, the wave helpers), so that the chain kernels' unit gains no
-// instantiation.
+// column, fp64 values). The host loop is hb_sbayes.hip (hb_sbayes_run_sparse). A unit of its own: it brings its own copies of the kernels
+// it shares with hb_kernels.hip (k_pre's thresholds, k_bayesl_post), so that the chain kernels' unit gains no instantiation; the
+// wave helpers are hb_wave.hpp's.
 //
 // SBayesS() is not SBayesD() with zeros: marker i is sampled under its own residual variance varei = varediff[i] vara + vare
 // (:285), BayesC / BayesCpi / BayesR effects with g^2 vx > vary are redrawn, at most 101 times (:388-398, :489-499), and a move
@@ -24,17 +24,11 @@
 #include "hb_sbayes_sparse.hpp"
 #include "hb_plan.hpp"
 #include "hb_rng.hpp"
+#include "hb_wave.hpp"
 
 #define HB_INF __builtin_huge_val()
 
 namespace {
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // block-wide sum, result valid in every thread; red must hold blockDim.x / 64 entries
 __device__ __forceinline__ double block_sum(double v, double *red)
@@ -47,13 +41,6 @@ __device__ __forceinline__ double block_sum(double v, double *red)
     double s = 0;
     for (int i = 0; i < nw; i++) s += red[i];
     return s;
-}
-
-__device__ __forceinline__ double readlane_f64(double v, int k)
-{
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), k);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), k);
-    return __hiloint2double(hi, lo);
 }
 
 // The inclusion test on q = rhs^2. k_pre's threshold form "q >= thr" comes from multiplying s1 - s0 >= log((1 - U) / U) by
