@@ -15,7 +15,17 @@ Draws come from the oracle's Philox functions: marker i's blocks 64 i + 0 / 1 / 
 oracle/hb_sbayes_oracle.c:61-84, the host stream as Stream(RNG_PHILOX, seed, (2 << 56) | iter), and — purpose 4, new with this
 sampler — the normal of redraw k = 1, 2, ... of marker i in sweep iter from block 128 i + k under sub = (4 << 56) | iter.
 
-Returns what O.sbayes returns, plus "redraws" (marker-sweeps that redrew at least once) and "zeroed" (those that ended at 0)."""
+Returns what O.sbayes returns, plus "redraws" (marker-sweeps that redrew at least once) and "zeroed" (those that ended at 0).
+
+`trace`: a list that receives one record per sweep, four m-long arrays taken from this sequential chain (nothing here simulates
+the device's rounds; `group` is the number of consecutive markers one chain launch of the device holds, SB_GS = SS_GS = 512):
+  g_before  the effects when the sweep began;
+  entry_in  the decision the marker would get, with its own draws, from r_hat as it stood when the sweep reached the first
+            marker of the marker's block of `group` (true for every marker with statistics under BayesRR / BayesA / BayesL);
+  turn_in   the decision at the marker's own turn;
+  moved     the marker's effect changed.
+Each model's decision is a function of (marker, right-hand side) for that; with trace=None nothing else differs, and the records
+are the same in every bit with the trace on or off (test_sbayes_rounds_host.py)."""
 import math
 
 import numpy as np
@@ -59,7 +69,7 @@ def varediff_of(csc):
 
 
 def sbayess_restatement(sumstat, csc, model, Pi, fold=None, niter=50000, nburn=20000, thin=5, vg=None, dfvg=None, s2vg=None,
-                        ve=None, dfve=None, s2ve=None, windindx=None, seed=666666):
+                        ve=None, dfve=None, s2ve=None, windindx=None, seed=666666, trace=None, group=512):
     L = O.lib()
     ss = np.asarray(sumstat, dtype=np.float64)
     m = csc.shape[0]
@@ -139,6 +149,24 @@ def sbayess_restatement(sumstat, csc, model, Pi, fold=None, niter=50000, nburn=2
         norm = lambda i: L.hbo_philox_normal(seed, sub, i * BLK_PER_MARKER + 1)
         chisq = lambda i, df: O.Stream(O.RNG_PHILOX, seed, sub, i * BLK_PER_MARKER + 4).chisq(df)
 
+        rec, nxt = None, 0
+        if trace is not None:
+            rec = {"g_before": g.copy(), "entry_in": np.zeros(m, dtype=bool), "turn_in": np.zeros(m, dtype=bool),
+                   "moved": np.zeros(m, dtype=bool)}
+            trace.append(rec)
+
+        def enter(i, included):
+            """before marker i's turn: every block of `group` the sweep has reached gets its markers' decisions from r_hat as it is"""
+            nonlocal nxt
+            while i >= nxt:
+                for j in est[(est >= nxt) & (est < nxt + group)]:
+                    j = int(j)
+                    rhs = r_hat[j]
+                    if g[j]:
+                        rhs += xpx[j] * g[j]
+                    rec["entry_in"][j] = included(j, rhs)
+                nxt += group
+
         def truncated(i, gi, rhs, v, varei):
             """:388-398 / :489-499; returns (gi, redrew, last draw squared)"""
             nonlocal redraws, zeroed
@@ -158,6 +186,9 @@ def sbayess_restatement(sumstat, csc, model, Pi, fold=None, niter=50000, nburn=2
         if mi in (1, 2, 5):
             for i in est:
                 i = int(i)
+                if rec is not None:
+                    enter(i, lambda j, rhs: True)
+                    rec["turn_in"][i] = True
                 xx, gi = xpx[i], g[i]
                 varei = varediff[i] * vara_ + vare_
                 if mi == 2:
@@ -177,6 +208,8 @@ def sbayess_restatement(sumstat, csc, model, Pi, fold=None, niter=50000, nburn=2
                         move(i, gi)
                 else:
                     move(i, gi)
+                if rec is not None:
+                    rec["moved"][i] = g[i] != rec["g_before"][i]
             if mi == 1:
                 varg = (seq_sum(g * g) + s2varg_ * dfvara_) / glob.chisq(dfvara_ + count_y)
             if mi == 5:
@@ -186,21 +219,32 @@ def sbayess_restatement(sumstat, csc, model, Pi, fold=None, niter=50000, nburn=2
             logpi = [_log(p) for p in Pi]
             s0 = logpi[0]
             vargi = 0.0
-            for i in est:
-                i = int(i)
+
+            def decide(i, rhs):
+                """marker i's class from its right-hand side, with its own draws (g[i] is the effect it entered the sweep with
+                until its turn is over); also the variance of its effect"""
                 xx, gi = xpx[i], g[i]
                 varei = varediff[i] * vara_ + vare_
-                if mi == 3:
-                    varg = (gi * gi + s2varg_ * dfvara_) / chisq(i, dfvara_ + 1)
+                vgi = (gi * gi + s2varg_ * dfvara_) / chisq(i, dfvara_ + 1) if mi == 3 else varg
+                lhs = xx / varei
+                logdetV = _log(vgi * lhs + 1)
+                uhat = rhs / (xx + varei / vgi)
+                s1 = -0.5 * (logdetV - (rhs * uhat / varei)) + logpi[1]
+                acceptProb = 1 / (_exp(s0 - s0) + _exp(s1 - s0))
+                return (0 if unif(i) < acceptProb else 1), vgi
+
+            for i in est:
+                i = int(i)
+                if rec is not None:
+                    enter(i, lambda j, rhs: decide(j, rhs)[0] != 0)
+                xx, gi = xpx[i], g[i]
+                varei = varediff[i] * vara_ + vare_
                 rhs = r_hat[i]
                 if gi:
                     rhs += xx * gi
-                lhs = xx / varei
-                logdetV = _log(varg * lhs + 1)
-                uhat = rhs / (xx + varei / varg)
-                s1 = -0.5 * (logdetV - (rhs * uhat / varei)) + logpi[1]
-                acceptProb = 1 / (_exp(s0 - s0) + _exp(s1 - s0))
-                flag = 0 if unif(i) < acceptProb else 1
+                flag, vgi = decide(i, rhs)
+                if mi == 3:
+                    varg = vgi
                 snptracker[i] = flag
                 if flag == 0:
                     gi = 0.0
@@ -214,6 +258,9 @@ def sbayess_restatement(sumstat, csc, model, Pi, fold=None, niter=50000, nburn=2
                         vargi += gi * gi
                 if gi != g[i]:
                     move(i, gi)
+                if rec is not None:
+                    rec["turn_in"][i] = flag != 0
+                    rec["moved"][i] = g[i] != rec["g_before"][i]
             fold_snp_num[1] = float(snptracker.sum())
             fold_snp_num[0] = m - nvar0 - fold_snp_num[1]
             NnzSnp = int(fold_snp_num[1])
@@ -225,16 +272,14 @@ def sbayess_restatement(sumstat, csc, model, Pi, fold=None, niter=50000, nburn=2
                 Pi = [x / sx for x in xn]
         else:
             logpi = [_log(p) for p in Pi]
-            s = [logpi[0]] + [0.0] * (n_fold - 1)
             varg = 0.0
-            for i in est:
-                i = int(i)
-                xx, gi = xpx[i], g[i]
+
+            def decide(i, rhs):
+                """marker i's class from its right-hand side, with its own draw"""
+                xx = xpx[i]
                 varei = varediff[i] * vara_ + vare_
-                rhs = r_hat[i]
-                if gi:
-                    rhs += xx * gi
                 lhs = xx / varei
+                s = [logpi[0]] + [0.0] * (n_fold - 1)
                 for j in range(1, n_fold):
                     logdetV = _log(vara_fold[j] * lhs + 1)
                     uhat = rhs / (xx + varei / vara_fold[j])
@@ -251,6 +296,18 @@ def sbayess_restatement(sumstat, csc, model, Pi, fold=None, niter=50000, nburn=2
                     if rval < acceptProb:
                         flag = j
                         break
+                return flag
+
+            for i in est:
+                i = int(i)
+                if rec is not None:
+                    enter(i, lambda j, rhs: decide(j, rhs) != 0)
+                xx, gi = xpx[i], g[i]
+                varei = varediff[i] * vara_ + vare_
+                rhs = r_hat[i]
+                if gi:
+                    rhs += xx * gi
+                flag = decide(i, rhs)
                 snptracker[i] = flag
                 if flag == 0:
                     gi = 0.0
@@ -261,6 +318,9 @@ def sbayess_restatement(sumstat, csc, model, Pi, fold=None, niter=50000, nburn=2
                     varg += gi * gi / fold_[flag]
                 if gi != g[i]:
                     move(i, gi)
+                if rec is not None:
+                    rec["turn_in"][i] = flag != 0
+                    rec["moved"][i] = g[i] != rec["g_before"][i]
             fold_snp_num = [float((snptracker == j).sum()) for j in range(n_fold)]
             NnzSnp = int(m - fold_snp_num[0])
             varg = (varg + s2varg_ * dfvara_) / glob.chisq(dfvara_ + NnzSnp)
