@@ -244,6 +244,8 @@ SYMBOLS = [
     # BSLMM: make_grm() src/rm.cpp:5-53, the polygenic block src/Bayes.cpp:518-552
     "hb_grm_build", "hb_grm_free", "hb_ctx_poly_setup", "hb_ctx_poly_step", "hb_ctx_poly_state", "hb_ctx_poly_debug_get",
     "hb_bayes_run_poly", "hb_run_poly",
+    # eigh(): dsytrd and dormtr of the dsyevd behind eigen_sym_dc, src/rm.cpp:46-52 (R/bayes.r:292-294)
+    "hb_eig_upload", "hb_eig_reduce", "hb_eig_tau", "hb_eig_vectors", "hb_eig_download", "hb_eig_release", "hb_eig_destroy",
 ]
 
 
@@ -369,6 +371,15 @@ def lib():
     L.hb_ctx_poly_state.argtypes = [vp, vp, C.POINTER(dbl), C.POINTER(dbl), C.POINTER(i32)]
     L.hb_ctx_poly_debug_get.argtypes = [vp, vp, vp, vp, vp]
     L.hb_run_destroy.restype = None
+    L.hb_eig_upload.argtypes = [vp, i64, i32, i32, C.POINTER(vp), C.POINTER(i64)]
+    L.hb_eig_reduce.argtypes = [vp, i64, i32, i32, vp, vp, C.POINTER(vp)]
+    L.hb_eig_tau.argtypes = [vp, vp]
+    L.hb_eig_vectors.argtypes = [vp, vp, i64, C.POINTER(vp), C.POINTER(i64)]
+    L.hb_eig_download.argtypes = [vp, i64, i32, i32, vp, i64]
+    L.hb_eig_release.argtypes = [vp]
+    L.hb_eig_release.restype = None
+    L.hb_eig_destroy.argtypes = [vp]
+    L.hb_eig_destroy.restype = None
     _lib = L
     return L
 

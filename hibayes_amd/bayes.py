@@ -359,7 +359,7 @@ def ibrm(formula, data=None, M=None, M_id=None, method="BayesCpi", map=None, Pi=
          niter=None, nburn=None, thin=5, windsize=None, windnum=None, dfvr=None, s2vr=None, vg=None,
          dfvg=None, s2vg=None, ve=None, dfve=None, s2ve=None, printfreq=100, seed=666666,
          threads=4, verbose=True, *, windindx=None, device=0, panel=0, precise=2,
-         store_alpha=True, comm=None, m_global=None, m_offset=0, gebv_samples=None, lambda_=0.0):
+         store_alpha=True, comm=None, m_global=None, m_offset=0, gebv_samples=None, lambda_=0.0, eigen_solver="host"):
     """Mirror of ibrm() (reference R/bayes.r:121-320). `formula` is a string such as
     "T1 ~ 1" or "T1 ~ season + bwt + (1 | loc) + (1 | dam)"; `data` a dict of columns or a
     pandas DataFrame whose first column holds the individual ids; `M` the n_all x m genotype
@@ -370,7 +370,12 @@ def ibrm(formula, data=None, M=None, M_id=None, method="BayesCpi", map=None, Pi=
     `gebv_samples` (default: store_alpha): also return MCMCsamples["g"] = M %*% MCMCsamples$alpha (n_all x n_records,
     R/bayes.r:303-305), computed on the device.
     `lambda_` (the reference's `lambda`, R/bayes.r:144): method "BSLMM" only — added to the diagonal of the relationship matrix of the
-    individuals in the fit before its eigen-decomposition (make_grm(M[rows], lambda, eigen = TRUE), :292-294)."""
+    individuals in the fit before its eigen-decomposition (make_grm(M[rows], lambda, eigen = TRUE), :292-294).
+    `eigen_solver`: method "BSLMM" only — "host" (default) decomposes the relationship matrix with LAPACK on the host; "device" with
+    hibayes_amd.eig: the genotypes of the fit are uploaded once, the matrix and its eigenvectors stay on the device and the sampler runs on
+    that context (the draws z_j are addressed by eigenvector index, so the chain is another equally valid realisation, not the host route's)."""
+    if eigen_solver not in ("host", "device"):
+        raise ValueError("ibrm: eigen_solver must be \"host\" or \"device\", not %r" % (eigen_solver,))
     if data is None:
         raise ValueError("no data assigned.")
     if M is None:
@@ -457,15 +462,26 @@ def ibrm(formula, data=None, M=None, M_id=None, method="BayesCpi", map=None, Pi=
             windindx = cutwind_by_bp(chrom, bp, windsize)
     y = np.array([float(cols[lhs][i]) for i in rows])
     Mfit = M[rows, :]
-    Kival = Ki = None
-    if method == "BSLMM":  # R/bayes.r:292-294
-        from .grm import make_grm
-        Kival, Ki = make_grm(Mfit, lambda_, eigen=True, verbose=verbose, device=device)
-    res = Bayes(y=y, X=Mfit, model=method, Pi=Pi, Kival=Kival, Ki=Ki, fold=fold, C_=Xfix, R=R, niter=niter, nburn=nburn,
-                thin=thin, windindx=windindx, dfvr=dfvr, s2vr=s2vr, vg=vg, dfvg=dfvg, s2vg=s2vg, ve=ve,
-                dfve=dfve, s2ve=s2ve, outfreq=printfreq, threads=threads, verbose=verbose, seed=seed,
-                device=device, panel=panel, precise=precise, store_alpha=store_alpha, comm=comm,
-                m_global=m_global, m_offset=m_offset)
+    Kival = Ki = fit_ctx = None
+    from .engine import Context
+    try:
+        if method == "BSLMM":  # R/bayes.r:292-294
+            from .grm import make_grm
+            if eigen_solver == "device":
+                fit_ctx = Context(Mfit.shape[0], Mfit.shape[1], device=device, panel=panel, precise=precise, m_offset=m_offset, seed=seed)
+                fit_ctx.upload(Mfit)
+                Kh = make_grm(fit_ctx, lambda_, eigen=True, verbose=verbose, eigen_solver="device", keep_on_device=True)
+                fit_ctx.poly_setup(Kh.values, Kh)
+            else:
+                Kival, Ki = make_grm(Mfit, lambda_, eigen=True, verbose=verbose, device=device)
+        res = Bayes(y=y, X=None if fit_ctx is not None else Mfit, model=method, Pi=Pi, Kival=Kival, Ki=Ki, fold=fold, C_=Xfix, R=R, niter=niter, nburn=nburn,
+                    thin=thin, windindx=windindx, dfvr=dfvr, s2vr=s2vr, vg=vg, dfvg=dfvg, s2vg=s2vg, ve=ve,
+                    dfve=dfve, s2ve=s2ve, outfreq=printfreq, threads=threads, verbose=verbose, seed=seed,
+                    device=device, panel=panel, precise=precise, store_alpha=store_alpha, comm=comm,
+                    m_global=m_global, m_offset=m_offset, ctx=fit_ctx)
+    finally:
+        if fit_ctx is not None:
+            fit_ctx.close()
     if "beta" in res:
         res["beta_names"] = fixed_names
     if "Vr" in res:
@@ -474,7 +490,6 @@ def ibrm(formula, data=None, M=None, M_id=None, method="BayesCpi", map=None, Pi=
     # On the device (hb_ctx_matmul: int8 genotypes x fp64 effects, eight records per pass over the non-zero columns).
     if gebv_samples is None:
         gebv_samples = bool(store_alpha)
-    from .engine import Context
     with Context(nall, M.shape[1], device=device, panel=panel) as cg:
         cg.upload(M)
         if gebv_samples and "alpha" in res["MCMCsamples"]:

@@ -262,9 +262,17 @@ class Context:
     # ---- BSLMM's polygenic block (reference src/Bayes.cpp:518-552) ----
     def poly_setup(self, Kival, Ki, on_device=False):
         """Eigenvalues (n) and eigenvectors (n x n) of the relationship matrix. Ki: a host array, or with on_device=True a CUDA/HIP torch
-        tensor (float64, row j = column j of K, an even row stride) that the context borrows and this object keeps alive."""
+        tensor (float64, row j = column j of K, an even row stride) that the context borrows and this object keeps alive; or an
+        eig.EigVectors handle (make_grm(eigen_solver="device", keep_on_device=True)), borrowed and kept alive likewise."""
         kv = np.ascontiguousarray(Kival, dtype=np.float64)
-        if on_device:
+        from .eig import EigVectors
+        if isinstance(Ki, EigVectors):
+            Ki._live("poly_setup")
+            if Ki.n != self.n or kv.size != self.n:
+                raise ValueError("poly_setup: the eigenvectors are %d x %d, the context holds %d individuals" % (Ki.n, Ki.n, self.n))
+            self._poly_keep = Ki
+            check(self.L.hb_ctx_poly_setup(self.h, kv.ctypes.data, Ki.ptr, Ki.ld, 1))
+        elif on_device:
             if Ki is None or Ki.dim() != 2 or Ki.shape[0] != self.n or Ki.shape[1] < self.n or Ki.stride(1) != 1:
                 raise ValueError("poly_setup: a device K is a tensor of n rows, row j holding column j of K (n values, then padding)")
             self._poly_keep = Ki

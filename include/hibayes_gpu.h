@@ -454,11 +454,43 @@ int hb_cg_run_sparse(const hb_cg_args *args, hb_ldm *ldm, hb_cg_out *out);
  * two builds agree bit for bit. G_host: n x n column-major or NULL; G_dev: NULL, or receives a device copy (leading dimension n) that
  * the caller releases with hb_grm_free. flags: HB_GRM_RAW = the centred cross-product Z Z' itself, no scaling and no lambda.
  * All markers monomorphic (mean diagonal 0; the reference returns NaN): HB_ERR_INVALID. The n x n matrix not fitting on the device:
- * HB_ERR_HIP with "out of memory" in the text. The inverse and the eigen-decomposition are not part of the library.
+ * HB_ERR_HIP with "out of memory" in the text. The inverse is not part of the library; the eigen-decomposition is hb_eig_* below.
  * ------------------------------------------------------------------------------------ */
 #define HB_GRM_RAW 1
 int hb_grm_build(hb_ctx *c, double lambda, int32_t flags, double *G_host, double **G_dev);
 void hb_grm_free(double *G_dev);
+
+/* ------------------------------------------------------------------------------------
+ * The symmetric eigen-decomposition behind make_grm(eigen = TRUE) (reference src/rm.cpp:46-52: eigen_sym_dc, LAPACK dsyevd; R/bayes.r:292-294
+ * hands its output to Bayes() as Kival / Ki) with its two O(n^3) stages on the device. The caller supplies the
+ * O(n^2) stage between them — the eigenvalues and eigenvectors Z of the tridiagonal matrix (d, e), LAPACK dstemr or dstedc on the host:
+ *     hb_eig_reduce  ->  (w, Z) = dstemr(d, e)  ->  hb_eig_vectors(Z)  ->  K = Q Z on the device, for hb_ctx_poly_setup(on_device = 1).
+ * No floating-point atomics: two runs on the same matrix agree bit for bit. Without a device every entry below that computes or copies
+ * fails with HB_ERR_NO_DEVICE.
+ * ------------------------------------------------------------------------------------ */
+typedef struct hb_eig hb_eig;
+/* A host matrix (n x n column-major, leading dimension lda_host) on the device, with an even leading dimension *lda; hb_eig_release frees it.
+ * hb_grm_build's G_dev needs no upload (src/rm.cpp:46: the matrix eigen_sym_dc receives). */
+int hb_eig_upload(const double *A_host, int64_t lda_host, int32_t n, int32_t device, double **A_dev, int64_t *lda);
+/* LAPACK dsytrd, uplo = 'L' (first stage of the dsyevd of src/rm.cpp:46-52): Q' A Q = T. Only the lower triangle of A_dev is read. A_dev is
+ * overwritten as dsytrd leaves it (reflector k below the subdiagonal of column k, v[0] = 1 implied, beta = -sign(alpha) ||x||, tau = 0 for a
+ * column that is exactly zero there; d on the diagonal, e on the subdiagonal) and is BORROWED until hb_eig_destroy. d_host (n) and e_host
+ * (n - 1) receive the tridiagonal matrix. lda < n or n < 1: HB_ERR_INVALID; a non-finite d or e: HB_ERR_INVALID, "the matrix holds a
+ * non-finite value". A 16-byte aligned A_dev with an even lda takes the fast mat-vec. */
+int hb_eig_reduce(double *A_dev, int64_t lda, int32_t n, int32_t device, double *d_host, double *e_host, hb_eig **out);
+/* dsytrd's TAU (n - 1 values) — with the reduced A_dev (hb_eig_download) the whole of Q; for the tests (src/rm.cpp:46-52). */
+int hb_eig_tau(hb_eig *h, double *tau_host);
+/* LAPACK dormtr (side L, uplo L, no transpose; last stage of the dsyevd of src/rm.cpp:46-52): *K_dev = Q Z, the matrix R/bayes.r:292-294
+ * passes on as Ki. Z_host: n x n column-major with leading dimension ldz, or NULL for Z = I (K = Q, dorgtr). K is allocated here with an
+ * even leading dimension *ldk (every column 16-byte aligned, as hb_ctx_poly_setup(on_device = 1) requires), is the caller's and outlives
+ * the handle; hb_eig_release frees it. */
+int hb_eig_vectors(hb_eig *h, const double *Z_host, int64_t ldz, double **K_dev, int64_t *ldk);
+/* An n x n device matrix of this interface — K (the Ki of R/bayes.r:292-294), or the reduced A (src/rm.cpp:46-52) — to a host column-major array. */
+int hb_eig_download(const double *M_dev, int64_t ld_dev, int32_t n, int32_t device, double *M_host, int64_t ld_host);
+/* Frees what hb_eig_upload or hb_eig_vectors allocated (the Ki of R/bayes.r:292-294 once the fit is done). */
+void hb_eig_release(double *M_dev);
+/* Ends the borrowing of A_dev and frees the handle's panels (src/rm.cpp:46-52 keeps nothing either). NULL is allowed. */
+void hb_eig_destroy(hb_eig *h);
 
 /* ====================================================================================
  * Fine-grained engine API.  hb_bayes_run() is built on it; the parity tests and bench.py
