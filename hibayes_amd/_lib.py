@@ -246,6 +246,8 @@ SYMBOLS = [
     "hb_bayes_run_poly", "hb_run_poly",
     # eigh(): dsytrd and dormtr of the dsyevd behind eigen_sym_dc, src/rm.cpp:46-52 (R/bayes.r:292-294)
     "hb_eig_upload", "hb_eig_reduce", "hb_eig_tau", "hb_eig_vectors", "hb_eig_download", "hb_eig_release", "hb_eig_destroy",
+    # its middle stage on the device: dstedc (hb_stedc.hip), and the back-transformation of a Z that lies there
+    "hb_eig_tridiagonal", "hb_eig_vectors_dev", "hb_stedc_plan", "hb_stedc_stats",
 ]
 
 
@@ -376,6 +378,10 @@ def lib():
     L.hb_eig_tau.argtypes = [vp, vp]
     L.hb_eig_vectors.argtypes = [vp, vp, i64, C.POINTER(vp), C.POINTER(i64)]
     L.hb_eig_download.argtypes = [vp, i64, i32, i32, vp, i64]
+    L.hb_eig_tridiagonal.argtypes = [vp, vp, i32, i32, vp, C.POINTER(vp), C.POINTER(i64)]
+    L.hb_eig_vectors_dev.argtypes = [vp, vp, i64, C.POINTER(vp), C.POINTER(i64)]
+    L.hb_stedc_plan.argtypes = [i32, vp, i32, i32] + [vp] * 10
+    L.hb_stedc_stats.argtypes = [vp, i32]
     L.hb_eig_release.argtypes = [vp]
     L.hb_eig_release.restype = None
     L.hb_eig_destroy.argtypes = [vp]

@@ -359,7 +359,7 @@ def ibrm(formula, data=None, M=None, M_id=None, method="BayesCpi", map=None, Pi=
          niter=None, nburn=None, thin=5, windsize=None, windnum=None, dfvr=None, s2vr=None, vg=None,
          dfvg=None, s2vg=None, ve=None, dfve=None, s2ve=None, printfreq=100, seed=666666,
          threads=4, verbose=True, *, windindx=None, device=0, panel=0, precise=2,
-         store_alpha=True, comm=None, m_global=None, m_offset=0, gebv_samples=None, lambda_=0.0, eigen_solver="host"):
+         store_alpha=True, comm=None, m_global=None, m_offset=0, gebv_samples=None, lambda_=0.0, eigen_solver="host", tridiagonal="host"):
     """Mirror of ibrm() (reference R/bayes.r:121-320). `formula` is a string such as
     "T1 ~ 1" or "T1 ~ season + bwt + (1 | loc) + (1 | dam)"; `data` a dict of columns or a
     pandas DataFrame whose first column holds the individual ids; `M` the n_all x m genotype
@@ -373,9 +373,13 @@ def ibrm(formula, data=None, M=None, M_id=None, method="BayesCpi", map=None, Pi=
     individuals in the fit before its eigen-decomposition (make_grm(M[rows], lambda, eigen = TRUE), :292-294).
     `eigen_solver`: method "BSLMM" only — "host" (default) decomposes the relationship matrix with LAPACK on the host; "device" with
     hibayes_amd.eig: the genotypes of the fit are uploaded once, the matrix and its eigenvectors stay on the device and the sampler runs on
-    that context (the draws z_j are addressed by eigenvector index, so the chain is another equally valid realisation, not the host route's)."""
+    that context (the draws z_j are addressed by eigenvector index, so the chain is another equally valid realisation, not the host route's).
+    `tridiagonal`: with eigen_solver="device" only — "host" (default) or "device", the stage between the reduction and the back-transformation
+    (make_grm's keyword of the same name)."""
     if eigen_solver not in ("host", "device"):
         raise ValueError("ibrm: eigen_solver must be \"host\" or \"device\", not %r" % (eigen_solver,))
+    from .eig import check_tridiagonal
+    check_tridiagonal("ibrm", tridiagonal, eigen_solver)
     if data is None:
         raise ValueError("no data assigned.")
     if M is None:
@@ -470,7 +474,7 @@ def ibrm(formula, data=None, M=None, M_id=None, method="BayesCpi", map=None, Pi=
             if eigen_solver == "device":
                 fit_ctx = Context(Mfit.shape[0], Mfit.shape[1], device=device, panel=panel, precise=precise, m_offset=m_offset, seed=seed)
                 fit_ctx.upload(Mfit)
-                Kh = make_grm(fit_ctx, lambda_, eigen=True, verbose=verbose, eigen_solver="device", keep_on_device=True)
+                Kh = make_grm(fit_ctx, lambda_, eigen=True, verbose=verbose, eigen_solver="device", keep_on_device=True, tridiagonal=tridiagonal)
                 fit_ctx.poly_setup(Kh.values, Kh)
             else:
                 Kival, Ki = make_grm(Mfit, lambda_, eigen=True, verbose=verbose, device=device)

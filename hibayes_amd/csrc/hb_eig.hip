@@ -13,7 +13,7 @@
 //     k_eig_fold     p = the chunks in order - V (W'v) - W (V'v); W[:, c] = tau p; the workgroups' sums of (tau p)' v
 //     k_eig_wfin     W[:, c] -= (tau / 2) (w'v) v
 // and after the panel k_eig_trail: A22 -= V W' + W V' on the matrix cores (v_mfma_f64_16x16x4_f64), 64 x 64 tiles of the lower triangle.
-// Stage 2, the tridiagonal problem, is the caller's (LAPACK dstemr on the host).
+// Stage 2, the tridiagonal problem, is the caller's: LAPACK dstemr on the host, or hb_eig_tridiagonal (hb_stedc.hip) on the device.
 // Stage 3, dormtr: K = Q Z by block reflectors in compact-WY form, K -= V (T (V' K)) per panel from the last to the first:
 //     k_eig_expand   the panel's V with its unit entries and zeros, from A
 //     k_eig_gram     V'V, a workgroup per pair of columns;  k_eig_tfac: dlarft's T from it, one workgroup
@@ -515,6 +515,25 @@ int reduce_all(hb_eig *h)
     return HB_OK;
 }
 
+// K <- Q K by the panels' block reflectors from the last to the first (dormtr); K is ldk x ldk, zero past n
+int back_transform(hb_eig *h, double *K)
+{
+    const int n = h->n;
+    const int nref = n - 1; // reflectors k = 0 .. n - 2
+    for (int k0 = (nref - 1) / NB * NB; nref > 0 && k0 >= 0; k0 -= NB) {
+        const int nbp = std::min(NB, nref - k0);
+        const int rbase = (k0 + 1) / TS * TS;
+        hipLaunchKernelGGL(k_eig_expand, dim3(blocks(h->ldv - rbase), (unsigned)NB), dim3(ET), 0, h->stream, h->A, h->lda, n, k0, nbp, rbase, h->Vp, h->ldv);
+        if (nbp > 1) hipLaunchKernelGGL(k_eig_gram, dim3((unsigned)(nbp * (nbp - 1) / 2)), dim3(ET), 0, h->stream, h->Vp, h->ldv, n, k0, h->S);
+        hipLaunchKernelGGL(k_eig_tfac, dim3(1), dim3(NB), 0, h->stream, h->S, h->tau, k0, nbp, h->T);
+        hipLaunchKernelGGL(k_eig_vtk, dim3((unsigned)(h->ldk / 16)), dim3(256), 0, h->stream, K, h->ldk, n, rbase, h->Vp, h->ldv, h->T, h->Y);
+        hipLaunchKernelGGL(k_eig_kupd, dim3((unsigned)((h->ldk - rbase) / TS), (unsigned)(h->ldk / TS)), dim3(256), 0, h->stream, K, h->ldk, rbase, h->Vp,
+                           h->ldv, h->Y);
+        HB_HIP(hipGetLastError());
+    }
+    return HB_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -641,18 +660,7 @@ int hb_eig_vectors(hb_eig *h, const double *Z_host, int64_t ldz, double **K_dev,
         } else
             hipLaunchKernelGGL(k_eig_identity, dim3(blocks(n)), dim3(ET), 0, h->stream, K, h->ldk, n);
         HB_HIP(hipGetLastError());
-        const int nref = n - 1; // reflectors k = 0 .. n - 2
-        for (int k0 = (nref - 1) / NB * NB; nref > 0 && k0 >= 0; k0 -= NB) {
-            const int nbp = std::min(NB, nref - k0);
-            const int rbase = (k0 + 1) / TS * TS;
-            hipLaunchKernelGGL(k_eig_expand, dim3(blocks(h->ldv - rbase), (unsigned)NB), dim3(ET), 0, h->stream, h->A, h->lda, n, k0, nbp, rbase, h->Vp, h->ldv);
-            if (nbp > 1) hipLaunchKernelGGL(k_eig_gram, dim3((unsigned)(nbp * (nbp - 1) / 2)), dim3(ET), 0, h->stream, h->Vp, h->ldv, n, k0, h->S);
-            hipLaunchKernelGGL(k_eig_tfac, dim3(1), dim3(NB), 0, h->stream, h->S, h->tau, k0, nbp, h->T);
-            hipLaunchKernelGGL(k_eig_vtk, dim3((unsigned)(h->ldk / 16)), dim3(256), 0, h->stream, K, h->ldk, n, rbase, h->Vp, h->ldv, h->T, h->Y);
-            hipLaunchKernelGGL(k_eig_kupd, dim3((unsigned)((h->ldk - rbase) / TS), (unsigned)(h->ldk / TS)), dim3(256), 0, h->stream, K, h->ldk, rbase, h->Vp,
-                               h->ldv, h->Y);
-            HB_HIP(hipGetLastError());
-        }
+        HB_TRY(back_transform(h, K));
         HB_HIP(hipStreamSynchronize(h->stream));
         return HB_OK;
     };
@@ -662,6 +670,23 @@ int hb_eig_vectors(hb_eig *h, const double *Z_host, int64_t ldz, double **K_dev,
         return rc;
     }
     *K_dev = K;
+    *ldk = h->ldk;
+    return HB_OK;
+}
+
+// hb_eig_vectors for a Z that is on the device already (hb_eig_tridiagonal): K = Q Z in place in Z's buffer, whose ownership passes to *K_dev
+// (hb_eig_release frees it; on failure the buffer stays the caller's). ldz must be the handle's ldk: n rounded up to 64, that many columns, padding zero.
+int hb_eig_vectors_dev(hb_eig *h, double *Z_dev, int64_t ldz, double **K_dev, int64_t *ldk)
+{
+    if (K_dev) *K_dev = nullptr;
+    if (!h) return hb_fail(HB_ERR_INVALID, "hb_eig_vectors_dev: null handle");
+    if (!Z_dev || !K_dev || !ldk) return hb_fail(HB_ERR_INVALID, "hb_eig_vectors_dev: null argument");
+    if (ldz != h->ldk) return hb_fail(HB_ERR_INVALID, "hb_eig_vectors_dev: the leading dimension of Z must be n rounded up to 64");
+    HB_TRY(no_device("hb_eig_vectors_dev"));
+    HB_HIP(hipSetDevice(h->device));
+    HB_TRY(back_transform(h, Z_dev));
+    HB_HIP(hipStreamSynchronize(h->stream));
+    *K_dev = Z_dev;
     *ldk = h->ldk;
     return HB_OK;
 }

@@ -5,6 +5,9 @@ its two O(n^3) stages on the device (hb_eig_*, hibayes_amd/csrc/hb_eig.hip, DESI
     dstemr           eigenvalues w and eigenvectors Z of T (scipy.linalg.eigh_tridiagonal)   host, O(n^2) work
     hb_eig_vectors   dormtr: K = Q Z by block reflectors                             device
 
+With tridiagonal="device" the middle stage is the device's too — hb_eig_tridiagonal (hibayes_amd/csrc/hb_stedc.hip): dstedc, Cuppen's divide and
+conquer with Gu-Eisenstat vectors — and hb_eig_vectors_dev back-transforms Z where it lies: no n x n matrix crosses the bus.
+
 The matrix never visits the host when it is built there (make_grm(eigen_solver="device")), and K need not either (keep_on_device=True):
 Context.poly_setup() borrows it where it lies."""
 import ctypes as C
@@ -22,6 +25,48 @@ def tridiagonal_eigh(d, e):
     from scipy.linalg import eigh_tridiagonal
     w, Z = eigh_tridiagonal(d, np.asarray(e, dtype=np.float64), lapack_driver="stemr")
     return w, np.asfortranarray(Z)
+
+
+def check_tridiagonal(who, tridiagonal, eigen_solver="device"):
+    if tridiagonal not in ("host", "device"):
+        raise ValueError("%s: tridiagonal must be \"host\" or \"device\", not %r" % (who, tridiagonal))
+    if tridiagonal == "device" and eigen_solver != "device":
+        raise ValueError("%s: tridiagonal=\"device\" goes with eigen_solver=\"device\"" % who)
+
+
+def tridiagonal_eigh_device(d, e, device=0):
+    """Stage 2 on the device: (w ascending, Z as a DeviceMatrix whose column j belongs to w[j]) of tridiag(e, d, e), by hb_eig_tridiagonal."""
+    d = np.ascontiguousarray(d, dtype=np.float64).ravel()
+    n = d.size
+    e = np.zeros(0) if e is None else np.ascontiguousarray(e, dtype=np.float64).ravel()
+    if n < 1 or e.size != max(n - 1, 0):
+        raise ValueError("tridiagonal_eigh_device: d must hold n >= 1 values and e n - 1")
+    w = np.zeros(n)
+    Z, ldz = C.c_void_p(), C.c_int64()
+    check(lib().hb_eig_tridiagonal(d.ctypes.data, e.ctypes.data if n > 1 else None, n, int(device), w.ctypes.data, C.byref(Z), C.byref(ldz)))
+    return w, DeviceMatrix(Z.value, n, ldz.value, device)
+
+
+def stedc_plan(n, splits=()):
+    """The merge tree hb_eig_tridiagonal uses (hb_stedc_plan; needs no device): dict(leaf_rows, levels, leaves [(lo, hi)], merges [(lo, mid, hi,
+    level)])."""
+    sp = np.ascontiguousarray(splits, dtype=np.int32)
+    cap = max(int(n), 1)
+    a = [np.zeros(cap, dtype=np.int32) for _ in range(6)]
+    cnt = [C.c_int32() for _ in range(4)]
+    check(lib().hb_stedc_plan(int(n), sp.ctypes.data if sp.size else None, int(sp.size), cap, a[0].ctypes.data, a[1].ctypes.data,
+                              C.addressof(cnt[0]), a[2].ctypes.data, a[3].ctypes.data, a[4].ctypes.data, a[5].ctypes.data, C.addressof(cnt[1]),
+                              C.addressof(cnt[2]), C.addressof(cnt[3])))
+    nl, nm = cnt[0].value, cnt[1].value
+    return dict(leaf_rows=cnt[3].value, levels=cnt[2].value, leaves=[(int(a[0][i]), int(a[1][i])) for i in range(nl)],
+                merges=[(int(a[2][i]), int(a[3][i]), int(a[4][i]), int(a[5][i])) for i in range(nm)])
+
+
+def stedc_stats():
+    """The phases of this process's last tridiagonal_eigh_device, in seconds, and its GEMM's floating-point operations (tools/eig_timing.py)"""
+    v = np.zeros(6)
+    check(lib().hb_stedc_stats(v.ctypes.data, 6))
+    return dict(leaves=v[0], scan=v[1], secular=v[2], gemm=v[3], copies=v[4], gemm_flops=v[5])
 
 
 class DeviceMatrix:
@@ -98,6 +143,17 @@ class Reduction:
         check(lib().hb_eig_vectors(self.h, None if Zf is None else Zf.ctypes.data, self.n, C.byref(K), C.byref(ldk)))
         return EigVectors(values, K.value, self.n, ldk.value, self.device)
 
+    def vectors_dev(self, Zdev, values=None):
+        """K = Q Z in place in the DeviceMatrix Zdev (tridiagonal_eigh_device's), which is taken over: it is closed, the EigVectors owns the buffer"""
+        self._live("vectors_dev")
+        Zdev._live("vectors_dev")
+        if Zdev.n != self.n or Zdev.device != self.device:
+            raise ValueError("vectors_dev: Z must be n x n on the reduction's device")
+        K, ldk = C.c_void_p(), C.c_int64()
+        check(lib().hb_eig_vectors_dev(self.h, Zdev.ptr, Zdev.ld, C.byref(K), C.byref(ldk)))
+        Zdev.ptr = None
+        return EigVectors(values, K.value, self.n, ldk.value, self.device)
+
     def reflectors(self):
         self._live("reflectors")
         tau = np.zeros(max(self.n - 1, 0))
@@ -134,16 +190,24 @@ def upload(A, device=0, lda=None):
     return DeviceMatrix(p.value, n, ld.value, device)
 
 
-def eigh_device(A, keep_on_device=False, stats=None):
-    """(values, vectors) of the DeviceMatrix A, which is overwritten and closed. `stats` (a dict) receives the stages' seconds."""
+def eigh_device(A, keep_on_device=False, stats=None, tridiagonal="host"):
+    """(values, vectors) of the DeviceMatrix A, which is overwritten and closed. `stats` (a dict) receives the stages' seconds. tridiagonal:
+    "host" (dstemr) or "device" (tridiagonal_eigh_device; Z is back-transformed where it lies)."""
     import time
+    check_tridiagonal("eigh", tridiagonal)
     t0 = time.perf_counter()
     try:
         with Reduction(A) as red:
             t1 = time.perf_counter()
-            w, Z = tridiagonal_eigh(red.d, red.e)
-            t2 = time.perf_counter()
-            K = red.vectors(Z, w)
+            if tridiagonal == "device":
+                w, Zdev = tridiagonal_eigh_device(red.d, red.e, red.device)
+                t2 = time.perf_counter()
+                with Zdev:
+                    K = red.vectors_dev(Zdev, w)
+            else:
+                w, Z = tridiagonal_eigh(red.d, red.e)
+                t2 = time.perf_counter()
+                K = red.vectors(Z, w)
             t3 = time.perf_counter()
     finally:
         A.close()
@@ -155,8 +219,10 @@ def eigh_device(A, keep_on_device=False, stats=None):
         return w, K.toarray()
 
 
-def eigh(A, *, device=0, keep_on_device=False):
+def eigh(A, *, device=0, keep_on_device=False, tridiagonal="host"):
     """Eigenvalues (ascending) and eigenvectors of the symmetric host matrix A, as numpy.linalg.eigh(A) returns them (UPLO = "L"), with the
     reduction to tridiagonal form and the back-transformation on the device. keep_on_device=True returns an EigVectors handle (.values, .shape,
-    .ld, .toarray(), .close()) instead of the pair: the vectors stay on the device."""
-    return eigh_device(upload(A, device), keep_on_device)
+    .ld, .toarray(), .close()) instead of the pair: the vectors stay on the device. tridiagonal="device" solves the tridiagonal stage on the
+    device as well (divide and conquer) instead of with LAPACK dstemr on the host."""
+    check_tridiagonal("eigh", tridiagonal)
+    return eigh_device(upload(A, device), keep_on_device, tridiagonal=tridiagonal)

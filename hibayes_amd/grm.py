@@ -30,16 +30,20 @@ def grm_build_device(ctx, lambda_=0.0):
     return DeviceMatrix(p.value, ctx.n, ctx.n, ctx.device, free="hb_grm_free")
 
 
-def make_grm(M, lambda_=0.0, inverse=False, eigen=False, verbose=True, *, device=0, eigen_solver="host", keep_on_device=False):
+def make_grm(M, lambda_=0.0, inverse=False, eigen=False, verbose=True, *, device=0, eigen_solver="host", keep_on_device=False, tridiagonal="host"):
     """Mirror of make_grm() (reference src/rm.cpp:5-53). `M` is the n x m genotype matrix (int8 preferred, or integer-valued floats)
     or an engine.Context with the genotypes already resident. Returns G, or with eigen=True the pair (eigenvalues, eigenvectors) in
     numpy.linalg.eigh's ascending order. As in the reference, `lambda_` is added to the diagonal before the decomposition (:46) and
     is not part of the plain G. inverse=True (solve(), :39-42) is not implemented.
     eigen_solver: "host" (default) decomposes G with numpy.linalg.eigh; "device" with hibayes_amd.eig — G goes from hb_grm_build straight
     into the reduction and never visits the host. keep_on_device=True (eigen_solver="device" only) returns an eig.EigVectors handle
-    (.values, .toarray(), .close()) instead of the pair, for Context.poly_setup()."""
+    (.values, .toarray(), .close()) instead of the pair, for Context.poly_setup(). tridiagonal (eigen_solver="device" only): "host" (default)
+    solves the tridiagonal stage with LAPACK dstemr on one host thread; "device" with the device's divide and conquer (eig.tridiagonal_eigh_device),
+    so that no n x n matrix crosses the bus."""
     if eigen_solver not in ("host", "device"):
         raise ValueError("make_grm: eigen_solver must be \"host\" or \"device\", not %r" % (eigen_solver,))
+    from .eig import check_tridiagonal
+    check_tridiagonal("make_grm", tridiagonal, eigen_solver)
     if keep_on_device and not (eigen and eigen_solver == "device"):
         raise ValueError("make_grm: keep_on_device=True goes with eigen=True, eigen_solver=\"device\"")
     if inverse:
@@ -72,6 +76,6 @@ def make_grm(M, lambda_=0.0, inverse=False, eigen=False, verbose=True, *, device
         print("Eigen decomposition on G matrix")
     if eigen_solver == "device":
         from .eig import eigh_device
-        return eigh_device(G, keep_on_device)
+        return eigh_device(G, keep_on_device, tridiagonal=tridiagonal)
     ev, K = np.linalg.eigh(G)
     return ev, np.asfortranarray(K)

@@ -464,7 +464,10 @@ void hb_grm_free(double *G_dev);
  * The symmetric eigen-decomposition behind make_grm(eigen = TRUE) (reference src/rm.cpp:46-52: eigen_sym_dc, LAPACK dsyevd; R/bayes.r:292-294
  * hands its output to Bayes() as Kival / Ki) with its two O(n^3) stages on the device. The caller supplies the
  * O(n^2) stage between them — the eigenvalues and eigenvectors Z of the tridiagonal matrix (d, e), LAPACK dstemr or dstedc on the host:
- *     hb_eig_reduce  ->  (w, Z) = dstemr(d, e)  ->  hb_eig_vectors(Z)  ->  K = Q Z on the device, for hb_ctx_poly_setup(on_device = 1).
+ *     hb_eig_reduce  ->  (w, Z) = dstemr(d, e)  ->  hb_eig_vectors(Z)  ->  K = Q Z on the device, for hb_ctx_poly_setup(on_device = 1)
+ * — or leaves that stage on the device too (hb_eig_tridiagonal: divide and conquer, the dstedc inside the dsyevd of src/rm.cpp:46-52), and
+ * then no n x n matrix crosses the bus:
+ *     hb_eig_reduce  ->  hb_eig_tridiagonal(d, e) -> (w, Z_dev)  ->  hb_eig_vectors_dev(Z_dev)  ->  K = Q Z in Z's buffer.
  * No floating-point atomics: two runs on the same matrix agree bit for bit. Without a device every entry below that computes or copies
  * fails with HB_ERR_NO_DEVICE.
  * ------------------------------------------------------------------------------------ */
@@ -485,9 +488,28 @@ int hb_eig_tau(hb_eig *h, double *tau_host);
  * even leading dimension *ldk (every column 16-byte aligned, as hb_ctx_poly_setup(on_device = 1) requires), is the caller's and outlives
  * the handle; hb_eig_release frees it. */
 int hb_eig_vectors(hb_eig *h, const double *Z_host, int64_t ldz, double **K_dev, int64_t *ldk);
+/* LAPACK dstedc (compz = 'I') on the device: the eigenvalues w_host (n, ascending) and eigenvectors Z of the symmetric tridiagonal matrix with
+ * diagonal d_host (n) and off-diagonal e_host (n - 1; may be NULL for n = 1), by Cuppen's divide and conquer with Gu-Eisenstat vectors
+ * (DESIGN.md section 16). Column j of *Z_dev belongs to w_host[j]; Z has hb_eig_vectors' layout — leading dimension *ldz = n rounded up to 64,
+ * that many columns allocated, padding zero — is the caller's, and is freed with hb_eig_release or handed to hb_eig_vectors_dev. Refused
+ * before any device is asked for, HB_ERR_INVALID: a null pointer, n < 1, a non-finite d or e. A secular iteration or a leaf that does not
+ * converge within its hard cap of steps is HB_ERR_HIP with a text, never a silent result. Deterministic: no floating-point atomics. */
+int hb_eig_tridiagonal(const double *d_host, const double *e_host, int32_t n, int32_t device, double *w_host, double **Z_dev, int64_t *ldz);
+/* hb_eig_vectors for a Z that lies on the device (hb_eig_tridiagonal's): K = Q Z in place in Z's buffer, by the same panels. Ownership of the
+ * buffer passes to *K_dev (hb_eig_release); on failure it stays the caller's. ldz other than n rounded up to 64: HB_ERR_INVALID. */
+int hb_eig_vectors_dev(hb_eig *h, double *Z_dev, int64_t ldz, double **K_dev, int64_t *ldk);
+/* The merge tree hb_eig_tridiagonal uses for n rows and the given split points (ascending indices i whose e_i is negligible), a pure function
+ * of its arguments that needs no device: leaves [leaf_lo, leaf_hi) of at most *leaf_rows rows, merges of [lo, mid) with [mid, hi) at level
+ * merge_level (children before parents; all merges of a level are disjoint and go in the same launches), *levels the highest level. cap: the
+ * length of every array; n entries always suffice. */
+int hb_stedc_plan(int32_t n, const int32_t *splits, int32_t nsplit, int32_t cap, int32_t *leaf_lo, int32_t *leaf_hi, int32_t *nleaf, int32_t *merge_lo,
+                  int32_t *merge_mid, int32_t *merge_hi, int32_t *merge_level, int32_t *nmerge, int32_t *levels, int32_t *leaf_rows);
+/* Seconds of this process's last hb_eig_tridiagonal by phase, for tools/eig_timing.py: [0] leaves (with set-up), [1] gather and deflation scan,
+ * [2] rotations, secular equation and vector work, [3] U strips and GEMM, [4] copies and ordering; [5] the GEMM's floating-point operations. */
+int hb_stedc_stats(double *out, int32_t count);
 /* An n x n device matrix of this interface — K (the Ki of R/bayes.r:292-294), or the reduced A (src/rm.cpp:46-52) — to a host column-major array. */
 int hb_eig_download(const double *M_dev, int64_t ld_dev, int32_t n, int32_t device, double *M_host, int64_t ld_host);
-/* Frees what hb_eig_upload or hb_eig_vectors allocated (the Ki of R/bayes.r:292-294 once the fit is done). */
+/* Frees what hb_eig_upload, hb_eig_vectors or hb_eig_tridiagonal allocated (the Ki of R/bayes.r:292-294 once the fit is done). */
 void hb_eig_release(double *M_dev);
 /* Ends the borrowing of A_dev and frees the handle's panels (src/rm.cpp:46-52 keeps nothing either). NULL is allowed. */
 void hb_eig_destroy(hb_eig *h);
