@@ -21,7 +21,7 @@
 //     k_eig_kupd     K -= V Y, 64 x 64 tiles
 // No floating-point atomic anywhere; every sum has one order that depends on n and EIG_NB alone, so two runs agree bit for bit.
 #include "hb_internal.hpp"
-#include "hb_wave.hpp"
+#include "hb_mma.hpp"
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -29,8 +29,6 @@
 #ifndef EIG_NB
 #define EIG_NB 64 // panel width (32 or 64): 64 halves the traffic of the trailing update and of the back-transformation
 #endif
-
-typedef double v4d __attribute__((ext_vector_type(4)));
 
 struct hb_eig {
     int n = 0, device = 0;
@@ -266,27 +264,20 @@ __global__ __launch_bounds__(ET) void k_eig_wfin(int n, int k, const double *__r
     if (i < n) Wc[i] = fma(a, Vc[i], Wc[i]);
 }
 
-// v_mfma_f64_16x16x4_f64: lane l gives A[row l & 15][k = l >> 4] and B[k = l >> 4][col l & 15]; it receives, in register r,
-// D[row (l >> 4) + 4 r][col l & 15]. In the three kernels below the columns of D run along the index that is contiguous in memory.
-__device__ __forceinline__ v4d mfma_f64(double a, double b, v4d acc) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0); }
+// The three matrix-core kernels below (hb_mma.hpp: mfma_f64 and its layout): the columns of D run along the index that is contiguous in memory.
 
 // A22 -= V W' + W V' on [k1, n)^2: 64 x 64 tiles bi >= bj of the lower triangle, four waves of 32 x 32; entry (i, j), i >= j, is computed once
 // and stored at (i, j) and (j, i). The panel buffers are read past row n (zeros, inside ldv); the matrix is not.
 __global__ __launch_bounds__(256) void k_eig_trail(double *__restrict__ A, int64_t lda, int n, int k1, const double *__restrict__ Vp, const double *__restrict__ Wp,
                                                    int64_t ldv)
 {
-    int bi = (int)((sqrt(8.0 * (double)blockIdx.x + 1.0) - 1.0) * 0.5);
-    while ((long long)(bi + 1) * (bi + 2) / 2 <= (long long)blockIdx.x) bi++;
-    while ((long long)bi * (bi + 1) / 2 > (long long)blockIdx.x) bi--;
-    const int bj = (int)(blockIdx.x - (long long)bi * (bi + 1) / 2);
+    int bi, bj;
+    tri_tile(blockIdx.x, &bi, &bj);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, wr = wave >> 1, wc = wave & 1, lr = lane & 15, q = lane >> 4;
     if (bi == bj && wr < wc) return; // (the wave's entries all lie above the diagonal)
     const int i0 = k1 + bi * TS + wr * 32, j0 = k1 + bj * TS + wc * 32;
     v4d acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; a++)
-#pragma unroll
-        for (int b = 0; b < 2; b++) acc[a][b] = (v4d){0.0, 0.0, 0.0, 0.0};
+    mma_f64_zero(acc);
 #pragma unroll 4
     for (int s = 0; s < NB / 4; s++) {
         const int64_t co = (int64_t)(4 * s + q) * ldv;
@@ -312,7 +303,7 @@ __global__ __launch_bounds__(256) void k_eig_trail(double *__restrict__ A, int64
         for (int b = 0; b < 2; b++)
 #pragma unroll
             for (int r = 0; r < 4; r++) {
-                const int i = i0 + 16 * a + lr, j = j0 + 16 * b + q + 4 * r;
+                const int i = i0 + mma_f64_col(a, lane), j = j0 + mma_f64_row(b, r, lane);
                 if (i < n && j <= i) {
                     const double nv = A[(int64_t)j * lda + i] - acc[a][b][r];
                     A[(int64_t)j * lda + i] = nv;
@@ -339,10 +330,9 @@ __global__ __launch_bounds__(ET) void k_eig_expand(const double *__restrict__ A,
 __global__ __launch_bounds__(ET) void k_eig_gram(const double *__restrict__ Vp, int64_t ldv, int n, int k0, double *__restrict__ S)
 {
     __shared__ double red[ET];
-    int b = (int)((sqrt(8.0 * (double)blockIdx.x + 1.0) + 1.0) * 0.5);
-    while (b * (b - 1) / 2 > (int)blockIdx.x) b--;
-    while ((b + 1) * b / 2 <= (int)blockIdx.x) b++;
-    const int a = blockIdx.x - b * (b - 1) / 2;
+    int a, b;
+    tri_tile(blockIdx.x, &b, &a); // (the strict triangle: b - 1 >= a)
+    b++;
     const double *x = Vp + (int64_t)a * ldv, *y = Vp + (int64_t)b * ldv;
     double s0 = 0.0, s1 = 0.0;
     int i = k0 + b + 1 + threadIdx.x;
@@ -426,10 +416,7 @@ __global__ __launch_bounds__(256) void k_eig_kupd(double *__restrict__ K, int64_
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, wr = wave >> 1, wc = wave & 1, lr = lane & 15, q = lane >> 4;
     const int i0 = rbase + blockIdx.x * TS + wr * 32, j0 = blockIdx.y * TS + wc * 32;
     v4d acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; a++)
-#pragma unroll
-        for (int b = 0; b < 2; b++) acc[a][b] = (v4d){0.0, 0.0, 0.0, 0.0};
+    mma_f64_zero(acc);
 #pragma unroll 4
     for (int s = 0; s < NB / 4; s++) {
         double vi[2], yj[2];
@@ -449,7 +436,7 @@ __global__ __launch_bounds__(256) void k_eig_kupd(double *__restrict__ K, int64_
         for (int b = 0; b < 2; b++)
 #pragma unroll
             for (int r = 0; r < 4; r++) {
-                double *p = K + (int64_t)(j0 + 16 * b + q + 4 * r) * ldk + i0 + 16 * a + lr;
+                double *p = K + (int64_t)(j0 + mma_f64_row(b, r, lane)) * ldk + i0 + mma_f64_col(a, lane);
                 *p -= acc[a][b][r];
             }
 }

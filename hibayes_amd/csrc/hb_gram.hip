@@ -7,8 +7,7 @@
 // v_mfma_i32_32x32x32_i8 straight from one 16-byte global load, no LDS transpose.
 // One wave = one 64x64 block of the panel's P x P matrix (2x2 MFMA tiles of 32x32).
 #include "hb_internal.hpp"
-#include "hb_wave.hpp"
-#include <cstdlib>
+#include "hb_mma.hpp"
 
 // Band layout: gram[(p * (L+1) + l) * P*P + row * P + col] = x_{(p-l)P + row} . x_{pP + col}, l = 0..L
 // (l = 0: the panel's own Gram; l >= 1: the panels the look-ahead pipeline has not yet folded into
@@ -23,26 +22,11 @@ __global__ __launch_bounds__(64) void k_gram(const int8_t *__restrict__ X, int64
     const int rem = blockIdx.x % (nb * nb);
     const int bi = rem / nb, bj = rem % nb;
     const int lane = threadIdx.x;
-    const int8_t *xa = X + ((int64_t)(p - l) * P + bi * 64 + (lane & 31)) * ld + 16 * (lane >> 5);
-    const int8_t *xb = X + ((int64_t)p * P + bj * 64 + (lane & 31)) * ld + 16 * (lane >> 5);
+    const int8_t *xa = X + ((int64_t)(p - l) * P + bi * 64) * ld + mma_i8_operand(lane, ld);
+    const int8_t *xb = X + ((int64_t)p * P + bj * 64) * ld + mma_i8_operand(lane, ld);
     v16i acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; a++)
-#pragma unroll
-        for (int b = 0; b < 2; b++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[a][b][r] = 0;
-    for (int64_t kk = 0; kk < ld; kk += 32) {
-        const v4i a0 = *reinterpret_cast<const v4i *>(xa + kk);
-        const v4i a1 = *reinterpret_cast<const v4i *>(xa + 32 * ld + kk);
-        const v4i b0 = *reinterpret_cast<const v4i *>(xb + kk);
-        const v4i b1 = *reinterpret_cast<const v4i *>(xb + 32 * ld + kk);
-        acc[0][0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, b0, acc[0][0], 0, 0, 0);
-        acc[0][1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, b1, acc[0][1], 0, 0, 0);
-        acc[1][0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, b0, acc[1][0], 0, 0, 0);
-        acc[1][1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, b1, acc[1][1], 0, 0, 0);
-    }
-    // C/D layout of the 32x32 MFMA: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
+    mma_i8_zero(acc);
+    for (int64_t kk = 0; kk < ld; kk += 32) mma_i8_step(acc, xa + kk, xb + kk, ld);
     int32_t *gp = gram + (size_t)pl * P * P;
 #pragma unroll
     for (int a = 0; a < 2; a++)
@@ -50,23 +34,18 @@ __global__ __launch_bounds__(64) void k_gram(const int8_t *__restrict__ X, int64
         for (int b = 0; b < 2; b++)
 #pragma unroll
             for (int r = 0; r < 16; r++) {
-                const int row = bi * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                const int col = bj * 64 + b * 32 + (lane & 31);
+                const int row = bi * 64 + mma_i8_row(a, r, lane);
+                const int col = bj * 64 + mma_i8_col(b, lane);
                 gp[(size_t)row * P + col] = acc[a][b][r];
             }
 }
 
-// The same blocks for P >= 256, one 256 x 256 tile per workgroup of 16 waves (4 x 4 wave tiles of 64 x 64): per 64-row step the
-// 256 + 256 operand columns are staged through LDS once (16-byte global loads into registers one step ahead, ds_write_b128 with
-// an 80-byte column stride so that the MFMA operand reads are bank-conflict free) instead of being re-read from global memory by
-// every wave tile — 4x less traffic than k_gram (9.5 TB -> 1.8 TB of fetches for the 18 GB band at n=50k, m=500k).
-#define HG_T 256
-#define HG_KS 64
-#define HG_CS 80 /* bytes per staged column: 64 + 16 */
+// The same blocks for P >= 256, one 256 x 256 tile per workgroup of 16 waves: hb_mma.hpp's staged loop, 4x less traffic than k_gram
+// (9.5 TB -> 1.8 TB of fetches for the 18 GB band at n=50k, m=500k).
 __global__ __launch_bounds__(1024) void k_gram_tiled(const int8_t *__restrict__ X, int64_t ld, int P, int L, int32_t *__restrict__ gram, int p_lo)
 {
-    __shared__ __attribute__((aligned(16))) char sa[HG_T * HG_CS], sb[HG_T * HG_CS];
-    const int nt = P / HG_T;
+    __shared__ __attribute__((aligned(16))) char sa[MMA_T * MMA_CS], sb[MMA_T * MMA_CS];
+    const int nt = P / MMA_T;
     const int pl = blockIdx.x / (nt * nt) + p_lo * (L + 1);
     const int p = pl / (L + 1), l = pl % (L + 1);
     if (p - l < 0) return;
@@ -74,43 +53,11 @@ __global__ __launch_bounds__(1024) void k_gram_tiled(const int8_t *__restrict__ 
     const int ti = rem / nt, tj = rem % nt;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int wr = wave >> 2, wc = wave & 3;
-    // staging: thread -> (column tid / 4, 16-byte part tid % 4) of both operand tiles
-    const int scol = tid >> 2, spart = tid & 3;
-    const int8_t *ga = X + ((int64_t)(p - l) * P + ti * HG_T + scol) * ld + spart * 16;
-    const int8_t *gb = X + ((int64_t)p * P + tj * HG_T + scol) * ld + spart * 16;
-    char *wa = sa + scol * HG_CS + spart * 16, *wb = sb + scol * HG_CS + spart * 16;
-    // MFMA operands: lane & 31 = column inside the 32-wide sub-tile, lane >> 5 = which 16 of the 32 k values
-    const char *ra = sa + (wr * 64 + (lane & 31)) * HG_CS + (lane >> 5) * 16;
-    const char *rb = sb + (wc * 64 + (lane & 31)) * HG_CS + (lane >> 5) * 16;
+    const int8_t *ga = X + ((int64_t)(p - l) * P + ti * MMA_T + mma_stage_col(tid)) * ld + mma_stage_part(tid) * 16;
+    const int8_t *gb = X + ((int64_t)p * P + tj * MMA_T + mma_stage_col(tid)) * ld + mma_stage_part(tid) * 16;
     v16i acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; a++)
-#pragma unroll
-        for (int b = 0; b < 2; b++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[a][b][r] = 0;
-    v4i na = *reinterpret_cast<const v4i *>(ga), nb = *reinterpret_cast<const v4i *>(gb);
-    for (int64_t kk = 0; kk < ld; kk += HG_KS) {
-        __syncthreads(); // everybody is done reading the previous step
-        *reinterpret_cast<v4i *>(wa) = na;
-        *reinterpret_cast<v4i *>(wb) = nb;
-        __syncthreads();
-        if (kk + HG_KS < ld) { // next step's operands travel while this one is multiplied
-            na = *reinterpret_cast<const v4i *>(ga + kk + HG_KS);
-            nb = *reinterpret_cast<const v4i *>(gb + kk + HG_KS);
-        }
-#pragma unroll
-        for (int ks = 0; ks < HG_KS; ks += 32) {
-            const v4i a0 = *reinterpret_cast<const v4i *>(ra + ks);
-            const v4i a1 = *reinterpret_cast<const v4i *>(ra + 32 * HG_CS + ks);
-            const v4i b0 = *reinterpret_cast<const v4i *>(rb + ks);
-            const v4i b1 = *reinterpret_cast<const v4i *>(rb + 32 * HG_CS + ks);
-            acc[0][0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, b1, acc[1][1], 0, 0, 0);
-        }
-    }
+    mma_i8_zero(acc);
+    mma_i8_staged(acc, ga, gb, ld, sa, sb, tid);
     int32_t *gp = gram + (size_t)pl * P * P;
 #pragma unroll
     for (int a = 0; a < 2; a++)
@@ -118,8 +65,8 @@ __global__ __launch_bounds__(1024) void k_gram_tiled(const int8_t *__restrict__ 
         for (int b = 0; b < 2; b++)
 #pragma unroll
             for (int r = 0; r < 16; r++) {
-                const int row = ti * HG_T + wr * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                const int col = tj * HG_T + wc * 64 + b * 32 + (lane & 31);
+                const int row = ti * MMA_T + wr * 64 + mma_i8_row(a, r, lane);
+                const int col = tj * MMA_T + wc * 64 + mma_i8_col(b, lane);
                 gp[(size_t)row * P + col] = acc[a][b][r];
             }
 }
@@ -130,8 +77,8 @@ int hbk_unpack2(hb_ctx *c, int col0, int ncols, int8_t *dst);
 // panels pa - Lg .. pb - 1 are read)
 static int gram_launch(hb_ctx *c, const int8_t *Xv, int pa, int pb)
 {
-    if (c->P >= HG_T && !getenv("HB_GRAM_UNTILED")) {
-        const int nt = c->P / HG_T;
+    if (c->P >= MMA_T) {
+        const int nt = c->P / MMA_T;
         hipLaunchKernelGGL(k_gram_tiled, dim3((unsigned)((pb - pa) * (c->Lg + 1) * nt * nt)), dim3(1024), 0, c->stream, Xv, c->ld,
                            c->P, c->Lg, c->gram, pa);
     } else {

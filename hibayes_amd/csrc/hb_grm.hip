@@ -20,7 +20,7 @@
 // No floating-point atomic anywhere: every sum has one fixed order and two runs agree bit for bit.
 #include "hb_internal.hpp"
 #include "hb_rng.hpp"
-#include "hb_wave.hpp"
+#include "hb_mma.hpp"
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -47,8 +47,7 @@ namespace {
 // GRM
 // ---------------------------------------------------------------------------------------------------------------------------------
 constexpr int GT = 128;            // individuals per side of a workgroup's tile (4 waves, 64 x 64 each)
-constexpr int GK = 64;             // markers per step
-constexpr int GCS = 80;            // bytes per staged row: 64 + 16, so that the 16-byte operand reads are conflict free
+constexpr int GK = 64;             // markers per step (a staged row takes hb_mma.hpp's MMA_CS bytes: the same conflict-free operand reads)
 constexpr int GRM_KCHUNK = 65536;  // markers summed in int32: 128^2 * 65536 = 2^30 < 2^31 for every int8 code
 
 // THE expression: raw_ij = (S_ij - (a_i + a_j) / n) + C / n^2, with S, a_i + a_j exact integers, cn2 = (double)C / (n * n)
@@ -84,7 +83,7 @@ __device__ __forceinline__ void grm_stage(const int8_t *__restrict__ X, int64_t 
         for (int rr = 0; rr < 4; rr++) {
             const int row = rg * 4 + rr;
             const unsigned v = (row0 + row < n) ? tr_row(d[0], d[1], d[2], d[3], rr) : 0u;
-            *reinterpret_cast<unsigned *>(lds + row * GCS + kq) = v;
+            *reinterpret_cast<unsigned *>(lds + row * MMA_CS + kq) = v;
         }
     }
 }
@@ -94,48 +93,31 @@ __device__ __forceinline__ void grm_stage(const int8_t *__restrict__ X, int64_t 
 // triangle, and k_grm_combine fills both from it.
 __global__ __launch_bounds__(256) void k_grm_tile(const int8_t *__restrict__ X, int64_t ld, int n, int k0, int k1, long long *__restrict__ S, int64_t ldS, int first)
 {
-    __shared__ __attribute__((aligned(16))) char sa[GT * GCS], sb[GT * GCS];
-    int bi = (int)((sqrt(8.0 * (double)blockIdx.x + 1.0) - 1.0) * 0.5);
-    while ((long long)(bi + 1) * (bi + 2) / 2 <= (long long)blockIdx.x) bi++;
-    while ((long long)bi * (bi + 1) / 2 > (long long)blockIdx.x) bi--;
-    const int bj = (int)(blockIdx.x - (long long)bi * (bi + 1) / 2);
+    __shared__ __attribute__((aligned(16))) char sa[GT * MMA_CS], sb[GT * MMA_CS];
+    int bi, bj;
+    tri_tile(blockIdx.x, &bi, &bj);
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int wr = wave >> 1, wc = wave & 1;
-    const char *ra = sa + (wr * 64 + (lane & 31)) * GCS + (lane >> 5) * 16;
-    const char *rb = sb + (wc * 64 + (lane & 31)) * GCS + (lane >> 5) * 16;
+    const char *ra = sa + wr * 64 * MMA_CS + mma_i8_operand(lane, MMA_CS);
+    const char *rb = sb + wc * 64 * MMA_CS + mma_i8_operand(lane, MMA_CS);
     v16i acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; a++)
-#pragma unroll
-        for (int b = 0; b < 2; b++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[a][b][r] = 0;
+    mma_i8_zero(acc);
     for (int kk = k0; kk < k1; kk += GK) {
         __syncthreads(); // everybody is done reading the previous step
         grm_stage(X, ld, n, bi * GT, kk, k1, sa, tid);
         grm_stage(X, ld, n, bj * GT, kk, k1, sb, tid);
         __syncthreads();
 #pragma unroll
-        for (int ks = 0; ks < GK; ks += 32) {
-            const v4i a0 = *reinterpret_cast<const v4i *>(ra + ks);
-            const v4i a1 = *reinterpret_cast<const v4i *>(ra + 32 * GCS + ks);
-            const v4i b0 = *reinterpret_cast<const v4i *>(rb + ks);
-            const v4i b1 = *reinterpret_cast<const v4i *>(rb + 32 * GCS + ks);
-            acc[0][0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, b1, acc[1][1], 0, 0, 0);
-        }
+        for (int ks = 0; ks < GK; ks += 32) mma_i8_step(acc, ra + ks, rb + ks, MMA_CS);
     }
-    // C/D layout of the 32x32 MFMA: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
 #pragma unroll
     for (int a = 0; a < 2; a++)
 #pragma unroll
         for (int b = 0; b < 2; b++)
 #pragma unroll
             for (int r = 0; r < 16; r++) {
-                const int i = bi * GT + wr * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                const int j = bj * GT + wc * 64 + b * 32 + (lane & 31);
+                const int i = bi * GT + wr * 64 + mma_i8_row(a, r, lane);
+                const int j = bj * GT + wc * 64 + mma_i8_col(b, lane);
                 if (i < n && j <= i) {
                     long long *p = S + (int64_t)i * ldS + j;
                     *p = first ? (long long)acc[a][b][r] : *p + (long long)acc[a][b][r];

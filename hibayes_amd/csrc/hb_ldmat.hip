@@ -1,8 +1,8 @@
 // hb_ldmat.hip — the LD variance-covariance matrix of the resident genotypes: ldmat() of the reference (R/ldm.r:31-112) as
 // tXXmat_Geno / tXXmat_Chr compute it (src/tXXmat.cpp:100-206, :504-626), without the four *_gwas variants.
 //
-// The work is the m x m integer contraction X'X over int8 columns — k_gram_tiled's tile loop (hb_gram.hip) on arbitrary column
-// pairs — followed per entry by the reference's own fp64 arithmetic, one correctly rounded operation at a time and in its order:
+// The work is the m x m integer contraction X'X over int8 columns — the staged tile loop of hb_mma.hpp (k_gram_tiled's) on arbitrary
+// column pairs — followed per entry by the reference's own fp64 arithmetic, one correctly rounded operation at a time and in its order:
 // the cross-products are exact integers, so every entry equals the reference's in every bit. Three things that arithmetic fixes:
 //   * it is not symmetric in its two markers: `ind * m1 * m2` is (ind * m1) * m2 with m1 the mean of the marker of the SMALLER
 //     index (the outer loop's j, :130-145), so each entry is computed with min(row, col) in the sum1 / m1 / p1 role;
@@ -14,7 +14,7 @@
 // row-sorted (row, value) lists per column (k_ld_compact: every other kind, the reference returns sp_mat there).
 // This whole unit is compiled with floating-point contraction off (Makefile and the pragma below): hipcc fuses by default.
 #include "hb_ldm.hpp"
-#include "hb_wave.hpp"
+#include "hb_mma.hpp"
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -62,65 +62,31 @@ struct ld_epi {
 };
 
 // ---- one strip: rows = all markers, columns = positions [c0, c0 + w) of the column order perm[] ----
-// k_gram_tiled's loop: a 256 x 256 tile per workgroup of 16 waves, both operand tiles staged through LDS in 64-row steps
-// (80-byte column stride: conflict-free operand reads), 2 x 2 v_mfma_i32_32x32x32_i8 per wave, the next step's operands in
-// flight. The strip's columns are the MFMA's A operand (accumulator registers) and the matrix' rows its B operand (lanes), so
+// hb_mma.hpp's staged loop (the one k_gram_tiled runs): a 256 x 256 tile per workgroup of 16 waves, 2 x 2 v_mfma_i32_32x32x32_i8 per
+// wave. The strip's columns are the MFMA's A operand (accumulator registers) and the matrix' rows its B operand (lanes), so
 // that a wave's stores run along a column of the column-major strip. Both operand sets go through perm[]; positions past the
 // ragged end read the last valid column and are masked at the store. XA / XB: where genotype column 0 WOULD be (windows of a
 // 2-bit resident matrix). Row tiles [rt0, rt0 + nrt) are this launch's. tchr (block mode): min / max chromosome id of every
 // 256-tile of positions — a tile whose two ranges are disjoint holds zeros only and is left to the strip's memset.
-#define LD_T 256
-#define LD_KS 64
-#define LD_CS 80
 template <bool SPARSE> // (a template, not a run-time switch: the arm not taken costs its fp64 division per element otherwise)
 __global__ __launch_bounds__(1024) void k_ld_strip(const int8_t *__restrict__ XA, const int8_t *__restrict__ XB, int64_t ld, int m,
                                                    const int32_t *__restrict__ perm, int c0, int w, int rt0, int nrt,
                                                    const int32_t *__restrict__ tchr, ld_epi e, double *__restrict__ strip)
 {
-    __shared__ __attribute__((aligned(16))) char sa[LD_T * LD_CS], sb[LD_T * LD_CS];
+    __shared__ __attribute__((aligned(16))) char sa[MMA_T * MMA_CS], sb[MMA_T * MMA_CS];
     const int tj = rt0 + (int)(blockIdx.x % (unsigned)nrt), ti = (int)(blockIdx.x / (unsigned)nrt);
     if (tchr) { // (uniform per workgroup, before the first barrier)
-        const int ct = c0 / LD_T + ti;
+        const int ct = c0 / MMA_T + ti;
         if (tchr[2 * tj + 1] < tchr[2 * ct] || tchr[2 * ct + 1] < tchr[2 * tj]) return;
     }
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int wr = wave >> 2, wc = wave & 3;
     const int cend = c0 + w; // (<= m)
-    const int scol = tid >> 2, spart = tid & 3;
-    const int8_t *ga = XA + (int64_t)perm[min(c0 + ti * LD_T + scol, cend - 1)] * ld + spart * 16;
-    const int8_t *gb = XB + (int64_t)perm[min(tj * LD_T + scol, m - 1)] * ld + spart * 16;
-    char *wa = sa + scol * LD_CS + spart * 16, *wb = sb + scol * LD_CS + spart * 16;
-    const char *ra = sa + (wr * 64 + (lane & 31)) * LD_CS + (lane >> 5) * 16;
-    const char *rb = sb + (wc * 64 + (lane & 31)) * LD_CS + (lane >> 5) * 16;
+    const int8_t *ga = XA + (int64_t)perm[min(c0 + ti * MMA_T + mma_stage_col(tid), cend - 1)] * ld + mma_stage_part(tid) * 16;
+    const int8_t *gb = XB + (int64_t)perm[min(tj * MMA_T + mma_stage_col(tid), m - 1)] * ld + mma_stage_part(tid) * 16;
     v16i acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; a++)
-#pragma unroll
-        for (int b = 0; b < 2; b++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[a][b][r] = 0;
-    v4i na = *reinterpret_cast<const v4i *>(ga), nb = *reinterpret_cast<const v4i *>(gb);
-    for (int64_t kk = 0; kk < ld; kk += LD_KS) {
-        __syncthreads();
-        *reinterpret_cast<v4i *>(wa) = na;
-        *reinterpret_cast<v4i *>(wb) = nb;
-        __syncthreads();
-        if (kk + LD_KS < ld) {
-            na = *reinterpret_cast<const v4i *>(ga + kk + LD_KS);
-            nb = *reinterpret_cast<const v4i *>(gb + kk + LD_KS);
-        }
-#pragma unroll
-        for (int ks = 0; ks < LD_KS; ks += 32) {
-            const v4i a0 = *reinterpret_cast<const v4i *>(ra + ks);
-            const v4i a1 = *reinterpret_cast<const v4i *>(ra + 32 * LD_CS + ks);
-            const v4i b0 = *reinterpret_cast<const v4i *>(rb + ks);
-            const v4i b1 = *reinterpret_cast<const v4i *>(rb + 32 * LD_CS + ks);
-            acc[0][0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, b1, acc[1][1], 0, 0, 0);
-        }
-    }
+    mma_i8_zero(acc);
+    mma_i8_staged(acc, ga, gb, ld, sa, sb, tid);
     // ---- epilogue: src/tXXmat.cpp:145-152 / :168 / :177-179 per accumulator element, j = the smaller marker index ----
     // C/D layout: the lane carries the B operand's column (here: the matrix row), the register the A operand's (the strip column)
     int rowm[2];
@@ -129,7 +95,7 @@ __global__ __launch_bounds__(1024) void k_ld_strip(const int8_t *__restrict__ XA
     int rc[2];
 #pragma unroll
     for (int b = 0; b < 2; b++) {
-        const int rp = tj * LD_T + wc * 64 + b * 32 + (lane & 31);
+        const int rp = tj * MMA_T + wc * 64 + mma_i8_col(b, lane);
         rok[b] = rp < m;
         rowm[b] = perm[min(rp, m - 1)];
         rs[b] = e.sum[rowm[b]];
@@ -141,7 +107,7 @@ __global__ __launch_bounds__(1024) void k_ld_strip(const int8_t *__restrict__ XA
     for (int a = 0; a < 2; a++)
 #pragma unroll
         for (int r = 0; r < 16; r++) {
-            const int cp = c0 + ti * LD_T + wr * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            const int cp = c0 + ti * MMA_T + wr * 64 + mma_i8_row(a, r, lane);
             if (cp >= cend) continue;
             const int colm = perm[cp];
             const double cs = e.sum[colm], cm = e.mean[colm], cx = e.xx[colm];
@@ -244,8 +210,8 @@ int build(hb_ctx *c, const int32_t *chr, bool sparse, double chisq, int64_t stri
     const auto t_all = hb_clk::now();
     hb_bufs D; // freed on every way out of the build
     // ---- where the int8 columns are: resident, or unpacked from the 2-bit layout (whole if small, else a window at a time) ----
-    int64_t wincols = std::max<int64_t>(LD_T, ((int64_t)1 << 30) / ld / LD_T * LD_T);
-    if (const char *ev = getenv("HB_LDM_WINDOW_COLS")) wincols = std::max<int64_t>(LD_T, (int64_t)atoi(ev) / LD_T * LD_T); // (tests: force the windowed path)
+    int64_t wincols = std::max<int64_t>(MMA_T, ((int64_t)1 << 30) / ld / MMA_T * MMA_T);
+    if (const char *ev = getenv("HB_LDM_WINDOW_COLS")) wincols = std::max<int64_t>(MMA_T, (int64_t)atoi(ev) / MMA_T * MMA_T); // (tests: force the windowed path)
     const int8_t *Xfull = c->X;
     int8_t *winA = nullptr, *winB = nullptr;
     if (!Xfull && wincols >= m) {
@@ -276,15 +242,15 @@ int build(hb_ctx *c, const int32_t *chr, bool sparse, double chisq, int64_t stri
     std::vector<int32_t> perm(m);
     std::iota(perm.begin(), perm.end(), 0);
     if (use_chr && Xfull) std::stable_sort(perm.begin(), perm.end(), [&](int32_t x, int32_t y) { return chr[x] < chr[y]; });
-    const int ntile = (m + LD_T - 1) / LD_T;
+    const int ntile = (m + MMA_T - 1) / MMA_T;
     int32_t *d_perm = nullptr, *d_chr = nullptr, *d_tchr = nullptr;
     HB_TRY(D.get(&d_perm, m));
     HB_HIP(hipMemcpy(d_perm, perm.data(), sizeof(int32_t) * m, hipMemcpyHostToDevice));
     if (use_chr) {
         std::vector<int32_t> tc(2 * (size_t)ntile);
         for (int t = 0; t < ntile; t++) {
-            int32_t lo = chr[perm[t * LD_T]], hi = lo;
-            for (int p = t * LD_T; p < std::min(m, (t + 1) * LD_T); p++) {
+            int32_t lo = chr[perm[t * MMA_T]], hi = lo;
+            for (int p = t * MMA_T; p < std::min(m, (t + 1) * MMA_T); p++) {
                 lo = std::min(lo, chr[perm[p]]);
                 hi = std::max(hi, chr[perm[p]]);
             }
@@ -300,8 +266,8 @@ int build(hb_ctx *c, const int32_t *chr, bool sparse, double chisq, int64_t stri
     const bool compacted = l->kind != HB_LDM_KIND_DENSE;
     const int64_t budget = strip_bytes > 0 ? strip_bytes : ((int64_t)1 << 30);
     const int64_t percol = (int64_t)m * (compacted ? 20 : 8);
-    const int m_up = ntile * LD_T;
-    const int w = (int)std::min<int64_t>(std::min(m_up, 32768), std::max<int64_t>(LD_T, budget / percol / LD_T * LD_T)); // (k_ld_scatter: one grid row per strip column)
+    const int m_up = ntile * MMA_T;
+    const int w = (int)std::min<int64_t>(std::min(m_up, 32768), std::max<int64_t>(MMA_T, budget / percol / MMA_T * MMA_T)); // (k_ld_scatter: one grid row per strip column)
     const size_t scount = (size_t)m * (size_t)std::min(w, m);
     double *d_strip = nullptr, *d_val = nullptr;
     int32_t *d_idx = nullptr, *d_cnt = nullptr;
@@ -332,7 +298,7 @@ int build(hb_ctx *c, const int32_t *chr, bool sparse, double chisq, int64_t stri
     std::vector<int32_t> cnt(w);
     std::vector<int64_t> off(w);
     for (int c0 = 0; c0 < m; c0 += w) {
-        const int ws = std::min(w, m - c0), ntc = (ws + LD_T - 1) / LD_T;
+        const int ws = std::min(w, m - c0), ntc = (ws + MMA_T - 1) / MMA_T;
         t0 = hb_clk::now();
         if (use_chr) HB_HIP(hipMemsetAsync(d_strip, 0, sizeof(double) * (size_t)m * ws, c->stream)); // (tiles across chromosomes are skipped)
         if (Xfull) {
@@ -341,10 +307,10 @@ int build(hb_ctx *c, const int32_t *chr, bool sparse, double chisq, int64_t stri
         } else { // perm is the identity here: position = marker
             HB_TRY(hbk_unpack2(c, c0, ws, winA));
             for (int r0 = 0; r0 < m; r0 += (int)wincols) {
-                const int nr = (int)std::min<int64_t>(wincols, m - r0), nrt = (nr + LD_T - 1) / LD_T;
+                const int nr = (int)std::min<int64_t>(wincols, m - r0), nrt = (nr + MMA_T - 1) / MMA_T;
                 HB_TRY(hbk_unpack2(c, r0, nr, winB));
                 hipLaunchKernelGGL(kstrip, dim3((unsigned)(nrt * ntc)), dim3(1024), 0, c->stream, winA - (int64_t)c0 * ld,
-                                   winB - (int64_t)r0 * ld, ld, m, d_perm, c0, ws, r0 / LD_T, nrt, d_tchr, e, d_strip);
+                                   winB - (int64_t)r0 * ld, ld, m, d_perm, c0, ws, r0 / MMA_T, nrt, d_tchr, e, d_strip);
             }
         }
         HB_HIP(hipGetLastError());

@@ -23,6 +23,7 @@
 // No floating-point atomic; every sum's order is a function of n, the split points, STEDC_LEAF and STEDC_STRIP alone. Peak device memory: Z, one
 // workspace of the same size, n x STEDC_STRIP doubles of U and a few n-vectors.
 #include "hb_internal.hpp"
+#include "hb_mma.hpp"
 #include "hb_stedcplan.hpp"
 #include <cmath>
 #include <cstdio>
@@ -34,8 +35,6 @@
 #endif
 #define STEDC_MAXIT 100 // steps of the secular iteration at most: reaching it is an error
 #define STEDC_SWEEPS 30 // Jacobi sweeps of a leaf at most: reaching it is an error
-
-typedef double v4d __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -369,12 +368,8 @@ __global__ __launch_bounds__(SS) void k_stedc_ubuild(int strip, const int *__res
     Ut[(int64_t)p * SS + threadIdx.x] = u;
 }
 
-// v_mfma_f64_16x16x4_f64 as in hb_eig.hip: lane l gives A[row l & 15][k = l >> 4] and B[k = l >> 4][col l & 15] and receives, in register r,
-// D[row (l >> 4) + 4 r][col l & 15]
-__device__ __forceinline__ v4d mfma_f64(double a, double b, v4d acc) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0); }
-
 // Znew[i][lo + c] = sum_t Zold[i][src[t]] U[list[t]][c] for the rows i of one child and the roots c of the strip: 64 x 64 tiles, four waves of
-// 32 x 32, the list in its order, four entries per MFMA. blockIdx.y = 2 * merge + child; blockIdx.x = 4-column-tile strips by row tiles. Rows past
+// 32 x 32 (hb_mma.hpp: mfma_f64 and its layout), the list in its order, four entries per MFMA. blockIdx.y = 2 * merge + child; blockIdx.x = 4-column-tile strips by row tiles. Rows past
 // the child's last are read from its last row and not stored; list entries past its end enter as zeros on both sides.
 __global__ __launch_bounds__(256) void k_stedc_gemm(int strip, const merge_dev *__restrict__ M, const int *__restrict__ tlist, const int *__restrict__ blist,
                                                     const int *__restrict__ tsrc, const int *__restrict__ bsrc, const double *__restrict__ Zold,
@@ -389,10 +384,7 @@ __global__ __launch_bounds__(256) void k_stedc_gemm(int strip, const merge_dev *
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, wr = wave >> 1, wc = wave & 1, lr = lane & 15, q = lane >> 4;
     const int i0 = r0 + tr * 64 + wr * 32, cb = tc * 64 + wc * 32;
     v4d acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; a++)
-#pragma unroll
-        for (int b = 0; b < 2; b++) acc[a][b] = (v4d){0.0, 0.0, 0.0, 0.0};
+    mma_f64_zero(acc);
     const int ra = min(i0 + lr, r1 - 1), rb = min(i0 + 16 + lr, r1 - 1);
     for (int s4 = 0; s4 < L; s4 += 4) {
         const int t = s4 + q;
@@ -416,7 +408,7 @@ __global__ __launch_bounds__(256) void k_stedc_gemm(int strip, const merge_dev *
         for (int b = 0; b < 2; b++)
 #pragma unroll
             for (int r = 0; r < 4; r++) {
-                const int i = i0 + 16 * a + lr, c = strip * SS + cb + 16 * b + q + 4 * r;
+                const int i = i0 + mma_f64_col(a, lane), c = strip * SS + cb + mma_f64_row(b, r, lane);
                 if (i < r1 && c < mg.kk) Znew[(int64_t)(mg.lo + c) * ldz + i] = acc[a][b][r];
             }
 }

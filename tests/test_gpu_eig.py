@@ -158,6 +158,16 @@ def test_two_runs_agree_bit_for_bit(n, m):
         assert np.array_equal(a[key], b[key]), key
 
 
+@pytest.mark.parametrize("tridiagonal", ["host", "device"])
+@pytest.mark.parametrize("n", [130, 70])
+def test_eigh_is_bit_for_bit_the_recorded_pair(n, tridiagonal):
+    """The measures above bound the error and would not notice a reordered fp64 accumulation in the matrix-core kernels; this does. The pair was
+    recorded from an earlier build of this library (tests/golden/eigh_device.txt names the commit and the shapes' reasons)."""
+    rec = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "eigh_device_n%d.npz" % n))
+    w, K = H.eigh(E.grm_case(n, 200, LAMBDA), tridiagonal=tridiagonal)
+    assert np.array_equal(w, rec["w_" + tridiagonal]) and np.array_equal(K, rec["K_" + tridiagonal])
+
+
 def test_refusals():
     G = E.grm_case(40, 90, LAMBDA)
     bad = G.copy()

@@ -669,3 +669,42 @@ def test_every_matvec_plan_equals_the_recorded_launch_and_names_a_built_kernel(t
     assert plan("dotq", "768", 50176, 3584, True) == ("k_dotq", 392, 28, 56, 784, 1036)
     assert plan("dotq2m", "1 0 4 0", 768, 512, False) == ("k_dotq2m<4,1,1>", 3, 3, 8, 8, 8)      # (768 is no multiple of 512: G falls back to 1)
     assert plan("dotq2m", "1 0 4 0", 400384, 3584, True)[:5] == ("k_dotq2m<4,0,1>", 782, 196, 56, 224)  # (196 stages of 512: the int32 floor)
+
+
+_TRI_TILE_PROGRAM = r"""
+#include "hb_mma.hpp"
+#include <cstdio>
+static long long seen = 0, wrong = 0;
+static void check(long long x)
+{
+    int bi = -1, bj = -1;
+    tri_tile(x, &bi, &bj);
+    seen++;
+    if (!(0 <= bj && bj <= bi && (long long)bi * (bi + 1) / 2 + bj == x) && wrong++ < 20) printf("wrong %lld -> (%d, %d)\n", x, bi, bj);
+}
+int main()
+{
+    for (int T : {1, 2, 3, 157})
+        for (long long x = 0; x < (long long)T * (T + 1) / 2; x++) check(x);
+    for (long long c : {46340LL, 2000000LL})
+        for (long long bi = c - 64; bi <= c + 64; bi++)
+            for (long long d = -2; d <= 2; d++) check(bi * (bi + 1) / 2 + d);
+    printf("checked %lld wrong %lld\n", seen, wrong);
+}
+"""
+
+
+def test_tri_tile_decodes_every_block_index_of_a_lower_triangle(tmp_path):
+    """tri_tile (hibayes_amd/csrc/hb_mma.hpp, __host__ __device__: the host half of the very text k_grm_tile, k_eig_trail and k_eig_gram run, compiled
+    here by hipcc for the host alone) turns a linear block index into the tile (bi, bj), bj <= bi, of a lower triangle. Every index of the
+    triangles of 1, 2, 3 and 157 tiles a side, and the two indices either side of every boundary bi (bi + 1) / 2 for the 129 bi around 46 340 —
+    where bi (bi + 1) passes 2^31 — and around 2 000 000, where the fp64 square root that seeds the search can be one off: 0 <= bj <= bi and
+    bi (bi + 1) / 2 + bj == index."""
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    src, exe = tmp_path / "tri_tile.cpp", tmp_path / "tri_tile"
+    src.write_text(_TRI_TILE_PROGRAM)
+    subprocess.check_call([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-x", "hip", "--cuda-host-only", "-std=c++17", "-Wall", "-Werror", "-I",
+                           os.path.join(root, "hibayes_amd", "csrc"), str(src), "-o", str(exe)])
+    out = subprocess.check_output([str(exe)]).decode().splitlines()
+    assert out == ["checked %d wrong 0" % (1 + 3 + 6 + 157 * 158 // 2 + 2 * 129 * 5)], "\n".join(out)

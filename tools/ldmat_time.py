@@ -3,7 +3,7 @@
 Genotypes are generated on the device (hb_ctx_generate_genotype). dense = the genome-wide matrix, sparse = chisq 5; each line
 splits the build into BigStat / strips (cross-products and epilogue, k_ld_strip) / compaction / device-to-host copies and gives
 k_ld_strip's int8 MAC/s (m * m * ld per build: the padded rows are multiplied too); gram = hb_ctx_build_gram's band of the same
-context, the MAC/s of k_gram_tiled — the same tile loop without the fp64 epilogue and the strip writes."""
+context, the MAC/s of k_gram_tiled — the same tile loop (hb_mma.hpp's mma_i8_staged) without the fp64 epilogue and the strip writes."""
 import json
 import os
 import sys
