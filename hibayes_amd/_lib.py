@@ -248,6 +248,8 @@ SYMBOLS = [
     "hb_eig_upload", "hb_eig_reduce", "hb_eig_tau", "hb_eig_vectors", "hb_eig_download", "hb_eig_release", "hb_eig_destroy",
     # its middle stage on the device: dstedc (hb_stedc.hip), and the back-transformation of a Z that lies there
     "hb_eig_tridiagonal", "hb_eig_vectors_dev", "hb_stedc_plan", "hb_stedc_stats",
+    # real-valued genotypes (imputed dosages): the fp64 resident layout, hb_real.hip
+    "hb_ctx_upload_genotype_real", "hb_ctx_download_genotype_real", "hb_ctx_download_gram_real",
 ]
 
 
@@ -301,6 +303,9 @@ def lib():
     vp, i32, i64, dbl = C.c_void_p, C.c_int32, C.c_int64, C.c_double
     L.hb_ctx_upload_genotype_i8.argtypes = [vp, vp, i64, i32, i32]
     L.hb_ctx_upload_genotype_f64.argtypes = [vp, vp, i64, i32, i32]
+    L.hb_ctx_upload_genotype_real.argtypes = [vp, vp, i64]
+    L.hb_ctx_download_genotype_real.argtypes = [vp, vp, i64]
+    L.hb_ctx_download_gram_real.argtypes = [vp, i32, vp]
     L.hb_ctx_upload_bed.argtypes = [vp, vp, i64, i32, vp, i32, i32]
     L.hb_ctx_generate_genotype.argtypes = [vp, C.c_uint64, i32]
     L.hb_ctx_download_genotype.argtypes = [vp, vp, i64, i32, i32]

@@ -32,8 +32,9 @@ def Bayes(y, X, model, Pi, Kival=None, Ki=None, C_=None, R=None, fold=None, nite
           shard_rows=False, n_global=None, row_offset=0, warm=None):
     """Individual-level Gibbs sampler on one MI355X (or one marker shard of it when `comm` is given).
 
-    X is n x m: int8 (fast path, no double blow-up) or any integer-valued float array in the
-    reference's layout. Returns a dict with the fields of the reference's Rcpp::List.
+    X is n x m: int8 (fast path, no double blow-up) or any float array in the reference's layout: integer-valued within int8's
+    range it takes the int8 route, anything else — imputed dosages — is kept as fp64 columns (genotype_bits = 64 below), never
+    rounded. Returns a dict with the fields of the reference's Rcpp::List.
     `precise` selects the arithmetic of the panel mat-vec x_j . yadj (everything else is fp64 in every mode):
     2 (default) exact fixed point — the fp64 residual as 7 int8 digit planes, int8 x int8 -> int32 dot products, error below
     an fp64 ddot's own rounding and independent of the launch geometry; 1 fp64 FMA; 0 the fp32 image of the residual.
@@ -42,6 +43,9 @@ def Bayes(y, X, model, Pi, Kival=None, Ki=None, C_=None, R=None, fold=None, nite
     `genotype_bits`: resident layout of the sweep — 0 (default) auto: 2 bits per genotype where that is exact and the faster sweep
     (every code in 0..3, precise = 2, BayesB / BayesBpi / BayesC / BayesCpi / BayesR with up to four classes, at panel 512), int8 columns otherwise; 8 / 2 force one.
     The chain is the same bit for bit; the result's "resident_bits" reports what ran.
+    64: fp64 columns for real-valued genotypes — what auto picks for a float X that is not integer-valued; the mat-vec is then fp64 FMA
+    whatever `precise` says and the sweep runs on the per-panel kernels. A NaN or Inf in X raises (status 1); 8 / 2 with a fractional X stay
+    refused (status 4), and so are shard_rows, comm with more than one rank and BSLMM on this layout.
     `warm` (a dict mu / vare / varg / pi / lambda2 / vargL, or a _lib.WarmState) with `g_init` continues a chain from a reported
     state instead of the prior defaults (hb_warm_state, include/hibayes_gpu.h).
     `Kival` / `Ki` (model "BSLMM"): the n eigenvalues and n x n eigenvectors of the relationship matrix, make_grm(eigen=True). The result
@@ -163,7 +167,7 @@ def Bayes(y, X, model, Pi, Kival=None, Ki=None, C_=None, R=None, fold=None, nite
         keep.append(ws)
     if shard_rows:  # exact cross-check mode: this process holds rows [row_offset, row_offset + n) of every marker (include/hibayes_gpu.h)
         a.shard_rows, a.n_global, a.row_offset = 1, int(n if n_global is None else n_global), int(row_offset)
-    a.genotype_bits = int(genotype_bits)  # 0 (default): auto — 2 bits where exact and faster (codes 0..3, BayesB / C at panel 512), int8 otherwise; 8 / 2 force a layout; same chain
+    a.genotype_bits = int(genotype_bits)  # 0 (default): auto — 2 bits where exact and faster (codes 0..3, BayesB / C at panel 512), int8 otherwise, fp64 columns for a fractional X; 8 / 2 / 64 force a layout
     a.sync_blocks = int(sync_every_blocks)  # exchanges per sweep of a sharded run; the chain itself does not depend on it
     if log is not None:
         logcb = _lib.LOG_FN(lambda line, _u: log(line.decode("utf-8", "replace")))
@@ -355,6 +359,13 @@ def _map_columns(map):
     return chrom, np.array(pos, dtype=np.float64)
 
 
+def _is_int8_valued(M):
+    """True where the int8 columns hold M exactly: an integer dtype, or floats that are integers within int8's range."""
+    if M.dtype.kind in "iub":
+        return True
+    return bool(np.all(np.isfinite(M)) and np.all(M == np.rint(M)) and np.all(np.abs(M) <= 127))
+
+
 def ibrm(formula, data=None, M=None, M_id=None, method="BayesCpi", map=None, Pi=None, fold=None,
          niter=None, nburn=None, thin=5, windsize=None, windnum=None, dfvr=None, s2vr=None, vg=None,
          dfvg=None, s2vg=None, ve=None, dfve=None, s2ve=None, printfreq=100, seed=666666,
@@ -363,7 +374,8 @@ def ibrm(formula, data=None, M=None, M_id=None, method="BayesCpi", map=None, Pi=
     """Mirror of ibrm() (reference R/bayes.r:121-320). `formula` is a string such as
     "T1 ~ 1" or "T1 ~ season + bwt + (1 | loc) + (1 | dam)"; `data` a dict of columns or a
     pandas DataFrame whose first column holds the individual ids; `M` the n_all x m genotype
-    matrix (int8 preferred) with row ids `M_id`.
+    matrix (int8 preferred) with row ids `M_id`; a float M with fractional entries (imputed dosages) runs on the fp64 resident layout,
+    the fit (Bayes(), genotype_bits auto) and the GEBV products alike.
     Sharded runs (`comm` with world > 1): M holds this rank's contiguous marker range [m_offset, m_offset + M.shape[1]) of
     m_global markers (hibayes_amd.dist.shard_range); `map` / `windindx` likewise cover the local markers only, and the GEBV
     partial products of the shards are summed over the ranks.
@@ -491,11 +503,14 @@ def ibrm(formula, data=None, M=None, M_id=None, method="BayesCpi", map=None, Pi=
     if "Vr" in res:
         res["Vr_names"] = list(rand_terms)
     # GEBV, R/bayes.r:303-308: MCMCsamples$g = M %*% MCMCsamples$alpha over ALL genotyped individuals, g$gebv = its row means.
-    # On the device (hb_ctx_matmul: int8 genotypes x fp64 effects, eight records per pass over the non-zero columns).
+    # On the device (hb_ctx_matmul: int8 or fp64 genotypes x fp64 effects, eight records per pass over the non-zero columns).
     if gebv_samples is None:
         gebv_samples = bool(store_alpha)
     with Context(nall, M.shape[1], device=device, panel=panel) as cg:
-        cg.upload(M)
+        if _is_int8_valued(M):
+            cg.upload(M)
+        else:  # real-valued genotypes: the fp64 columns, M %*% alpha through the real k_xmat
+            cg.upload_real(M)
         if gebv_samples and "alpha" in res["MCMCsamples"]:
             gs = cg.matmul(res["MCMCsamples"]["alpha"])
             if comm is not None and comm.world > 1:

@@ -105,14 +105,18 @@ __device__ __forceinline__ int wave_scan_incl(int v)
 // The row cache holds the full Gram rows G[k][0..P) of the markers that are certain to move this sweep
 // (g_old != 0): both the in-wave corrections and the cross-wave ones are then LDS reads.  A marker that
 // enters the model from zero (a "surprise") falls back to reading its row from global memory.
-template <int K1>
+// GT: the element of the Gram block — int32_t (the exact integer Gram of the int8 and 2-bit layouts), or double (the fp64 columns of the
+// real layout, hb_real.hip: v.gram then points at doubles, Lb = 0, no certificate, no bound; a cached row is P * 8 bytes, so nslot is
+// chain_nslot's for that element size).
+template <int K1, typename GT = int32_t>
 __global__ __launch_bounds__(512) void k_chain(const hb_sweep_in *__restrict__ pin, chain_view v, int p, int nslot)
 {
+    constexpr int EPL = 16 / (int)sizeof(GT); // elements of a 16-byte load: the row cache is streamed 64 * EPL elements per wave and item
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int P = v.P, S = P >> 6;
     const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
-    int32_t *rowc = reinterpret_cast<int32_t *>(smem);
-    char *base = smem + (size_t)nslot * P * 4;
+    GT *rowc = reinterpret_cast<GT *>(smem);
+    char *base = smem + (size_t)nslot * P * sizeof(GT);
     double *ev_del = reinterpret_cast<double *>(base);
     int *ev_ix = reinterpret_cast<int *>(base + (size_t)P * 8);
     int *slot_of = reinterpret_cast<int *>(base + (size_t)P * 12);
@@ -121,7 +125,7 @@ __global__ __launch_bounds__(512) void k_chain(const hb_sweep_in *__restrict__ p
     int *wcnt = cnts + 16;
 
     const int j = p * P + t;
-    const int32_t *gp = v.gram + (size_t)p * (v.Lb + 1) * P * P; // l = 0: this panel's own Gram block
+    const GT *gp = reinterpret_cast<const GT *>(v.gram) + (size_t)p * (v.Lb + 1) * P * P; // l = 0: this panel's own Gram block
     HB_STAMP(0);
 
     // ---- issue every per-marker load up front (one memory latency for all of them) ----
@@ -167,13 +171,13 @@ __global__ __launch_bounds__(512) void k_chain(const hb_sweep_in *__restrict__ p
         const int ncached = min(nhot, nslot);
         if (ncached > 0) {
             const int lgP = 31 - __clz(P);
-            const int total = ncached << lgP;          // ints in the cache image
-            const int items = (total + 255) >> 8;
+            const int total = ncached << lgP;          // elements in the cache image
+            const int items = (total + 64 * EPL - 1) / (64 * EPL);
             for (int it0 = wave; it0 < items; it0 += 4 * S) {
                 int4 val0, val1, val2, val3;
                 int lin[4];
 #pragma unroll
-                for (int q = 0; q < 4; q++) lin[q] = min(((it0 + q * S) << 8) + lane * 4, total - 4);
+                for (int q = 0; q < 4; q++) lin[q] = min((it0 + q * S) * (64 * EPL) + lane * EPL, total - EPL);
                 val0 = *reinterpret_cast<const int4 *>(gp + ((size_t)ev_ix[lin[0] >> lgP] << lgP) + (lin[0] & (P - 1)));
                 val1 = *reinterpret_cast<const int4 *>(gp + ((size_t)ev_ix[lin[1] >> lgP] << lgP) + (lin[1] & (P - 1)));
                 val2 = *reinterpret_cast<const int4 *>(gp + ((size_t)ev_ix[lin[2] >> lgP] << lgP) + (lin[2] & (P - 1)));
@@ -197,11 +201,11 @@ __global__ __launch_bounds__(512) void k_chain(const hb_sweep_in *__restrict__ p
         const int bp = p - l;
         if (bp < 0) break;
         const int nevp = v.ev_count[(size_t)bp * HB_EVS];
-        const int32_t *gx = gp + (size_t)l * P * P;
+        const GT *gx = gp + (size_t)l * P * P;
         const int32_t *eix = v.ev_idx + (size_t)bp * P;
         const double *edl = v.ev_delta + (size_t)bp * P;
         for (int e0 = 0; e0 < nevp; e0 += 8) {
-            int gv[8];
+            GT gv[8];
             double dl[8];
 #pragma unroll
             for (int q8 = 0; q8 < 8; q8++) {
@@ -231,7 +235,7 @@ __global__ __launch_bounds__(512) void k_chain(const hb_sweep_in *__restrict__ p
                 // the next certain event is the next hot lane: fetch its Gram entry while deciding
                 const int knext = hleft ? (__ffsll((long long)hleft) - 1) : 0;
                 const int snext = __builtin_amdgcn_readlane(myslot, knext);
-                int gnext = 0;
+                GT gnext = 0;
                 if (hleft && snext >= 0) gnext = rowc[(size_t)snext * P + t];
                 const double q = rhs * rhs;
                 // a marker at zero moves only if it enters the model (q >= thr[0]); a hot one always moves
@@ -255,7 +259,7 @@ __global__ __launch_bounds__(512) void k_chain(const hb_sweep_in *__restrict__ p
                 const double dk = readlane_f64(delta, k);
                 const int tk = 64 * s + k;
                 if (dk != 0.0) { // (a hot marker redrawing exactly its old value would be a no-op)
-                    int gv;
+                    GT gv;
                     int slot = snext;
                     if (!(hleft && k == knext)) slot = __builtin_amdgcn_readlane(myslot, k);
                     if (hleft && k == knext && snext >= 0) {
@@ -279,7 +283,8 @@ __global__ __launch_bounds__(512) void k_chain(const hb_sweep_in *__restrict__ p
         const int ev_now = cnts[0];
         if (wave > s) { // later sub-blocks take the new events; event records first, Gram entries second
             for (int e0 = ev_prev; e0 < ev_now; e0 += 8) {
-                int rec[8], gv[8];
+                int rec[8];
+                GT gv[8];
                 double dl[8];
 #pragma unroll
                 for (int q8 = 0; q8 < 8; q8++) {

@@ -333,7 +333,7 @@ void hb_ctx_destroy(hb_ctx *c)
     if (c->s_upd) (void)hipStreamDestroy(c->s_upd);
     if (c->s_warm) (void)hipStreamDestroy(c->s_warm);
     if (c->s_dbg) (void)hipStreamDestroy(c->s_dbg);
-    void *ptrs[] = {c->X, c->X2, c->xpx, c->vx, c->s1, c->g, c->vargL, c->alpha_sum, c->alpha_sq, c->tracker, c->nzrate, c->r, c->u,
+    void *ptrs[] = {c->X, c->X2, c->Xd, c->gramd, c->xpx, c->vx, c->s1, c->g, c->vargL, c->alpha_sum, c->alpha_sq, c->tracker, c->nzrate, c->r, c->u,
                     c->r32, c->rq, c->vexp, c->gexp, c->mb, c->accq, c->gram, c->xinfo, c->thr, c->invv, c->sdz, c->partial, c->dsum, c->fcorr, c->ddense, c->fcorr2, c->dots, c->ev_count, c->ev_idx,
                     c->ev_delta, c->acc, c->d_in, c->scratch, c->dbg, c->lstamp, c->flags, c->ga, c->gB, c->gcmax, c->hot_slot, c->hot_list, c->hot_n, c->thr0f, c->opn, c->ru_ws, c->Cmat, c->zid, c->lev_buf, c->wind, c->wflag, c->wppa, c->snap, c->ldiag};
     for (void *p : ptrs)
@@ -371,6 +371,33 @@ static void invalidate(hb_ctx *c)
         c->layout = 8;
         c->graph_model = -1;
     }
+    if (c->layout == 64) { // integer genotypes over real ones: back to the int8 columns (the geometry stays where the real layout put it until its owner sets another)
+        c->layout = 8;
+        c->graph_model = -1;
+        if (c->Xd) (void)hipFree(c->Xd);
+        c->Xd = nullptr;
+    }
+}
+
+// the fp64 resident layout: the per-panel kernels at lag 0, one panel per mat-vec, no band (hb_ctx_switch_geometry keeps it there)
+static void real_geometry(hb_ctx *c)
+{
+    c->layout = 64;
+    c->graph_model = -1;
+    c->pipeline = 0, c->Lv = 0, c->D = 1;
+    hb_pipeline_geometry(c);
+    c->home_lv = 0, c->home_d = 1;
+    c->adaptive = false;
+    c->gram_ready = false;
+    c->stats_ready = false;
+    c->gcert_ok = false;
+    if (c->concurrent) c->pipeline_note = HB_REAL_NOTE;
+}
+
+static int real_alloc(hb_ctx *c)
+{
+    if (!c->Xd) HB_HIP(hipMalloc(reinterpret_cast<void **>(&c->Xd), sizeof(double) * (size_t)c->ld * c->m_pad));
+    return HB_OK;
 }
 
 static int need_int8(hb_ctx *c, const char *who)
@@ -425,7 +452,47 @@ int hb_ctx_upload_genotype_f64(hb_ctx *c, const double *X, int64_t ld, int32_t c
     if (bad)
         return hb_fail(HB_ERR_UNSUPPORTED,
                        "genotype matrix holds non-integer or out-of-range values: the int8 GPU path needs integer "
-                       "codes in [-127, 127] (imputed fractional genotypes are not supported)");
+                       "codes in [-127, 127] (imputed fractional genotypes are not supported on it: hb_ctx_upload_genotype_real "
+                       "keeps real values as fp64 columns, and genotype_bits = 0 or 64 of hb_bayes_run chooses that)");
+    return HB_OK;
+}
+
+// Real-valued genotypes (imputed dosages): every finite value is taken as it is, into the fp64 resident layout. The whole matrix at once.
+int hb_ctx_upload_genotype_real(hb_ctx *c, const double *X, int64_t ld)
+{
+    int rc = check_cols(c, 0, 0, "hb_ctx_upload_genotype_real");
+    if (rc) return rc;
+    if (!X || ld < c->n) return hb_fail(HB_ERR_INVALID, "hb_ctx_upload_genotype_real: bad source");
+    if (c->row_reduce) return hb_fail(HB_ERR_UNSUPPORTED, "shard_rows runs on the int8 layout, not on the fp64 resident layout (real-valued genotypes)");
+    HB_HIP(hipStreamSynchronize(c->stream));
+    rc = real_alloc(c);
+    if (rc) return rc;
+    HB_HIP(hipMemsetAsync(c->Xd, 0, sizeof(double) * (size_t)c->ld * c->m_pad, c->stream));
+    HB_HIP(hipMemcpy2DAsync(c->Xd, (size_t)c->ld * sizeof(double), X, (size_t)ld * sizeof(double), (size_t)c->n * sizeof(double), (size_t)c->m,
+                            hipMemcpyHostToDevice, c->stream));
+    int bad = 0;
+    rc = hbk_real_check(c, &bad);
+    {
+        std::lock_guard<std::mutex> lk(g_loaded_mu);
+        g_loaded.insert(c);
+    }
+    real_geometry(c);
+    if (rc) return rc;
+    if (bad) {
+        HB_HIP(hipMemset(c->Xd, 0, sizeof(double) * (size_t)c->ld * c->m_pad)); // (nothing non-finite stays resident)
+        return hb_fail(HB_ERR_INVALID, "NAs are not allowed in genotype.");
+    }
+    return HB_OK;
+}
+
+int hb_ctx_download_genotype_real(hb_ctx *c, double *X, int64_t ld)
+{
+    int rc = check_cols(c, 0, 0, "hb_ctx_download_genotype_real");
+    if (rc) return rc;
+    if (!X || ld < c->n) return hb_fail(HB_ERR_INVALID, "hb_ctx_download_genotype_real: bad destination");
+    if (c->layout != 64 || !c->Xd) return hb_fail(HB_ERR_INVALID, "hb_ctx_download_genotype_real: the context does not hold the fp64 resident layout");
+    HB_HIP(hipStreamSynchronize(c->stream));
+    HB_HIP(hipMemcpy2D(X, (size_t)ld * sizeof(double), c->Xd, (size_t)c->ld * sizeof(double), (size_t)c->n * sizeof(double), (size_t)c->m, hipMemcpyDeviceToHost));
     return HB_OK;
 }
 
@@ -477,6 +544,7 @@ int hb_ctx_download_genotype(hb_ctx *c, int8_t *X, int64_t ld, int32_t col0, int
 {
     int rc = check_cols(c, col0, ncols, "hb_ctx_download_genotype");
     if (rc) return rc;
+    if (c->layout == 64) return hb_fail(HB_ERR_INVALID, "hb_ctx_download_genotype: the context holds the fp64 resident layout (hb_ctx_download_genotype_real)");
     if (!c->X) { // 2-bit only: unpack a slab at a time into a scratch buffer
         const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(ncols, (int64_t)(256 << 20) / c->ld));
         int8_t *tmp = nullptr;
@@ -526,9 +594,25 @@ int hb_ctx_set_layout(hb_ctx *c, int32_t bits, int32_t keep_int8)
 {
     int rc = check_cols(c, 0, 0, "hb_ctx_set_layout");
     if (rc) return rc;
-    if (bits == 0) bits = 8;
-    if (bits != 8 && bits != 2) return hb_fail(HB_ERR_INVALID, "hb_ctx_set_layout: bits must be 8 or 2");
+    if (bits == 0) bits = c->layout == 64 ? 64 : 8;
+    if (bits != 8 && bits != 2 && bits != 64) return hb_fail(HB_ERR_INVALID, "hb_ctx_set_layout: bits must be 8, 2 or 64");
     HB_HIP(hipStreamSynchronize(c->stream));
+    if (bits == 64) { // the int8 columns converted on the device (the same numbers, as doubles)
+        if (c->layout == 64) return HB_OK;
+        if (c->row_reduce) return hb_fail(HB_ERR_UNSUPPORTED, "shard_rows runs on the int8 layout, not on the fp64 resident layout");
+        if (c->layout == 2 && !c->X) {
+            rc = hb_ctx_set_layout(c, 8, 1);
+            if (rc) return rc;
+        }
+        rc = real_alloc(c);
+        if (!rc) rc = hbk_real_from_i8(c);
+        if (rc) return rc;
+        HB_HIP(hipStreamSynchronize(c->stream));
+        real_geometry(c);
+        return HB_OK;
+    }
+    if (c->layout == 64)
+        return hb_fail(HB_ERR_UNSUPPORTED, "the context holds the fp64 resident layout (real-valued genotypes): it has no int8 or 2-bit form; upload integer genotypes instead");
     if (bits == 8) {
         if (!c->X) { // unpack the dropped int8 copy
             HB_HIP(hipMalloc(reinterpret_cast<void **>(&c->X), (size_t)c->ld * c->m_pad));
@@ -589,6 +673,7 @@ int hb_ctx_switch_geometry(hb_ctx *c, int32_t pipeline, int32_t lookahead, int32
 {
     int rc = check_cols(c, 0, 0, "hb_ctx_set_pipeline");
     if (rc) return rc;
+    if (c->layout == 64) return HB_OK; // (the fp64 resident layout keeps pipeline 0, lag 0, one panel per mat-vec: hb_ctx_pipeline_note says so)
     if (c->env_pinned && c->concurrent && !c->force_geometry) return HB_OK; // HB_PIPELINE / HB_LOOKAHEAD / HB_DOTGROUP in the environment win (tuning runs)
     c->pipeline = pipeline ? 1 : 0;
     c->Lv = lookahead;
@@ -611,6 +696,29 @@ int hb_ctx_build_gram(hb_ctx *c, double *seconds)
 {
     int rc = check_cols(c, 0, 0, "hb_ctx_build_gram");
     if (rc) return rc;
+    if (c->layout == 64) { // fp64 columns: the diagonal block of every panel, in fp64 (hb_real.hip)
+        c->Lg = 0;
+        c->graph_model = -1;
+        c->gcert_ok = false;
+        const size_t need = (size_t)c->m_pad * (size_t)c->P;
+        if (need > c->gramd_cap) {
+            if (c->gramd) { (void)hipFree(c->gramd); c->gramd = nullptr; }
+            c->gramd_cap = 0;
+            HB_HIP(hipMalloc(reinterpret_cast<void **>(&c->gramd), need * sizeof(double)));
+            c->gramd_cap = need;
+        }
+        if (!c->stats_ready) {
+            rc = hbk_stats(c);
+            if (rc) return rc;
+        }
+        const auto t0 = hb_clk::now();
+        rc = hbk_real_gram(c);
+        if (rc) return rc;
+        HB_HIP(hipStreamSynchronize(c->stream));
+        if (seconds) *seconds = hb_since(t0);
+        c->gram_ready = true;
+        return HB_OK;
+    }
     // (a context that holds only the 2-bit layout: hb_build_gram_impl unpacks a window of panels at a time into a scratch buffer)
     c->Lg = c->L; // the band this build stores
     c->graph_model = -1; // the captured sweeps hold the old band's stride (and, after a re-allocation, its pointer)
@@ -646,7 +754,21 @@ int hb_ctx_download_gram(hb_ctx *c, int32_t panel_index, int32_t *G)
     if (rc) return rc;
     if (!c->gram_ready) return hb_fail(HB_ERR_INVALID, "hb_ctx_download_gram: call hb_ctx_build_gram first");
     if (panel_index < 0 || panel_index >= c->npanels) return hb_fail(HB_ERR_INVALID, "hb_ctx_download_gram: bad panel");
+    if (c->layout == 64) return hb_fail(HB_ERR_INVALID, "hb_ctx_download_gram: the fp64 resident layout keeps its Gram blocks in fp64 (hb_ctx_download_gram_real)");
     HB_HIP(hipMemcpy(G, c->gram + (size_t)panel_index * (c->Lg + 1) * c->P * c->P, sizeof(int32_t) * c->P * c->P, hipMemcpyDeviceToHost));
+    return HB_OK;
+}
+
+// the fp64 resident layout's twin of hb_ctx_download_gram: P x P doubles
+int hb_ctx_download_gram_real(hb_ctx *c, int32_t panel_index, double *G)
+{
+    int rc = check_cols(c, 0, 0, "hb_ctx_download_gram_real");
+    if (rc) return rc;
+    if (c->layout != 64) return hb_fail(HB_ERR_INVALID, "hb_ctx_download_gram_real: the context does not hold the fp64 resident layout");
+    if (!c->gram_ready || !c->gramd) return hb_fail(HB_ERR_INVALID, "hb_ctx_download_gram_real: call hb_ctx_build_gram first");
+    if (panel_index < 0 || panel_index >= c->npanels || !G) return hb_fail(HB_ERR_INVALID, "hb_ctx_download_gram_real: bad panel");
+    HB_HIP(hipStreamSynchronize(c->stream));
+    HB_HIP(hipMemcpy(G, c->gramd + (size_t)panel_index * c->P * c->P, sizeof(double) * c->P * c->P, hipMemcpyDeviceToHost));
     return HB_OK;
 }
 
@@ -654,6 +776,7 @@ int hb_ctx_download_gram_band(hb_ctx *c, int32_t panel_index, int32_t l, int32_t
 {
     int rc = check_cols(c, 0, 0, "hb_ctx_download_gram_band");
     if (rc) return rc;
+    if (c->layout == 64) return hb_fail(HB_ERR_INVALID, "hb_ctx_download_gram_band: the fp64 resident layout stores no band (hb_ctx_download_gram_real)");
     if (!c->gram_ready) return hb_fail(HB_ERR_INVALID, "hb_ctx_download_gram_band: call hb_ctx_build_gram first");
     if (panel_index < 0 || panel_index >= c->npanels || l < 0 || l > c->Lg)
         return hb_fail(HB_ERR_INVALID, "hb_ctx_download_gram_band: bad panel or band index");
@@ -663,7 +786,7 @@ int hb_ctx_download_gram_band(hb_ctx *c, int32_t panel_index, int32_t l, int32_t
     return HB_OK;
 }
 
-const char *hb_ctx_pipeline_note(const hb_ctx *c) { return (c && !c->concurrent) ? c->pipeline_note.c_str() : nullptr; }
+const char *hb_ctx_pipeline_note(const hb_ctx *c) { return (c && (!c->concurrent || c->layout == 64)) ? c->pipeline_note.c_str() : nullptr; }
 
 int hb_ctx_get_pipeline(const hb_ctx *c, int32_t *pipeline, int32_t *lookahead, int32_t *dotgroup, int32_t *band)
 {

@@ -459,6 +459,8 @@ int hb_grm_build(hb_ctx *c, double lambda, int32_t flags, double *G_host, double
     if (!G_host && !G_dev) return hb_fail(HB_ERR_INVALID, "hb_grm_build: nowhere to put the matrix (G_host and G_dev are NULL)");
     if (!std::isfinite(lambda)) return hb_fail(HB_ERR_INVALID, "hb_grm_build: lambda must be finite");
     HB_HIP(hipSetDevice(c->device));
+    if (c->layout == 64)
+        return hb_fail(HB_ERR_UNSUPPORTED, "hb_grm_build: the context holds the fp64 resident layout (real-valued genotypes); the relationship matrix is an integer contraction");
     if (!c->X) return hb_fail(HB_ERR_INVALID, "hb_grm_build: the context holds its genotypes in the 2-bit layout only (hb_ctx_set_layout(c, 8, 1) unpacks them)");
     int rc;
     if (!c->stats_ready) {

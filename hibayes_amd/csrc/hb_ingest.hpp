@@ -118,6 +118,7 @@ __global__ __launch_bounds__(256) void k_xmat(const int8_t *__restrict__ X, int6
 
 int hbk_xmat(hb_ctx *c, const int *didx, const double *dval, int nnz, double *dout)
 {
+    if (c->layout == 64) return hbk_real_xmat(c, didx, dval, nnz, dout); // (fp64 columns: hb_real.hip)
     hipLaunchKernelGGL(k_xmat, dim3((unsigned)((c->ld / 4 + 255) / 256)), dim3(256), 0, c->stream, c->X, c->ld, c->layout == 2 ? c->X2 : nullptr, c->ld2 / 4, didx, dval, nnz, dout, c->ld);
     HB_HIP(hipGetLastError());
     return HB_OK;
@@ -179,8 +180,9 @@ int hbk_time_stream_read(hb_ctx *c, int reps, double *avg_ms, int64_t *bytes)
 {
     HB_HIP(hipSetDevice(c->device));
     const bool two = c->layout == 2 && c->X2;
-    const void *p = two ? (const void *)c->X2 : (const void *)c->X;
-    const int64_t nb = (two ? c->ld2 : c->ld) * (int64_t)c->m_pad;
+    const bool real = c->layout == 64 && c->Xd; // (fp64 columns: 8 bytes per genotype)
+    const void *p = real ? (const void *)c->Xd : two ? (const void *)c->X2 : (const void *)c->X;
+    const int64_t nb = (real ? c->ld * 8 : two ? c->ld2 : c->ld) * (int64_t)c->m_pad;
     if (!p || nb < 16) return hb_fail(HB_ERR_INVALID, "hb_ctx_time_stream_read: no resident genotypes");
     hipEvent_t e0, e1;
     HB_HIP(hipEventCreate(&e0));

@@ -123,7 +123,13 @@ struct hb_ctx {
     // 2-bit resident layout (hb_dotq2.hpp; hb_ctx_set_layout): layout == 2 makes the sweep's kernels read X2; X may then be dropped
     uint32_t *X2 = nullptr;
     int64_t ld2 = 0;     // bytes per column of X2 = 128 * ceil(ld / 512)
-    int layout = 8;      // 8: int8 columns, 2: 2-bit columns
+    int layout = 8;      // 8: int8 columns, 2: 2-bit columns, 64: fp64 columns (Xd)
+    // fp64 resident layout (hb_real.hip; hb_ctx_upload_genotype_real): real-valued genotypes — imputed dosages — as column-major doubles with X's row
+    // padding (ld rows, zero-filled; m_pad columns). layout == 64 makes the per-panel kernels read Xd and the chain read gramd; the context
+    // stays on pipeline = 0, Lv = 0, D = 1 (hb_ctx_switch_geometry)
+    double *Xd = nullptr;
+    double *gramd = nullptr; // [npanels][P][P]: the diagonal Gram blocks in fp64 (Lg = 0), diagonal = xpx
+    size_t gramd_cap = 0;    // doubles allocated
     hb_matvec_knobs mv;  // the mat-vec launches' kernel and tiling knobs (hb_matvecplan.hpp: plan_matvec reads them)
     double *xpx = nullptr, *vx = nullptr, *g = nullptr, *vargL = nullptr;
     double *s1 = nullptr; // column sums of the resident rows (k_stats), for the row-sharded mode's global statistics
@@ -267,6 +273,16 @@ int hb_poly_reset(hb_ctx *c);                         // k = 0, no records: a ru
 int hbk_poly_accumulate(hb_ctx *c);                   // k_sum += k
 int hbk_poly_backproject(hb_ctx *c, double sumvx, int count, double *k_mean, double *v);
 int hb_build_gcert(hb_ctx *c);
+// the fp64 resident layout (hb_real.hip): every launcher enqueues on st (null: the context's stream) and synchronises nothing unless it says so
+#define HB_REAL_NOTE "real-valued genotypes (the fp64 resident layout, genotype_bits = 64) run on the event-ordered per-panel kernels: lag 0, one panel per mat-vec, no band"
+int hbk_real_check(hb_ctx *c, int *bad);                                                // non-finite entries in Xd? (synchronises)
+int hbk_real_from_i8(hb_ctx *c);                                                        // Xd = (double)X
+int hbk_real_stats(hb_ctx *c);                                                          // xpx, vx (two passes), s1, xmin / xmax (synchronises)
+int hbk_real_dot(hb_ctx *c, int col0, int ncols, const double *r, hipStream_t st);      // partial[split][col0 ..) = X' r by row split
+int hbk_real_gram(hb_ctx *c);                                                           // gramd from Xd and xpx
+int hbk_real_update(hb_ctx *c, int p, double *r, float *r32, hipStream_t st);           // panel p's moves applied to r, u, r32
+int hbk_real_xalpha(hb_ctx *c, const double *dev_alpha, double *dev_out);               // (dev_out zeroed by the caller)
+int hbk_real_xmat(hb_ctx *c, const int *didx, const double *dval, int nnz, double *dout);
 
 // device buffers of one summary-level run (hb_sbayes.hip owns them; the kernels are in hb_sbayes.hpp)
 struct hb_sb_dev {

@@ -145,7 +145,8 @@ __global__ __launch_bounds__(256) void k_update(int64_t ld, upd_view q)
 // host side: launchers
 // =============================================================================================
 // LDS budget of k_chain: as many Gram rows as fit beside the event lists
-static int chain_nslot(int P) { return (int)((158 * 1024 - ((size_t)P * 16 + 128 + 128 + 64)) / ((size_t)P * 4)); }
+// (elem: bytes per Gram entry — 4, or 8 on the fp64 resident layout, whose rows are doubles)
+static int chain_nslot(int P, int elem = 4) { return (int)((158 * 1024 - ((size_t)P * 16 + 128 + 128 + 64)) / ((size_t)P * elem)); }
 #define HB_PERSIST_RING(P) ((size_t)4 * ((((size_t)12 * (P) + 1023) >> 10 << 10) + 1024)) /* HB_RD slots of the opening ring */
 // move lists (12 B per marker) + reduction / counter words + one round's candidate staging (sized by the model's K1 non-null classes)
 // + the 64 x 64 block of mutual Gram entries + the correction ring + the opening ring; the rest is the double-buffered row cache
@@ -153,7 +154,9 @@ static int chain_nslot(int P) { return (int)((158 * 1024 - ((size_t)P * 16 + 128
 static int persist_nslot(int P, int Lb, int K1) { return std::min(P, std::min(250, (int)((160 * 1024 - HB_PERSIST_FIXED(P, Lb, K1)) / ((size_t)P * 4)))); }
 // the whole 160 KiB: nothing that needs LDS (mat-vec, update) can then be co-scheduled on the chain's CU
 static size_t persist_smem(int) { return (size_t)160 * 1024; }
-static size_t chain_smem(int P) { return (size_t)chain_nslot(P) * P * 4 + (size_t)P * 16 + 128 + 128 + 64; }
+static size_t chain_smem(int P, int elem = 4) { return (size_t)chain_nslot(P, elem) * P * elem + (size_t)P * 16 + 128 + 128 + 64; }
+// the fixed-point mat-vec: precise = 2 on the integer layouts (the fp64 resident layout multiplies in fp64 whatever precise says)
+static inline bool fixed_point(const hb_ctx *c) { return c->precise == 2 && c->layout != 64; }
 
 // The launch tables: a sweep plan's template arguments (plan_sweep, hb_plan.hpp) -> the instantiation, one table per kernel family, expanded
 // from the plan's own lists. The three chain tables are also the list of the kernels that ask for the whole 160 KiB of LDS (hbk_init_attrs).
@@ -190,14 +193,19 @@ int hbk_init_attrs()
     HB_HIP(lds160(reinterpret_cast<const void *>(&k_chain<1>)));
     HB_HIP(lds160(reinterpret_cast<const void *>(&k_chain<3>)));
     HB_HIP(lds160(reinterpret_cast<const void *>(&k_chain<7>)));
+    HB_HIP(lds160(reinterpret_cast<const void *>(&k_chain<1, double>)));
+    HB_HIP(lds160(reinterpret_cast<const void *>(&k_chain<3, double>)));
+    HB_HIP(lds160(reinterpret_cast<const void *>(&k_chain<7, double>)));
     return HB_OK;
 }
 
 template <int K1>
 static hipError_t launch_chain(hb_ctx *c, const chain_view &cv, int p, hipStream_t st)
 {
-    const size_t smem = chain_smem(c->P);
-    hipLaunchKernelGGL(k_chain<K1>, dim3(1), dim3(c->P), smem, st, c->d_in, cv, p, chain_nslot(c->P));
+    if (c->layout == 64) // (cv.gram points at the fp64 Gram blocks)
+        hipLaunchKernelGGL((k_chain<K1, double>), dim3(1), dim3(c->P), chain_smem(c->P, 8), st, c->d_in, cv, p, chain_nslot(c->P, 8));
+    else
+        hipLaunchKernelGGL(k_chain<K1>, dim3(1), dim3(c->P), chain_smem(c->P), st, c->d_in, cv, p, chain_nslot(c->P));
     return hipGetLastError();
 }
 
@@ -274,6 +282,7 @@ static int launch_dotq(hb_ctx *c, const dot_launch &l, hipStream_t st)
 static int launch_dot(hb_ctx *c, const dot_launch &l)
 {
     hipStream_t st = l.st ? l.st : c->stream;
+    if (c->layout == 64) return hbk_real_dot(c, l.col0, l.ncols, c->r + (size_t)l.slot * c->ld, st); // (per-panel route only: nothing rides in the launch)
     if (c->precise == 2) return launch_dotq(c, l, st);
     upd_view uq{};
     if (l.upd) uq = *l.upd;
@@ -339,7 +348,7 @@ static int row_reduce_accq(hb_ctx *c, int col0, int ncols, hipStream_t st)
 // the reduction of the last launch's partials (there is no next launch to carry it)
 static void launch_reduce(hb_ctx *c, int col0, int ncols, hipStream_t st, int gidx = 0)
 {
-    if (c->precise == 2) {
+    if (fixed_point(c)) {
         launch_dotq_fin(c, col0, ncols, gidx, c->dsum + col0, st);
         return;
     }
@@ -404,7 +413,9 @@ static int enqueue_sweep_kernels(hb_ctx *c, int model, int n_fold, bool timed)
     const int L = c->Lv, np = c->npanels; // per-panel launches: lag Lv with one panel per mat-vec
     hipStream_t sA = c->stream, sB = timed ? c->stream : c->s_chain, sC = timed ? c->stream : c->s_upd;
     HB_HIP(hipMemsetAsync(c->acc, 0, sizeof(double) * HB_ACC_N, sA));
-    const bool fx = c->precise == 2;
+    const bool fx = fixed_point(c);
+    const bool real = c->layout == 64; // fp64 columns (hb_real.hip): k_dot_real, k_chain on the fp64 Gram block, k_update_real
+    if (real && (L != 0 || c->NB != 1 || !c->gramd)) return hb_fail(HB_ERR_INVALID, "the fp64 resident layout runs at lag 0 on its own Gram blocks (hb_ctx_build_gram)");
     if (fx) launch_quant0(c, sA);
     hipEvent_t t_all = tm.begin();
     {
@@ -420,8 +431,9 @@ static int enqueue_sweep_kernels(hb_ctx *c, int model, int n_fold, bool timed)
     }
     const double xabs = std::max(std::abs((double)c->xmin), std::abs((double)c->xmax));
     chain_view cv{c->m_pad, c->P, fx ? 1 : c->nsplit, L, c->Lg, c->xpx, c->vx, c->g, c->tracker, c->nzrate, c->alpha_sum, c->alpha_sq,
-                  c->thr, c->invv, c->sdz, c->gram, c->partial, c->dsum, c->ev_count, c->ev_idx, c->ev_delta, c->acc,
+                  c->thr, c->invv, c->sdz, real ? reinterpret_cast<const int32_t *>(c->gramd) : c->gram, c->partial, c->dsum, c->ev_count, c->ev_idx, c->ev_delta, c->acc,
                   c->wind, c->wflag, c->dbg, fx ? c->mb : nullptr, xabs};
+    if (real) cv.Lb = 0; // (one block per panel)
     const int upd_blocks = (int)((c->ld / 4 + 255) / 256);
     // software pipeline in issue order: mat-vec runs L panels ahead of chain/update in program order too,
     // so that a plain in-order replay of the captured graph is still dependency-correct
@@ -450,6 +462,9 @@ static int enqueue_sweep_kernels(hb_ctx *c, int model, int n_fold, bool timed)
             b = tm.begin();
             if (!timed) HB_HIP(hipStreamWaitEvent(sC, c->ev_chain[pc], 0));
             const int sin = ver_slot(c, pc - 1), sout = ver_slot(c, pc);
+            if (real) { // (lag 0: one residual version, updated in place)
+                if (int rc = hbk_real_update(c, pc, c->r + (size_t)sout * c->ld, c->r32 + (size_t)sout * c->ld, sC)) return rc;
+            } else
             hipLaunchKernelGGL(k_update, dim3(upd_blocks), dim3(256), 0, sC, c->ld, make_upd(c, pc, pc + 1, sin, sout, nullptr, pc));
             if (!timed) HB_HIP(hipEventRecord(c->ev_upd[pc], sC));
             tm.end(2, b);
@@ -792,6 +807,7 @@ int hbk_probe_concurrency(hb_ctx *c, int *concurrent)
 // ---- thin launch wrappers used by hb_ctx.cpp ----
 int hbk_stats(hb_ctx *c)
 {
+    if (c->layout == 64) return hbk_real_stats(c);
     int init[2] = {127, -128};
     HB_HIP(hipMemcpyAsync(c->xinfo, init, sizeof(init), hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_stats, dim3(c->m_pad), dim3(256), 0, c->stream, c->X, c->ld, c->n, c->m, c->xpx, c->vx, c->xinfo, c->s1);
@@ -807,7 +823,7 @@ int hbk_stats(hb_ctx *c)
 
 int hbk_dot_all(hb_ctx *c)
 {
-    if (c->precise == 2) {
+    if (fixed_point(c)) {
         launch_quant0(c, c->stream);
         for (int p = 0; p < c->npanels; p++) if (int rc = launch_dot(c, dot_launch{p * c->P, c->P})) return rc;
         launch_dotq_fin(c, 0, c->m_pad, 0, c->dots, c->stream);
@@ -994,6 +1010,7 @@ int hbk_delta_unpack(hb_ctx *c, const double *r0, const double *u0, const double
 int hbk_xalpha(hb_ctx *c, const double *dev_alpha, double *dev_out)
 {
     HB_HIP(hipMemsetAsync(dev_out, 0, sizeof(double) * (size_t)c->ld, c->stream));
+    if (c->layout == 64) return hbk_real_xalpha(c, dev_alpha, dev_out);
     const dim3 grid((unsigned)((c->ld / 4 + 255) / 256), (unsigned)((c->m_pad + 255) / 256));
     hipLaunchKernelGGL(k_xalpha, grid, dim3(256), 0, c->stream, c->X, c->ld, c->layout == 2 ? c->X2 : nullptr, c->ld2 / 4, c->m_pad, dev_alpha, dev_out);
     HB_HIP(hipGetLastError());
@@ -1029,7 +1046,7 @@ int hbk_time_matvec(hb_ctx *c, int D, int reps, int as_pipeline, double *avg_us,
     HB_HIP(hipEventCreate(&e1));
     const int ngroups = (c->npanels + D - 1) / D;
     HB_HIP(hipMemsetAsync(c->flags, 0, sizeof(unsigned) * HB_NFLAGS, c->stream));
-    if (c->precise == 2) launch_quant0(c, c->stream);
+    if (fixed_point(c)) launch_quant0(c, c->stream);
     // one pass over the sweep's launches, captured into a graph as the sweep itself is (the launches then follow each other
     // as closely as they do in a run), replayed once untimed and `reps` times between the two events
     HB_HIP(hipStreamSynchronize(c->stream));

@@ -536,6 +536,8 @@ int hb_ldm_build(hb_ctx *c, const int32_t *chr, int32_t has_chisq, double chisq,
 {
     if (!c || !out) return hb_fail(HB_ERR_INVALID, "hb_ldm_build: null argument");
     *out = nullptr;
+    if (c->layout == 64)
+        return hb_fail(HB_ERR_UNSUPPORTED, "hb_ldm_build: the context holds the fp64 resident layout (real-valued genotypes); the LD matrix is built from integer genotypes");
     if (!hb_ctx_has_genotypes(c) || (!c->X && !c->X2)) return hb_fail(HB_ERR_INVALID, "hb_ldm_build: no genotypes on the device");
     if (strip_bytes < 0) return hb_fail(HB_ERR_INVALID, "hb_ldm_build: strip_bytes must be >= 0");
     if (c->row_reduce) return hb_fail(HB_ERR_UNSUPPORTED, "hb_ldm_build: a row-sharded context holds a block of individuals only");

@@ -175,6 +175,7 @@ struct hb_run {
     int row_sums(double *sr, double *sr2, double *varu);
     int setup(const hb_bayes_args *args);
     // setup's parts, in the order it calls them
+    int refuse_on_real(bool real) const;
     int take_args();
     int encode_random_effects();
     int take_model_args();
@@ -283,6 +284,19 @@ int hb_run::setup(const hb_bayes_args *args)
     return HB_OK;
 }
 
+// what the fp64 resident layout (real-valued genotypes, genotype_bits = 64) does not run with: asked as soon as the layout is known — from the
+// arguments, and again once an upload under genotype_bits = 0 has chosen it
+int hb_run::refuse_on_real(bool real) const
+{
+    if (!real) return HB_OK;
+    if (rowmode) return hb_fail(HB_ERR_UNSUPPORTED, "shard_rows runs on the int8 layout, not on the fp64 resident layout (real-valued genotypes, genotype_bits = 64)");
+    if (sharded || world > 1)
+        return hb_fail(HB_ERR_UNSUPPORTED, "the fp64 resident layout (real-valued genotypes, genotype_bits = 64) is not sharded — it runs on one GPU only (comm / world > 1)");
+    if (poly || model == "BSLMM")
+        return hb_fail(HB_ERR_UNSUPPORTED, "BSLMM is not available on the fp64 resident layout (real-valued genotypes, genotype_bits = 64): the relationship matrix is an integer contraction");
+    return HB_OK;
+}
+
 // the arguments' validation and deep copies, first half
 int hb_run::take_args()
 {
@@ -331,8 +345,9 @@ int hb_run::take_args()
         if ((a.C && a.nc) || (a.R && a.nr)) return hb_fail(HB_ERR_UNSUPPORTED, "shard_rows: covariates and random effects are not part of the cross-check mode");
         if (a.genotype_bits == 2) return hb_fail(HB_ERR_UNSUPPORTED, "shard_rows runs on the int8 layout");
     }
-    if (a.genotype_bits != 0 && a.genotype_bits != 8 && a.genotype_bits != 2)
-        return hb_fail(HB_ERR_INVALID, "hb_bayes_run: genotype_bits must be 0 (auto), 8 or 2");
+    if (a.genotype_bits != 0 && a.genotype_bits != 8 && a.genotype_bits != 2 && a.genotype_bits != 64)
+        return hb_fail(HB_ERR_INVALID, "hb_bayes_run: genotype_bits must be 0 (auto), 8, 2 or 64");
+    if (int rc = refuse_on_real(a.genotype_bits == 64 || (a.ctx && a.ctx->layout == 64))) return rc;
     if (poly && (sharded || world > 1))
         return hb_fail(HB_ERR_UNSUPPORTED, "BSLMM: the polygenic block is not sharded — it runs on one GPU only (comm / world > 1)");
     if (poly && rowmode) return hb_fail(HB_ERR_UNSUPPORTED, "BSLMM: the polygenic block is not available with shard_rows");
@@ -490,8 +505,19 @@ int hb_run::configure_device()
         const hb_geometry ask = plan_default_geometry(model_index, n_fold, c->P, rowmode, wide_lv, no_adaptive_r);
         rc = hb_ctx_set_pipeline(c, ask.pipeline, ask.Lv, ask.D);
         if (rc) return rc;
-        if (a.X_i8) rc = hb_ctx_upload_genotype_i8(c, a.X_i8, a.ld_i8, 0, m);
-        else rc = hb_ctx_upload_genotype_f64(c, a.X_f64, a.ld_f64, 0, m);
+        // integer genotypes take the int8 columns; real values — imputed dosages — the fp64 columns, where genotype_bits lets them (0: wherever the
+        // matrix is not integer-valued within int8's range; 64: always, int8 input converted on the device; 8 / 2: never, the refusal stands)
+        if (a.X_i8) {
+            rc = hb_ctx_upload_genotype_i8(c, a.X_i8, a.ld_i8, 0, m);
+            if (!rc && a.genotype_bits == 64) rc = hb_ctx_set_layout(c, 64, 0);
+        } else if (a.genotype_bits == 64) rc = hb_ctx_upload_genotype_real(c, a.X_f64, a.ld_f64);
+        else {
+            rc = hb_ctx_upload_genotype_f64(c, a.X_f64, a.ld_f64, 0, m);
+            if (rc == HB_ERR_UNSUPPORTED && a.genotype_bits == 0) {
+                rc = refuse_on_real(true);
+                if (!rc) rc = hb_ctx_upload_genotype_real(c, a.X_f64, a.ld_f64);
+            }
+        }
         if (rc) return rc;
     }
     a.X_i8 = nullptr;
@@ -511,7 +537,7 @@ int hb_run::configure_device()
         return plan_layout(a.genotype_bits, own_ctx, rowmode, a.precise, model_index, n_fold, c->P, c->pipeline, c->xmin, c->xmax, no_auto_bits,
                            free_bytes, c->m_pad, c->ld, wide_lv);
     };
-    int bits_run = layout(SIZE_MAX); // a probe with all the memory there could be: the device is asked only where its answer decides
+    int bits_run = c->layout == 64 ? 64 : layout(SIZE_MAX); // (fp64 columns stay what they are) a probe with all the memory there could be: the device is asked only where its answer decides
     if (bits_run == 2 && a.genotype_bits == 0) {
         size_t fr = 0, tot = 0;
         if (hipMemGetInfo(&fr, &tot) != hipSuccess) fr = 0;

@@ -54,6 +54,20 @@ class Context:
             Xa = np.asfortranarray(X, dtype=np.float64)
             check(self.L.hb_ctx_upload_genotype_f64(self.h, Xa.ctypes.data, max(Xa.strides[1] // 8, Xa.shape[0]), col0, Xa.shape[1]))
 
+    def upload_real(self, X):
+        """Real-valued genotypes (imputed dosages), n x m: any finite value as it is, into the fp64 resident layout (genotype_bits = 64). The
+        context then sweeps on the per-panel kernels (pipeline_note() says so); a NaN or Inf raises with status 1."""
+        Xa = np.asfortranarray(X, dtype=np.float64)
+        if Xa.ndim != 2 or Xa.shape != (self.n, self.m):
+            raise ValueError("upload_real: X must be %d x %d" % (self.n, self.m))
+        check(self.L.hb_ctx_upload_genotype_real(self.h, Xa.ctypes.data, max(Xa.strides[1] // 8, Xa.shape[0])))
+
+    def download_real(self):
+        """The fp64 resident layout's columns, bit for bit what upload_real() was given."""
+        out = np.zeros((self.n, self.m), dtype=np.float64, order="F")
+        check(self.L.hb_ctx_download_genotype_real(self.h, out.ctypes.data, self.n))
+        return out
+
     def upload_bed(self, raw, nind, rows=None, col0=0, ncols=None):
         raw = np.frombuffer(raw, dtype=np.uint8)
         r = None if rows is None else np.ascontiguousarray(rows, dtype=np.int32)
@@ -76,7 +90,8 @@ class Context:
         return xpx, vx, s.value, z.value
 
     def set_layout(self, bits=2, keep_int8=True):
-        """Resident genotype layout the sweep reads: 8 (int8 columns) or 2 (2 bits per genotype, a quarter of the bytes)."""
+        """Resident genotype layout the sweep reads: 8 (int8 columns) or 2 (2 bits per genotype, a quarter of the bytes); 64 converts the
+        int8 columns to the fp64 layout of upload_real()."""
         check(self.L.hb_ctx_set_layout(self.h, int(bits), 1 if keep_int8 else 0))
 
     def layout(self):
@@ -132,6 +147,13 @@ class Context:
         P = self.panel
         G = np.zeros((P, P), dtype=np.int32)
         check(self.L.hb_ctx_download_gram(self.h, p, G.ctypes.data))
+        return G
+
+    def gram_real(self, p):
+        """Panel p's Gram block on the fp64 resident layout (P x P doubles; hb_ctx_download_gram_real)."""
+        P = self.panel
+        G = np.zeros((P, P), dtype=np.float64)
+        check(self.L.hb_ctx_download_gram_real(self.h, p, G.ctypes.data))
         return G
 
     def ldmat(self, chr=None, chisq=None, strip_bytes=0):

@@ -35,7 +35,9 @@ typedef enum {
     HB_ERR_INVALID = 1,     /* argument validation (reference exception text in hb_last_error) */
     HB_ERR_NO_DEVICE = 2,   /* no usable HIP device / runtime */
     HB_ERR_HIP = 3,         /* a HIP call or kernel failed */
-    HB_ERR_UNSUPPORTED = 4, /* argument outside the GPU path (BSLMM without Kival / Ki, or sharded / warm; epsilon block; non-integer X) */
+    HB_ERR_UNSUPPORTED = 4, /* argument outside the GPU path (BSLMM without Kival / Ki, or sharded / warm; epsilon block; non-integer X on the integer
+                             * layouts — genotype_bits 8 or 2, hb_ctx_upload_genotype_f64; shard_rows, marker shards, BSLMM, hb_ldm_build and
+                             * hb_grm_build on the fp64 resident layout) */
     HB_ERR_COMM = 5,        /* the multi-GPU all-reduce callback failed */
     HB_ERR_INTERRUPT = 6,   /* interrupt callback asked to stop */
     HB_ERR_ABORTED = 7      /* a wait inside the device pipeline timed out and the sweep was abandoned (hb_ctx_sweep_end); the
@@ -178,7 +180,13 @@ typedef struct hb_bayes_args {
      * BayesB / BayesBpi / BayesC / BayesCpi (450 against 213 sweeps/s at n = 50k, m = 500k) and BayesR with up to four classes (103 against 98
      * converged, 64.5 against 58 cold) at panel 512, the band and the packed copy fitting the device — int8 columns otherwise (the models in which
      * every marker moves, other genotype codes, small problems). hb_bayes_out.resident_bits / hb_run_info.resident_bits
-     * report the choice. HB_NO_AUTO_BITS=1 in the environment keeps int8. */
+     * report the choice. HB_NO_AUTO_BITS=1 in the environment keeps int8.
+     * 64 = fp64 columns, for real-valued genotypes (imputed dosages; the reference's Bayes() takes any arma::mat): any finite value, a NaN or Inf is
+     * HB_ERR_INVALID with "NAs are not allowed in genotype."; X_i8 is converted on the device. The mat-vec is the fp64 FMA one whatever `precise`
+     * says, the sweep runs on the event-ordered per-panel kernels (pipeline 0, lag 0, one panel per mat-vec, the diagonal Gram blocks in fp64;
+     * hb_ctx_pipeline_note says so), resident_bits reports 64. Under 0 (auto) an X_f64 that is integer-valued within int8's range takes the route above
+     * unchanged; any other takes 64 (it used to be refused). 8 / 2 with such a matrix stay refused (HB_ERR_UNSUPPORTED): never rounded silently.
+     * Not on this layout (HB_ERR_UNSUPPORTED): shard_rows, marker shards (comm / world > 1), BSLMM. */
     int32_t genotype_bits;
     /* Exact multi-GPU cross-check mode (ABI 4; SURVEY §8e "alternative rejected ... keep only as a correctness cross-check mode"):
      * shard the INDIVIDUALS instead of the markers. This process holds rows [row_offset, row_offset + n) of all m markers and of y
@@ -233,7 +241,7 @@ typedef struct hb_bayes_out {
     int32_t iters_done;
     double mean_events;      /* mean number of markers whose effect changed per sweep     */
     int32_t sweeps_replayed; /* (ABI 5) sweeps that timed out on the device and were replayed from the saved state */
-    int32_t resident_bits;   /* (was reserved_) the genotype layout the sweep read: 8 or 2 — what genotype_bits = 0 ("auto") chose */
+    int32_t resident_bits;   /* (was reserved_) the genotype layout the sweep read: 8, 2 or 64 — what genotype_bits = 0 ("auto") chose */
     /* (ABI 6) the chain's state after its LAST iteration — what hb_bayes_args.g_init / .warm of a following run take to continue it:
      * the scalars in `last` (last.vargL is set to vargL_last), the effects in g_last (m, caller-allocated or NULL) and, for BayesL,
      * the per-marker variances in vargL_last (m, caller-allocated or NULL). */
@@ -273,7 +281,7 @@ typedef struct hb_run_info {
     double mean_redo;        /* mean rolled-back chain rounds per sweep so far */
     double loop_seconds, setup_seconds, gram_seconds;
     int32_t sweeps_replayed; /* (ABI 5) sweeps whose device pipeline timed out and that were replayed from the saved state (HB_ERR_ABORTED) */
-    int32_t resident_bits;   /* (was reserved_) the genotype layout the sweep read: 8 or 2 — what genotype_bits = 0 ("auto") chose */
+    int32_t resident_bits;   /* (was reserved_) the genotype layout the sweep read: 8, 2 or 64 — what genotype_bits = 0 ("auto") chose */
     double lambda2;          /* (ABI 6) BayesL's lambda^2 after the last iteration (hb_warm_state.lambda2) */
 } hb_run_info;
 int hb_run_create(const hb_bayes_args *args, hb_run **out);
@@ -548,7 +556,17 @@ int hb_ctx_upload_bed(hb_ctx *c, const uint8_t *bed, int64_t nbytes, int32_t nin
  * x ~ Binomial(2,p_j), every mono_every-th column forced monomorphic (0 = never) */
 int hb_ctx_generate_genotype(hb_ctx *c, uint64_t seed, int32_t mono_every);
 int hb_ctx_download_genotype(hb_ctx *c, int8_t *X, int64_t ld, int32_t col0, int32_t ncols);
-/* Resident layout the sweep's kernels read: bits = 8 (int8 columns) or 2 (2 bits per genotype: 16 individuals per 32-bit word,
+/* Real-valued genotypes (imputed dosages) -> the fp64 resident layout: column-major doubles with the row padding of the int8 columns. All m
+ * columns at once, any finite value as it is; a NaN or Inf is HB_ERR_INVALID, "NAs are not allowed in genotype.". The context then stays on the
+ * event-ordered per-panel kernels (hb_ctx_set_pipeline(1, ...) keeps pipeline 0, hb_ctx_pipeline_note tells why), hb_ctx_get_layout reports
+ * 64, hb_ctx_build_gram builds the diagonal Gram block of each panel in fp64 (hb_ctx_download_gram_real), hb_ctx_dot / hb_ctx_matvec /
+ * hb_ctx_matmul / hb_ctx_marker_stats / the sweeps read the doubles. hb_ldm_build, hb_grm_build and hb_ctx_set_layout(2 or 8) refuse such a
+ * context (HB_ERR_UNSUPPORTED); an integer upload (hb_ctx_upload_genotype_i8 / _f64 / _bed) puts it back on the int8 columns.
+ * hb_ctx_download_genotype_real gives the values back bit for bit. */
+int hb_ctx_upload_genotype_real(hb_ctx *c, const double *X, int64_t ld);
+int hb_ctx_download_genotype_real(hb_ctx *c, double *X, int64_t ld);
+/* (bits = 64: the int8 columns converted to the fp64 resident layout on the device — see hb_ctx_upload_genotype_real.)
+ * Resident layout the sweep's kernels read: bits = 8 (int8 columns) or 2 (2 bits per genotype: 16 individuals per 32-bit word,
  * expanded in registers — hb_dotq2.hpp; codes must be 0..3). Packing happens on the device from the int8 columns. keep_int8 = 0
  * frees the int8 copy afterwards (every kernel of the run — mat-vec, residual update, X*alpha, the GEBV sample matrix, genotype
  * download — then reads the packed form; the Gram blocks must have been built for the widest geometry the run will use, a
@@ -564,7 +582,8 @@ int hb_ctx_get_layout(const hb_ctx *c, int32_t *bits, int32_t *int8_resident);
  * individuals across the lanes. Also HB_DOTQ2_KIND. The int8-column layout (the library's default layout) always runs k_dotq: v_dot4, no MFMA. */
 int hb_ctx_set_matvec_kernel(hb_ctx *c, int32_t kind);
 
-/* xpx_i = sum x^2, vx_i = var(x_i) (N-1), reference src/Bayes.cpp:310-317; integer-exact */
+/* xpx_i = sum x^2, vx_i = var(x_i) (N-1), reference src/Bayes.cpp:310-317; integer-exact (the fp64 resident layout: two passes, arma::var's
+ * form; a column of one repeated value has vx == 0 exactly) */
 int hb_ctx_marker_stats(hb_ctx *c, double *xpx, double *vx, double *sumvx, int32_t *nvar0);
 /* Pipeline geometry of the sweep: pipeline 0 = one kernel per step and panel, 1 = persistent
  * chain workgroup overlapped with the mat-vec stream; `lookahead` mat-vec groups of `dotgroup` panels each run
@@ -578,12 +597,16 @@ int hb_ctx_set_pipeline(hb_ctx *c, int32_t pipeline, int32_t lookahead, int32_t 
 int hb_ctx_build_gram(hb_ctx *c, double *seconds);
 /* rows x cols window of panel p's Gram (row-major int32, P x P) for exactness tests */
 int hb_ctx_download_gram(hb_ctx *c, int32_t panel_index, int32_t *G);
+/* its twin on the fp64 resident layout: panel p's Gram block as row-major doubles, P x P — symmetric bit for bit, its diagonal the xpx of
+ * hb_ctx_marker_stats bit for bit */
+int hb_ctx_download_gram_real(hb_ctx *c, int32_t panel_index, double *G);
 /* band block l of panel p (row-major int32, P x P): G[k][t] = x_{(p-l)P+k} . x_{pP+t}, l = 0..band; the look-ahead
  * pipeline folds the moves of panel p-l into panel p's right-hand sides with it */
 int hb_ctx_download_gram_band(hb_ctx *c, int32_t panel_index, int32_t l, int32_t *G);
 /* NULL when the persistent pipeline is available; otherwise the reason the context fell back to the event-ordered
  * per-panel kernels (kernels on two streams are not co-resident here: AMD_SERIALIZE_KERNEL, HIP_LAUNCH_BLOCKING, a
- * counter-collecting profiler ...). Probed once at hb_ctx_create(); hb_ctx_set_pipeline(1, ...) then keeps pipeline 0. */
+ * counter-collecting profiler ...). Probed once at hb_ctx_create(); hb_ctx_set_pipeline(1, ...) then keeps pipeline 0.
+ * A context on the fp64 resident layout (hb_ctx_upload_genotype_real) also has a note: that layout runs on the per-panel kernels only. */
 const char *hb_ctx_pipeline_note(const hb_ctx *c);
 /* Geometry by regime. The band Gram blocks are stored once, for the widest band built so far; hb_ctx_set_pipeline() to any
  * geometry whose band fits reuses them (and the sweeps captured for each geometry are cached). With adaptive != 0,
