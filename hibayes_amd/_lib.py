@@ -119,6 +119,24 @@ class PolyOut(C.Structure):
     ]
 
 
+class EpslGi(C.Structure):
+    """hb_epsl_gi: the q x q matrix of the epsilon term in canonical CSC, and ne"""
+    _fields_ = [("q", C.c_int32), ("ne", C.c_int32), ("indptr", C.c_void_p), ("indices", C.c_void_p), ("data", C.c_void_p)]
+
+
+class EpslDesc(C.Structure):
+    """hb_epsl_desc: what hb_ctx_epsl_setup takes"""
+    _fields_ = [("Gi", C.POINTER(EpslGi)), ("index", C.c_void_p), ("y_J", C.c_void_p)]
+
+
+class EpslOut(C.Structure):
+    """hb_epsl_out: what the single-step model's epsilon block adds to the result"""
+    _fields_ = [
+        ("Veps", C.c_double), ("Veps_sd", C.c_double), ("J", C.c_double), ("J_sd", C.c_double),
+        ("s_Veps", C.c_void_p), ("s_J", C.c_void_p), ("epsilon", C.c_void_p), ("s_epsilon", C.c_void_p),
+    ]
+
+
 class SBayesArgs(C.Structure):
     _fields_ = [
         ("m", C.c_int32), ("sumstat", C.c_void_p), ("ld_sumstat", C.c_int64), ("ldm", C.c_void_p), ("ld_ldm", C.c_int64),
@@ -250,6 +268,9 @@ SYMBOLS = [
     "hb_eig_tridiagonal", "hb_eig_vectors_dev", "hb_stedc_plan", "hb_stedc_stats",
     # real-valued genotypes (imputed dosages): the fp64 resident layout, hb_real.hip
     "hb_ctx_upload_genotype_real", "hb_ctx_download_genotype_real", "hb_ctx_download_gram_real",
+    # ssbrm(): the epsilon block src/Bayes.cpp:554-584, Gibbs() src/solver.cpp:131-140 (hb_epsl.hip)
+    "hb_ctx_epsl_setup", "hb_ctx_epsl_step", "hb_ctx_epsl_state", "hb_ctx_epsl_debug_get", "hb_ctx_epsl_debug_set",
+    "hb_epsl_check", "hb_epsl_plan", "hb_bayes_run_epsl", "hb_run_epsl", "hb_run_epsl_store",
 ]
 
 
@@ -378,6 +399,16 @@ def lib():
     L.hb_ctx_poly_state.argtypes = [vp, vp, C.POINTER(dbl), C.POINTER(dbl), C.POINTER(i32)]
     L.hb_ctx_poly_debug_get.argtypes = [vp, vp, vp, vp, vp]
     L.hb_run_destroy.restype = None
+    L.hb_ctx_epsl_setup.argtypes = [vp, C.POINTER(EpslDesc)]
+    L.hb_ctx_epsl_step.argtypes = [vp, dbl, dbl, C.c_uint64, i64, dbl, dbl, dbl]
+    L.hb_ctx_epsl_state.argtypes = [vp, vp, C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl)]
+    L.hb_ctx_epsl_debug_get.argtypes = [vp, vp, vp, vp, vp]
+    L.hb_ctx_epsl_debug_set.argtypes = [vp, i32, i32]
+    L.hb_epsl_check.argtypes = [C.POINTER(EpslGi), vp, i32]
+    L.hb_epsl_plan.argtypes = [i32, vp, vp, i32, i32, vp, vp, vp, vp, vp]
+    L.hb_bayes_run_epsl.argtypes = [C.POINTER(BayesArgs), C.POINTER(BayesOut), C.POINTER(PolyOut), C.POINTER(EpslOut)]
+    L.hb_run_epsl.argtypes = [vp, C.POINTER(EpslOut)]
+    L.hb_run_epsl_store.argtypes = [vp, i32]
     L.hb_eig_upload.argtypes = [vp, i64, i32, i32, C.POINTER(vp), C.POINTER(i64)]
     L.hb_eig_reduce.argtypes = [vp, i64, i32, i32, vp, vp, C.POINTER(vp)]
     L.hb_eig_tau.argtypes = [vp, vp]

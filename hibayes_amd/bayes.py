@@ -15,7 +15,7 @@ import re
 import numpy as np
 
 from . import _lib
-from ._lib import BayesArgs, BayesOut, HibayesError, PolyOut, check, lib
+from ._lib import BayesArgs, BayesOut, EpslOut, HibayesError, PolyOut, check, lib
 
 METHODS = ("BayesCpi", "BayesA", "BayesL", "BSLMM", "BayesR", "BayesB", "BayesC", "BayesBpi", "BayesRR")
 
@@ -29,7 +29,7 @@ def Bayes(y, X, model, Pi, Kival=None, Ki=None, C_=None, R=None, fold=None, nite
           dfvg=None, s2vg=None, ve=None, dfve=None, s2ve=None, windindx=None, outfreq=100, threads=0,
           verbose=True, *, seed=666666, device=0, panel=0, precise=2, store_alpha=True,
           comm=None, m_global=None, m_offset=0, log=None, C=None, g_init=None, ctx=None, sync_every_blocks=1, genotype_bits=0,
-          shard_rows=False, n_global=None, row_offset=0, warm=None):
+          shard_rows=False, n_global=None, row_offset=0, warm=None, store_epsilon=True):
     """Individual-level Gibbs sampler on one MI355X (or one marker shard of it when `comm` is given).
 
     X is n x m: int8 (fast path, no double blow-up) or any float array in the reference's layout: integer-valued within int8's
@@ -51,6 +51,11 @@ def Bayes(y, X, model, Pi, Kival=None, Ki=None, C_=None, R=None, fold=None, nite
     `Kival` / `Ki` (model "BSLMM"): the n eigenvalues and n x n eigenvectors of the relationship matrix, make_grm(eigen=True). The result
     then also holds Va, Vb, MCMCsamples["Va"] / ["Vb"], k (the mean polygenic vector) and ghat (its back-projection onto the markers,
     already part of alpha) — extensions: the reference only prints Va and Vb.
+    `epsl_y_J` / `epsl_Gi` / `epsl_index` (all three or none): the epsilon block of the single-step model, src/Bayes.cpp:554-584 — the J
+    covariate (n), the q x q matrix of the non-genotyped individuals (a scipy sparse matrix, or an (indptr, indices, data) CSC triple of
+    the full symmetric matrix) and the 1-based column of each of the LAST len(epsl_index) records. The result then also holds Veps, J,
+    epsilon (q) and their MCMCsamples; `store_epsilon=False` keeps the mean of epsilon without the q x R matrix. Any model but BSLMM, any
+    resident layout of a single-GPU run; refused (status 4) with comm of more than one rank, shard_rows or a warm start.
     """
     if C is not None and C_ is None:
         C_ = C
@@ -119,10 +124,21 @@ def Bayes(y, X, model, Pi, Kival=None, Ki=None, C_=None, R=None, fold=None, nite
         fold = _f64(fold).ravel()
         a.fold, a.n_fold = fold.ctypes.data, fold.size
     a.niter, a.nburn, a.thin = int(niter), int(nburn), int(thin)
-    if epsl_y_J is not None or epsl_Gi is not None or epsl_index is not None:
-        dummy = np.zeros(1)
-        keep.append(dummy)
-        a.epsl_index = dummy.ctypes.data  # refused by the library with HB_ERR_UNSUPPORTED
+    has_epsl = epsl_y_J is not None or epsl_Gi is not None or epsl_index is not None
+    qe = 0
+    if has_epsl:
+        if epsl_Gi is None:
+            raise HibayesError(1, "variance-covariance matrix should be provided for epsilon term.")
+        if epsl_y_J is None or epsl_index is None:
+            raise HibayesError(1, "epsl_y_J, epsl_Gi and epsl_index go together")
+        from .ssbayes import epsl_descriptor
+        gi, eidx, ekeep = epsl_descriptor(epsl_Gi, epsl_index)
+        yj = _f64(epsl_y_J).ravel()
+        if yj.size != n:
+            raise HibayesError(1, "Number of individuals not equals.")
+        a.epsl_y_J, a.epsl_Gi, a.epsl_index = yj.ctypes.data, ct.addressof(gi), eidx.ctypes.data
+        qe = gi.q
+        keep += [gi, eidx, ekeep, yj]
     for name, val in (("dfvr", dfvr), ("s2vr", s2vr), ("vg", vg), ("dfvg", dfvg), ("s2vg", s2vg),
                       ("ve", ve), ("dfve", dfve), ("s2ve", s2ve)):
         if val is not None:
@@ -203,7 +219,13 @@ def Bayes(y, X, model, Pi, Kival=None, Ki=None, C_=None, R=None, fold=None, nite
     if model == "BayesL":
         o.vargL_last = buf("vargL_last", m)
 
-    if has_poly:
+    if has_epsl:
+        eo = EpslOut()
+        eo.s_Veps, eo.s_J, eo.epsilon = buf("s_Veps", nrec), buf("s_J", nrec), buf("epsilon", qe)
+        if store_epsilon:
+            eo.s_epsilon = buf("s_epsilon", (qe, nrec))
+        check(L.hb_bayes_run_epsl(ct.byref(a), ct.byref(o), None, ct.byref(eo)))
+    elif has_poly:
         po = PolyOut()
         po.s_Va, po.s_Vb, po.k_mean, po.ghat = buf("s_Va", nrec), buf("s_Vb", nrec), buf("k_mean", n), buf("ghat", m)
         check(L.hb_bayes_run_poly(ct.byref(a), ct.byref(o), ct.byref(po)))
@@ -220,7 +242,13 @@ def Bayes(y, X, model, Pi, Kival=None, Ki=None, C_=None, R=None, fold=None, nite
                                     bufs["s_h2"].reshape(1, -1))
     res["mu"] = o.mu
     mc["mu"] = bufs["s_mu"].reshape(1, -1)
-    if has_poly:
+    if has_epsl:  # src/Bayes.cpp:995-1000
+        res["Veps"], res["J"], res["epsilon"] = eo.Veps, eo.J, bufs["epsilon"]
+        res["Veps_sd"], res["J_sd"] = eo.Veps_sd, eo.J_sd
+        mc["Veps"], mc["J"] = bufs["s_Veps"].reshape(1, -1), bufs["s_J"].reshape(1, -1)
+        if store_epsilon:
+            mc["epsilon"] = bufs["s_epsilon"]
+    if has_poly and not has_epsl:
         res["Va"], res["Vb"], res["Va_sd"], res["Vb_sd"] = po.Va, po.Vb, po.Va_sd, po.Vb_sd
         mc["Va"], mc["Vb"] = bufs["s_Va"].reshape(1, -1), bufs["s_Vb"].reshape(1, -1)
         res["k"], res["ghat"] = bufs["k_mean"], bufs["ghat"]

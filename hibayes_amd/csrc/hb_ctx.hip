@@ -340,6 +340,7 @@ void hb_ctx_destroy(hb_ctx *c)
         if (p) (void)hipFree(p);
     blocks_free(c);
     hb_poly_free(c);
+    hb_epsl_free(c);
     if (c->h_acc) (void)hipHostFree(c->h_acc);
     if (c->h_in) (void)hipHostFree(c->h_in);
     if (c->h_flags) (void)hipHostFree(c->h_flags);
@@ -984,6 +985,10 @@ static int fetch_acc(hb_ctx *c)
     if (c->poly) { // (the polygenic block's vb, q and flag come back the same way)
         const int prc = hb_poly_fetch_enqueue(c);
         if (prc) return prc;
+    }
+    if (c->epsl) { // (and the epsilon block's veps, q and J)
+        const int erc = hb_epsl_fetch_enqueue(c);
+        if (erc) return erc;
     }
     HB_HIP(hipStreamSynchronize(c->stream));
     c->aborted = false;

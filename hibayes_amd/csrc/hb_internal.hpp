@@ -229,6 +229,7 @@ struct hb_ctx {
     std::vector<hipEvent_t> ev_pool;
 
     struct hb_poly *poly = nullptr; // BSLMM's polygenic block (hb_ctx_poly_setup; hb_grm.hip owns it)
+    struct hb_epsl *epsl = nullptr; // the single-step model's epsilon block (hb_ctx_epsl_setup; hb_epsl.hip owns it)
 
     // ---- an aborted sweep is replayed ----
     // Every wait of the persistent pipeline is bounded; a waiter that gives up raises the abort flag, all kernels of the sweep
@@ -272,6 +273,15 @@ const double *hb_poly_host_state(const hb_ctx *c);    // that mirror: [0] vb, [1
 int hb_poly_reset(hb_ctx *c);                         // k = 0, no records: a run starts (:228-230)
 int hbk_poly_accumulate(hb_ctx *c);                   // k_sum += k
 int hbk_poly_backproject(hb_ctx *c, double sumvx, int count, double *k_mean, double *v);
+// the epsilon block (hb_epsl.hip)
+void hb_epsl_free(hb_ctx *c);
+int hb_epsl_fetch_enqueue(hb_ctx *c);                 // veps, q, J -> the pinned mirror, on the context's stream (rides on fetch_acc)
+const double *hb_epsl_host_state(const hb_ctx *c);    // that mirror: [0] veps, [1] q = x'Gx, [2] J; NULL without a block
+int hb_epsl_q(const hb_ctx *c);
+int hb_epsl_ne(const hb_ctx *c);
+int hb_epsl_reset(hb_ctx *c);                         // epsilon = 0, J = 0, no records: a run starts
+int hbk_epsl_accumulate(hb_ctx *c, double *record);   // the running sum += epsilon; record (host, q; may be NULL) = epsilon
+int hbk_epsl_sum(hb_ctx *c, double *xsum, int32_t *idx);
 int hb_build_gcert(hb_ctx *c);
 // the fp64 resident layout (hb_real.hip): every launcher enqueues on st (null: the context's stream) and synchronises nothing unless it says so
 #define HB_REAL_NOTE "real-valued genotypes (the fp64 resident layout, genotype_bits = 64) run on the event-ordered per-panel kernels: lag 0, one panel per mat-vec, no band"

@@ -16,6 +16,8 @@
 //         normal of redraw k = 1 .. 101 of that marker in sweep `iter` (hb_sbayes_sparse.hip)
 //     purpose 5, BSLMM's polygenic block (src/Bayes.cpp:535, randn(nk)): blk = j is the normal of eigenvector j in iteration `iter`
 //         (hb_grm.hip)
+//     purpose 6, the single-step model's epsilon block (src/Bayes.cpp:570, Gibbs() src/solver.cpp:138): blk = i is the normal of row i of the
+//         pass in iteration `iter` (hb_epsl.hip) — addressed by row, so the draw does not depend on how the pass is scheduled
 // The reference draws the same quantities from R's global Mersenne-Twister (src/stats.cpp:3-24).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -28,6 +30,7 @@
 #define HB_PURPOSE_DATA 3ull
 #define HB_PURPOSE_REDRAW 4ull
 #define HB_PURPOSE_POLY 5ull
+#define HB_PURPOSE_EPSL 6ull
 #define HB_BLK_PER_MARKER 64ull
 
 __host__ __device__ inline uint4 hb_block(uint64_t seed, uint64_t sub, uint64_t blk)

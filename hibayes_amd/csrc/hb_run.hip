@@ -5,8 +5,8 @@
 // (:479-516), the hyper-parameter draws after the marker sweep (:603, :666-669, :710-716, :738-741,
 // :803-814, :819-823), the thinned store (:848-882) and the posterior assembly (:919-1040).
 // What runs on the device: everything that touches an n- or m-long vector (hb_kernels.hip).
-// BSLMM's polygenic block (nk, :518-552) runs on the device too (hb_grm.hip) when Kival / Ki are given; the single-step epsilon
-// block (ne) is refused with HB_ERR_UNSUPPORTED.
+// BSLMM's polygenic block (nk, :518-552) runs on the device too (hb_grm.hip) when Kival / Ki are given, and so does the single-step
+// epsilon block (ne, :554-584; hb_epsl.hip) when epsl_y_J / epsl_Gi / epsl_index are.
 //
 // hb_bayes_run() == hb_run_create() + hb_run_step(niter) + hb_run_finish(); bench.py drives the
 // three separately so that exactly K iterations sit between its barriers.
@@ -99,6 +99,16 @@ struct hb_run {
     bool poly = false, poly_finished = false;
     double va = 0, vb = 0;     // :715, :550
     std::vector<double> s_Va, s_Vb, k_mean, ghat;
+    // ---- the single-step model's epsilon block (:554-584): the state lives on the context (hb_ctx_epsl_*), the records here ----
+    bool epsl = false, epsl_finished = false, store_eps = true;
+    int qe = 0, ne = 0;
+    hb_epsl_gi epsl_gi{};
+    std::vector<int64_t> eg_indptr;
+    std::vector<int32_t> eg_indices;
+    std::vector<double> eg_data, eps_yJ;
+    std::vector<uint32_t> eps_index;
+    double veps = 0, eps_J = 0;
+    std::vector<double> s_Veps, s_J, s_eps, eps_mean;
 
     ~hb_run()
     {
@@ -324,9 +334,30 @@ int hb_run::take_args()
     // BSLMM runs with both Kival and Ki, or on a context prepared by hb_ctx_poly_setup; anything else about them keeps the refusal (and its
     // text, which tests pin) from before the block existed
     poly = model == "BSLMM" && ((a.Ki && a.Kival) || (!a.Ki && !a.Kival && a.ctx && a.ctx->poly));
+    if ((a.epsl_index || a.epsl_Gi || a.epsl_y_J) && model == "BSLMM")
+        return hb_fail(HB_ERR_UNSUPPORTED, "the epsilon block is not available with BSLMM: the reference's ssbrm() has no such method");
     if (!poly && (a.Ki || a.Kival || model == "BSLMM")) return hb_fail(HB_ERR_UNSUPPORTED, "BSLMM (Ki/Kival) is not part of the GPU path");
-    if (a.epsl_index || a.epsl_Gi || a.epsl_y_J)
-        return hb_fail(HB_ERR_UNSUPPORTED, "the single-step epsilon block is not part of the GPU path");
+    // the single-step epsilon block (:254-275): all three arguments or none, validated and copied here
+    if (a.epsl_index || a.epsl_Gi || a.epsl_y_J) {
+        if (!a.epsl_Gi) return hb_fail(HB_ERR_INVALID, "variance-covariance matrix should be provided for epsilon term.");
+        if (!a.epsl_index || !a.epsl_y_J) return hb_fail(HB_ERR_INVALID, "hb_bayes_run: epsl_y_J, epsl_Gi and epsl_index go together");
+        const hb_epsl_gi *G = static_cast<const hb_epsl_gi *>(a.epsl_Gi);
+        if (int rc = hb_epsl_check(G, a.epsl_index, n)) return rc;
+        for (int i = 0; i < n; i++)
+            if (!std::isfinite(a.epsl_y_J[i])) return hb_fail(HB_ERR_INVALID, "epsl_y_J: a value is not finite");
+        epsl = true;
+        qe = G->q;
+        ne = G->ne;
+        eg_indptr.assign(G->indptr, G->indptr + qe + 1);
+        eg_indices.assign(G->indices, G->indices + G->indptr[qe]);
+        eg_data.assign(G->data, G->data + G->indptr[qe]);
+        eps_yJ.assign(a.epsl_y_J, a.epsl_y_J + n);
+        eps_index.assign(a.epsl_index, a.epsl_index + ne);
+        epsl_gi = hb_epsl_gi{qe, ne, eg_indptr.data(), eg_indices.data(), eg_data.data()};
+    }
+    a.epsl_Gi = nullptr; // consumed
+    a.epsl_index = nullptr;
+    a.epsl_y_J = nullptr;
 
     world = a.world > 1 ? a.world : 1;
     if (a.comm) {
@@ -352,6 +383,10 @@ int hb_run::take_args()
         return hb_fail(HB_ERR_UNSUPPORTED, "BSLMM: the polygenic block is not sharded — it runs on one GPU only (comm / world > 1)");
     if (poly && rowmode) return hb_fail(HB_ERR_UNSUPPORTED, "BSLMM: the polygenic block is not available with shard_rows");
     if (poly && a.warm) return hb_fail(HB_ERR_UNSUPPORTED, "BSLMM: a warm start (hb_warm_state) does not carry the polygenic state (k, vb)");
+    if (epsl && (sharded || world > 1))
+        return hb_fail(HB_ERR_UNSUPPORTED, "the epsilon block is not sharded — it runs on one GPU only (comm / world > 1)");
+    if (epsl && rowmode) return hb_fail(HB_ERR_UNSUPPORTED, "the epsilon block is not available with shard_rows");
+    if (epsl && a.warm) return hb_fail(HB_ERR_UNSUPPORTED, "the epsilon block: a warm start (hb_warm_state) does not carry its state (epsilon, J, veps)");
     sync_blocks = std::max(1, std::min(64, (int)a.sync_blocks));
     m_global = (!rowmode && (world > 1 || a.m_global > 0)) ? a.m_global : m;
     if (!rowmode && world > 1 && ((!a.allreduce && !a.comm) || m_global < m))
@@ -528,6 +563,17 @@ int hb_run::configure_device()
         if (rc) return rc;
     }
     a.Ki = a.Kival = nullptr; // consumed
+    if (epsl) {
+        const hb_epsl_desc d{&epsl_gi, eps_index.data(), eps_yJ.data()};
+        rc = hb_ctx_epsl_setup(c, &d);
+        if (rc) return rc;
+        std::vector<int64_t>().swap(eg_indptr); // (the context holds its own copies)
+        std::vector<int32_t>().swap(eg_indices);
+        std::vector<double>().swap(eg_data);
+    } else if (c->epsl) { // a caller's context that an earlier run left the block on: this run has none
+        rc = hb_ctx_epsl_setup(c, nullptr);
+        if (rc) return rc;
+    }
 
     rc = open_exchange();
     if (!rc) rc = marker_statistics();
@@ -792,6 +838,13 @@ int hb_run::start_chain()
         s_Va.assign(n_records, 0.0);
         s_Vb.assign(n_records, 0.0);
     }
+    if (epsl) {
+        rc = hb_epsl_reset(c); // epsilon = 0, J = 0 (:251, :268)
+        if (rc) return rc;
+        s_Veps.assign(n_records, 0.0);
+        s_J.assign(n_records, 0.0);
+        if (store_eps) s_eps.assign((size_t)n_records * qe, 0.0);
+    }
     return HB_OK;
 }
 
@@ -836,6 +889,14 @@ int hb_run::step()
     if (poly) {
         const double chis = hs.chisq(dfvara_ + (double)n);
         rc = hb_ctx_poly_step(c, vare_, iter == 0 ? vara_ : -1.0, a.seed, iter, chis, s2vara_ * dfvara_); // (vbtmp = vara_, :333)
+        if (rc) return rc;
+    }
+    // the single-step epsilon block (:554-584), enqueued the same way and at the same place: the J draw's normal (:559) and the chisq of :579
+    // from the host stream here, the rows' normals on the device; veps and J come back with the sweep's fetch
+    if (epsl) {
+        const double zJ = hs.norm();
+        const double chis = hs.chisq(dfvara_ + (double)qe);
+        rc = hb_ctx_epsl_step(c, vare_, iter == 0 ? vara_ : -1.0, a.seed, iter, zJ, chis, s2vara_ * dfvara_); // (vepstmp = vara_, :332)
         if (rc) return rc;
     }
 
@@ -985,6 +1046,12 @@ int hb_run::step()
         vb = ps[0];
     }
 
+    if (epsl) {
+        const double *es = hb_epsl_host_state(c);
+        veps = es[0];
+        eps_J = es[2];
+    }
+
     // hyper-parameters after the sweep (hb_model.hpp)
     hb_draw_hyper(hs, hb_hyper_prior{model_index, n_fold, fixpi, dfvara_, s2varg_, shape0, rate0, fold_.data()},
                   hb_hyper_sums{so.sum_g2, so.sum_vargL, so.class_count, (double)m_global, (double)nvar0},
@@ -1012,6 +1079,12 @@ int hb_run::step()
             s_Va[count] = va;
             s_Vb[count] = vb;
             rc = hbk_poly_accumulate(c);
+            if (rc) return rc;
+        }
+        if (epsl) { // :873-877
+            s_Veps[count] = veps;
+            s_J[count] = eps_J;
+            rc = hbk_epsl_accumulate(c, store_eps ? s_eps.data() + (size_t)count * qe : nullptr);
             if (rc) return rc;
         }
         vara_sum += vara_;
@@ -1052,6 +1125,7 @@ int hb_run::step()
         char lam[32] = {0};
         if (model == "BayesL") snprintf(lam, sizeof(lam), "%.4f ", lambda);
         if (poly) snprintf(lam, sizeof(lam), "%.4f %.4f ", va, vb); // :901
+        if (epsl) snprintf(lam + strlen(lam), sizeof(lam) - strlen(lam), "%.4f ", veps); // :908
         line(" %d %lld %s%s%.4f %.4f %.4f %02dh%02dm%02ds", iter + 1, NnzSnp, pis, lam, vara_, vare_, vara_ / vt, tt / 3600,
              tt % 3600 / 60, tt % 3600 % 60);
     }
@@ -1153,6 +1227,21 @@ int hb_run::finish(hb_bayes_out *o)
         for (int t = 0; t < nr; t++)
             for (int k = 0; k < n; k++) e[k] -= est[lev_first[t] + zid[(size_t)t * n + k]];
         if (o->r_est) std::memcpy(o->r_est, est.data(), sizeof(double) * n_levels);
+    }
+    if (epsl) { // :987-994: e -= mean(J) y_J, e.tail(ne) -= Z mean(epsilon)
+        if (!epsl_finished) {
+            eps_mean.assign(qe, 0.0);
+            std::vector<int32_t> idx(ne);
+            rc = hbk_epsl_sum(c, eps_mean.data(), idx.data());
+            if (rc) return rc;
+            for (double &v : eps_mean) v /= Rn;
+            eps_index.resize(ne);
+            for (int r = 0; r < ne; r++) eps_index[r] = (uint32_t)idx[r];
+            epsl_finished = true;
+        }
+        const double Jm = n_records > 0 ? arma_sum(s_J.data(), s_J.size()) / Rn : 0.0;
+        for (int k = 0; k < n; k++) e[k] -= Jm * eps_yJ[k];
+        for (int r = 0; r < ne; r++) e[n - ne + r] -= eps_mean[eps_index[r]];
     }
     if (o->g) { rc = hb_ctx_get_residual(c, nullptr, o->g); if (rc) return rc; } // :1023, final-iteration u
     if (o->e) std::memcpy(o->e, e.data(), sizeof(double) * n);
@@ -1266,6 +1355,39 @@ int hb_run_poly(hb_run *r, hb_poly_out *po)
     return HB_OK;
 }
 
+int hb_run_epsl(hb_run *r, hb_epsl_out *eo)
+{
+    if (!r || !eo) return hb_fail(HB_ERR_INVALID, "hb_run_epsl: null argument");
+    if (!r->epsl) return hb_fail(HB_ERR_INVALID, "hb_run_epsl: the run has no epsilon block (epsl_y_J / epsl_Gi / epsl_index)");
+    if (!r->epsl_finished) return hb_fail(HB_ERR_INVALID, "hb_run_epsl: call hb_run_finish first");
+    const int R = r->n_records;
+    auto mean_sd = [&](const std::vector<double> &v, double *mean, double *sd) { // arma::mean / stddev (N - 1), :988-991
+        *mean = R > 0 ? arma_sum(v.data(), v.size()) / R : 0.0;
+        *sd = std::sqrt(var_n1(v.data(), v.size()));
+    };
+    mean_sd(r->s_Veps, &eo->Veps, &eo->Veps_sd);
+    mean_sd(r->s_J, &eo->J, &eo->J_sd);
+    if (eo->s_Veps && R) std::memcpy(eo->s_Veps, r->s_Veps.data(), sizeof(double) * R);
+    if (eo->s_J && R) std::memcpy(eo->s_J, r->s_J.data(), sizeof(double) * R);
+    if (eo->epsilon) std::memcpy(eo->epsilon, r->eps_mean.data(), sizeof(double) * r->qe);
+    if (eo->s_epsilon) {
+        if (!r->store_eps) return hb_fail(HB_ERR_INVALID, "hb_run_epsl: the run kept no epsilon records (hb_run_epsl_store(r, 0))");
+        if (R) std::memcpy(eo->s_epsilon, r->s_eps.data(), sizeof(double) * (size_t)R * r->qe);
+    }
+    return HB_OK;
+}
+
+int hb_run_epsl_store(hb_run *r, int32_t store_epsilon)
+{
+    if (!r) return hb_fail(HB_ERR_INVALID, "hb_run_epsl_store: null run");
+    if (!r->epsl) return hb_fail(HB_ERR_INVALID, "hb_run_epsl_store: the run has no epsilon block (epsl_y_J / epsl_Gi / epsl_index)");
+    if (r->iter > 0) return hb_fail(HB_ERR_INVALID, "hb_run_epsl_store: the run has started");
+    r->store_eps = store_epsilon != 0;
+    if (r->store_eps) r->s_eps.assign((size_t)r->n_records * r->qe, 0.0);
+    else std::vector<double>().swap(r->s_eps);
+    return HB_OK;
+}
+
 int hb_run_finish(hb_run *r, hb_bayes_out *out)
 {
     if (!r || !out) return hb_fail(HB_ERR_INVALID, "hb_run_finish: null argument");
@@ -1276,18 +1398,19 @@ void hb_run_destroy(hb_run *r) { delete r; }
 
 int hb_bayes_run(const hb_bayes_args *args, hb_bayes_out *out) { return hb_bayes_run_poly(args, out, nullptr); }
 
-int hb_bayes_run_poly(const hb_bayes_args *args, hb_bayes_out *out, hb_poly_out *poly_out)
+int hb_bayes_run_poly(const hb_bayes_args *args, hb_bayes_out *out, hb_poly_out *poly_out) { return hb_bayes_run_epsl(args, out, poly_out, nullptr); }
+
+int hb_bayes_run_epsl(const hb_bayes_args *args, hb_bayes_out *out, hb_poly_out *poly_out, hb_epsl_out *epsl_out)
 {
     if (!args || !out) return hb_fail(HB_ERR_INVALID, "hb_bayes_run: null argument");
     hb_run *r = nullptr;
     int rc = hb_run_create(args, &r);
     if (rc) return rc;
-    while (!r->done) {
-        rc = r->step();
-        if (rc) break;
-    }
+    if (r->epsl && !(epsl_out && epsl_out->s_epsilon)) rc = hb_run_epsl_store(r, 0);
+    while (!rc && !r->done) rc = r->step();
     if (!rc) rc = r->finish(out);
     if (!rc && poly_out) rc = hb_run_poly(r, poly_out);
+    if (!rc && epsl_out) rc = hb_run_epsl(r, epsl_out);
     delete r;
     return rc;
 }

@@ -4,6 +4,7 @@ import ctypes as C
 
 import numpy as np
 
+from . import _lib
 from ._lib import CtxParams, LaunchStats, SweepIn, SweepOut, SweepTiming, HB_MAX_FOLD, HB_ND, check, lib
 
 MODEL_INDEX = {"BayesRR": 1, "BayesA": 2, "BayesB": 3, "BayesBpi": 3, "BayesC": 4, "BayesCpi": 4,
@@ -319,6 +320,42 @@ class Context:
         out = [np.zeros(self.n) for _ in range(4)]
         check(self.L.hb_ctx_poly_debug_get(self.h, *[x.ctypes.data for x in out]))
         return dict(zip(("t", "w", "eval", "Kg"), out))
+
+    # ---- the single-step model's epsilon block (reference src/Bayes.cpp:554-584) ----
+    def epsl_setup(self, y_J, Gi, index):
+        """y_J (n), Gi (q x q: a scipy sparse matrix or an (indptr, indices, data) CSC triple of the full symmetric matrix) and index (the
+        1-based column of Gi of each of the LAST len(index) individuals). epsilon and J start at 0."""
+        from .ssbayes import epsl_descriptor
+        gi, idx, keep = epsl_descriptor(Gi, index)
+        yj = np.ascontiguousarray(y_J, dtype=np.float64).ravel()
+        if yj.size != self.n:
+            raise ValueError("epsl_setup: y_J holds %d values, the context %d individuals" % (yj.size, self.n))
+        d = _lib.EpslDesc(C.pointer(gi), idx.ctypes.data, yj.ctypes.data)
+        check(self.L.hb_ctx_epsl_setup(self.h, C.byref(d)))
+        self._epsl_q = gi.q
+        del keep
+
+    def epsl_step(self, vare, veps_in, seed, it, zJ, chis, s2_df):
+        """Enqueue one iteration of the block (no host sync): veps_in < 0 keeps the device's veps."""
+        check(self.L.hb_ctx_epsl_step(self.h, float(vare), float(veps_in), int(seed), int(it), float(zJ), float(chis), float(s2_df)))
+
+    def epsl_state(self):
+        """(epsilon, veps, q = x'Gx, J) after the last step."""
+        x = np.zeros(self._epsl_q)
+        ve, q, J = C.c_double(), C.c_double(), C.c_double()
+        check(self.L.hb_ctx_epsl_state(self.h, x.ctypes.data, C.byref(ve), C.byref(q), C.byref(J)))
+        return x, ve.value, q.value, J.value
+
+    def epsl_debug(self):
+        """Debug read-out of the last step: b, the epsilon it started from, the J draw's y_J . yadj, and the schedule's counts."""
+        b, xo, rhs, cnt = np.zeros(self._epsl_q), np.zeros(self._epsl_q), np.zeros(1), np.zeros(4, dtype=np.int32)
+        check(self.L.hb_ctx_epsl_debug_get(self.h, b.ctypes.data, xo.ctypes.data, rhs.ctypes.data, cnt.ctypes.data))
+        return {"b": b, "x_old": xo, "rhs": float(rhs[0]), "steps": int(cnt[0]), "launches": int(cnt[1]), "levels": int(cnt[2]), "max_col": int(cnt[3])}
+
+    def epsl_force(self, sched_mode=0, row_mode=0):
+        """Debug setter: rebuild the schedule with every step in single-workgroup launches (sched_mode 1) or wide (2), every row on a lane
+        (row_mode 1) or a wave (2); 0 = the plan's own choice. The chain must not change by a bit."""
+        check(self.L.hb_ctx_epsl_debug_set(self.h, int(sched_mode), int(row_mode)))
 
     def grm(self, lambda_=0.0, raw=False):
         """The genomic relationship matrix of the resident int8 genotypes (hb_grm_build; make_grm() of the reference, src/rm.cpp:5-53)."""

@@ -128,9 +128,10 @@ typedef struct hb_bayes_args {
     int32_t niter;           /* (:70) default 50000 */
     int32_t nburn;           /* (:71) default 20000 */
     int32_t thin;            /* (:72) default 5     */
-    const double *epsl_y_J;  /* single-step epsilon block (:73-75) — must be NULL           */
-    const void *epsl_Gi;
-    const uint32_t *epsl_index;
+    const double *epsl_y_J;  /* single-step epsilon block (:73-75, :554-584): all three or none. epsl_y_J: the n values of the J covariate */
+    const void *epsl_Gi;     /* -> hb_epsl_gi (below): the q x q matrix of the non-genotyped individuals, A^-1_nn, and ne                 */
+    const uint32_t *epsl_index; /* ne entries, 1-BASED as the reference takes them (:255-256): the column of epsl_Gi of each of the LAST ne
+                                records. With marker shards, shard_rows, a warm start or BSLMM: HB_ERR_UNSUPPORTED                        */
     /* Nullable<double> dfvr..s2ve (:76-83): value used only when the has_ flag is set      */
     int32_t has_dfvr, has_s2vr, has_vg, has_dfvg, has_s2vg, has_ve, has_dfve, has_s2ve;
     double dfvr, s2vr, vg, dfvg, s2vg, ve, dfve, s2ve;
@@ -265,6 +266,36 @@ typedef struct hb_poly_out {
  * that has no polygenic block is HB_ERR_INVALID. */
 int hb_bayes_run_poly(const hb_bayes_args *args, hb_bayes_out *out, hb_poly_out *poly_out);
 
+/* The single-step model (ssbrm(), R/ssbayes.r; src/Bayes.cpp:254-275, :554-584, :873-878, :987-1001). hb_bayes_args.epsl_Gi points at this
+ * descriptor: the FULL symmetric q x q matrix (both triangles) in canonical compressed-sparse-column form — indptr q + 1 entries from 0,
+ * the row indices of a column 0-based, sorted and unique, a positive diagonal stored in every column, finite values — and ne, the length of
+ * epsl_index. Anything else is HB_ERR_INVALID. */
+typedef struct hb_epsl_gi {
+    int32_t q, ne;
+    const int64_t *indptr;
+    const int32_t *indices;
+    const double *data;
+} hb_epsl_gi;
+/* What the epsilon block adds to the result. Caller-allocated arrays, NULL = not wanted; s_epsilon == NULL in hb_bayes_run_epsl is the
+ * reference's store without the q x R matrix (store_epsilon = 0): only the running mean is kept. */
+typedef struct hb_epsl_out {
+    double Veps, Veps_sd, J, J_sd; /* mean and sd (N - 1) of the records (:988-991) */
+    double *s_Veps, *s_J;    /* R each (:874-875) */
+    double *epsilon;         /* q: the mean of the records (:992) */
+    double *s_epsilon;       /* q x R column-major (:876) */
+} hb_epsl_out;
+/* hb_bayes_run that also reports the epsilon block (and the polygenic one: never both in one run); either out may be NULL. epsl_out with a
+ * run that has no epsilon block is HB_ERR_INVALID. */
+int hb_bayes_run_epsl(const hb_bayes_args *args, hb_bayes_out *out, hb_poly_out *poly_out, hb_epsl_out *epsl_out);
+/* the descriptor's and the index's validation alone (no device needed): HB_OK or HB_ERR_INVALID with the reason in hb_last_error() */
+int hb_epsl_check(const hb_epsl_gi *Gi, const uint32_t *epsl_index, int32_t n);
+/* The schedule of the Gibbs pass for a pattern (hb_epslplan.hpp; no device needed): level[q], rows[q] (the rows in launch order), steps
+ * (5 ints each: level, first lane row, lane rows, first wave row, wave rows — positions in rows[]; room for q steps), launches (3 ints
+ * each: kind 0 = one workgroup walks steps [s0, s1) / 1 = step s0 over the chip, s0, s1; room for q), counts[4] = steps, launches, levels,
+ * longest column. sched_mode 0 auto / 1 all single-workgroup / 2 all wide; row_mode 0 auto / 1 lanes only / 2 waves only. NULL = not wanted. */
+int hb_epsl_plan(int32_t q, const int64_t *indptr, const int32_t *indices, int32_t sched_mode, int32_t row_mode, int32_t *level, int32_t *rows,
+                 int32_t *steps, int32_t *launches, int32_t *counts);
+
 /* The same sampler, stepwise: create (validation, upload, marker statistics, Gram, priors) ->
  * step (iterations of the loop at src/Bayes.cpp:477) -> finish (posterior assembly, :919-1040).
  * hb_bayes_run() is exactly create + step-until-finished + finish. The caller's arrays are copied
@@ -291,6 +322,10 @@ hb_ctx *hb_run_ctx(hb_run *r);
 int hb_run_finish(hb_run *r, hb_bayes_out *out);
 /* after hb_run_finish of a BSLMM run: the polygenic block's results */
 int hb_run_poly(hb_run *r, hb_poly_out *poly_out);
+/* after hb_run_finish of a run with the epsilon block: its results */
+int hb_run_epsl(hb_run *r, hb_epsl_out *epsl_out);
+/* before the first step: keep the q x R matrix of epsilon records (default 1), or the running mean alone (0) */
+int hb_run_epsl_store(hb_run *r, int32_t store_epsilon);
 void hb_run_destroy(hb_run *r);
 
 /* ------------------------------------------------------------------------------------
@@ -670,6 +705,27 @@ int hb_ctx_poly_state(hb_ctx *c, double *k, double *vb, double *q, int32_t *flag
 /* Debug read-out for the kernel-level tests (tests/test_gpu_bslmm.py): what the last step left, n doubles each, any pointer may be NULL —
  * t = K'(yadj + k_old), w (the vector K multiplies), eval, Kg = K' k_new. Synchronises and changes nothing. */
 int hb_ctx_poly_debug_get(hb_ctx *c, double *t, double *w, double *eval, double *Kg);
+
+/* The single-step model's epsilon block of one iteration (src/Bayes.cpp:554-584) as device kernels with no host synchronisation (DESIGN.md
+ * section 18). setup copies the descriptor's arrays, y_J (n) and index (ne, 1-based), validates them as hb_epsl_check does and builds the
+ * schedule; epsilon and J start at 0. desc == NULL drops the block.
+ * step: J (:555-564) with the caller's normal zJ; the Gibbs pass over the q rows (:565-576), row i drawing the normal of Philox purpose 6 at
+ * blk = i; veps = (x'Gx + s2_df) / chis (:577-583) with chis = chisq_sample(dfvara + q) drawn by the caller. veps_in < 0 uses the veps the
+ * previous step left on the device (the first step needs veps_in = vara, :332). yadj, its fp32 image and u stay coherent.
+ * state: synchronises; x (q) = epsilon. Inside hb_run_step veps, q and J come back with the sweep's fetch. */
+typedef struct hb_epsl_desc {
+    const hb_epsl_gi *Gi;
+    const uint32_t *index;
+    const double *y_J;
+} hb_epsl_desc;
+int hb_ctx_epsl_setup(hb_ctx *c, const hb_epsl_desc *desc);
+int hb_ctx_epsl_step(hb_ctx *c, double vare, double veps_in, uint64_t seed, int64_t iter, double zJ, double chis, double s2_df);
+int hb_ctx_epsl_state(hb_ctx *c, double *x, double *veps, double *q, double *J);
+/* Debug read-out and setter for the kernel-level tests (tests/test_gpu_epsl.py): what the last step left — b (q), the epsilon it started
+ * from (q), the J draw's y_J . yadj —, counts[4] as hb_epsl_plan's; any pointer may be NULL. debug_set rebuilds the schedule under forced
+ * modes (hb_epsl_plan's): the chain must not change by a bit. Both synchronise. */
+int hb_ctx_epsl_debug_get(hb_ctx *c, double *b, double *x_old, double *rhs, int32_t *counts);
+int hb_ctx_epsl_debug_set(hb_ctx *c, int32_t sched_mode, int32_t row_mode);
 
 /* One marker sweep (reference src/Bayes.cpp:586-816) plus the two reductions behind
  * :819 and :823.  Hyper-parameters come from the host, per-SNP draws happen on device. */

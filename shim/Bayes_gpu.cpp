@@ -59,13 +59,25 @@ Rcpp::List Bayes(arma::vec &y, arma::mat &X, std::string model, arma::vec Pi,
         for (auto &s : rs) rp.push_back(s.c_str());
         a.R = rp.data();  a.nr = R_.ncol(); }
     // BSLMM's Kival / Ki and the single-step epsilon block: ANY non-NULL value reaches the library. With both Kival and Ki and model "BSLMM" the
-    // polygenic block runs on the device; an incomplete pair, either of them under another model, and the epsilon block are answered with
-    // HB_ERR_UNSUPPORTED and a text (-> an R error), never with a silent fit without the block
+    // polygenic block runs on the device, with all three epsl_* arguments the epsilon block does (src/Bayes.cpp:554-584); an incomplete pair or
+    // triple and either pair under another model are answered with an error code and a text (-> an R error), never with a silent fit without the block
     arma::vec Kival_; if (Kival.isNotNull()) { Kival_ = as<arma::vec>(Kival); a.Kival = Kival_.memptr(); }
     arma::mat Ki_;    if (Ki.isNotNull())    { Ki_ = as<arma::mat>(Ki);       a.Ki = Ki_.memptr(); }
     arma::vec ey_;    if (epsl_y_J.isNotNull())   { ey_ = as<arma::vec>(epsl_y_J); a.epsl_y_J = ey_.memptr(); }
-    arma::sp_mat eg_; if (epsl_Gi.isNotNull())    { eg_ = as<arma::sp_mat>(epsl_Gi); a.epsl_Gi = (const void *)&eg_; }
-    arma::uvec ei_;   if (epsl_index.isNotNull()) { ei_ = as<arma::uvec>(epsl_index); a.epsl_index = (const uint32_t *)ei_.memptr(); }
+    // epsl_Gi as the library's descriptor hb_epsl_gi: the sp_mat is compressed-sparse-column already (sync() settles pending writes; its
+    // columns are sorted), its uword arrays are narrowed to the descriptor's types; epsl_index stays 1-based as R passes it (:255-256)
+    arma::sp_mat eg_; hb_epsl_gi gi_ = {}; std::vector<int64_t> gp_; std::vector<int32_t> gr_; std::vector<uint32_t> ei_;
+    if (epsl_index.isNotNull()) { arma::uvec e_ = as<arma::uvec>(epsl_index); ei_.assign(e_.begin(), e_.end()); if (ei_.empty()) ei_.push_back(0); a.epsl_index = ei_.data(); }
+    if (epsl_Gi.isNotNull()) {
+        eg_ = as<arma::sp_mat>(epsl_Gi);
+        if (eg_.n_cols != eg_.n_rows) throw Rcpp::exception("variance-covariance matrix should be in square.");   // :263
+        eg_.sync();
+        gp_.assign(eg_.col_ptrs, eg_.col_ptrs + eg_.n_cols + 1);
+        gr_.assign(eg_.row_indices, eg_.row_indices + eg_.n_nonzero);
+        gi_.q = (int32_t)eg_.n_cols;  gi_.ne = epsl_index.isNotNull() ? (int32_t)as<arma::uvec>(epsl_index).n_elem : 0;
+        gi_.indptr = gp_.data();  gi_.indices = gr_.data();  gi_.data = eg_.values;
+        a.epsl_Gi = (const void *)&gi_;
+    }
     a.niter = niter;  a.nburn = nburn;  a.thin = thin;
     #define OPT(name) if (name.isNotNull()) { a.has_##name = 1; a.name = as<double>(name); }
     OPT(dfvr) OPT(s2vr) OPT(vg) OPT(dfvg) OPT(s2vg) OPT(ve) OPT(dfve) OPT(s2ve)
@@ -93,7 +105,12 @@ Rcpp::List Bayes(arma::vec &y, arma::mat &X, std::string model, arma::vec Pi,
     o.s_alpha = s_alpha.memptr(); o.s_pi = s_pi.memptr(); o.s_beta = s_beta.memptr(); o.s_Vr = s_Vr.memptr(); o.s_r = s_r.memptr();
     o.s_Vg = s_Vg.memptr(); o.s_Ve = s_Ve.memptr(); o.s_h2 = s_h2.memptr(); o.s_mu = s_mu.memptr();
 
-    if (hb_bayes_run(&a, &o) != HB_OK) throw Rcpp::exception(hb_last_error());   // same texts as src/Bayes.cpp:92-117
+    const bool has_epsl = a.epsl_Gi != nullptr;
+    const int qe = has_epsl ? gi_.q : 0;
+    arma::vec epsilon(qe);  arma::mat s_epsilon(qe, has_epsl ? n_records : 0);  arma::rowvec s_Veps(has_epsl ? n_records : 0), s_J(has_epsl ? n_records : 0);
+    hb_epsl_out eo = {};
+    eo.epsilon = epsilon.memptr(); eo.s_epsilon = s_epsilon.memptr(); eo.s_Veps = s_Veps.memptr(); eo.s_J = s_J.memptr();
+    if (hb_bayes_run_epsl(&a, &o, nullptr, has_epsl ? &eo : nullptr) != HB_OK) throw Rcpp::exception(hb_last_error());   // same texts as src/Bayes.cpp:92-117
 
     List results, MCMCsample;                                    // same names/shapes as src/Bayes.cpp:919-1040
     if (nr) { results["Vr"] = Vr; MCMCsample["Vr"] = s_Vr; }
@@ -105,6 +122,9 @@ Rcpp::List Bayes(arma::vec &y, arma::mat &X, std::string model, arma::vec Pi,
     if (nr) { // Levels = sorted unique strings of each R column (makeZ, :36-37), Estimation = r_est[0 : o.n_levels)
         results["r"] = DataFrame::create(Named("Levels") = levels_of(R_, nlev), Named("Estimation") = arma::vec(r_est.head(o.n_levels)));
         MCMCsample["r"] = arma::mat(s_r.head_rows(o.n_levels)); }
+    if (has_epsl) { // :995-1000
+        results["Veps"] = eo.Veps; results["J"] = eo.J; results["epsilon"] = epsilon;
+        MCMCsample["Veps"] = s_Veps; MCMCsample["J"] = s_J; MCMCsample["epsilon"] = s_epsilon; }
     results["g"] = g; results["e"] = e; results["pip"] = pip;
     if (nw) results["gwas"] = gwas;
     results["MCMCsamples"] = MCMCsample;
