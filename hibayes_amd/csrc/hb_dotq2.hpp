@@ -327,16 +327,102 @@ __device__ __forceinline__ void dotq2m_tile(const dq_view &v, char *smem, int b)
 // 16-byte chunk l % 8 — k_dotq2's mapping) and a stage is multiplied in two halves of 256 individuals. The operand read of lane (m, kb), half h,
 // is chunk 4 h + kb of column m of the column tile: a 4-way bank conflict on the read (eight 128-byte rows 128 bytes apart), paid for with LDS
 // cycles the kernel does not need. 64 columns per wave.
+//
+// The digit planes do not pass through LDS here: lane (m, kb) needs, for half h of a stage, the 64 contiguous bytes of plane m at offset 256 h + 64 kb
+// of the stage's 512 — two times four 16-byte loads straight into registers (lanes m >= 7 feed output columns nobody looks at: they load nothing and
+// hold zeros), 8 loads per stage where there were 4 DMA pieces, 8 LDS reads and their bank conflicts. The LDS ring holds genotype stages only,
+// Q2M_RING of them at the head of the shape's allocation (q2m512_lds, which still counts the digit pieces: the launch plan and its recorded LDS sizes are
+// unchanged), and a tile keeps Q2M_RING - 1 stages of 8 KB in flight. A stage is 8 DMA pieces followed by 8 register loads on the wave's one vmcnt queue,
+// counted by hand: the DMA statements and the register loads are both inline asm (the compiler counts neither; beside loads of its own it would wait
+// for the DMA early).
+//   Depth: three, as before. Four stage buffers fit the allocation and were measured (profiles/q2m_ring_timing.txt): three stages in flight are
+// SLOWER than two at 784, 616 and 448 tiles alike (616, the pipeline's count: 12.6 - 13.3 against 12.1 - 12.2 us per isolated launch) — a tile is
+// not waiting out a round trip that more requests would hide.
+//   The digit ring lives in accumulator registers that the statements below name themselves, a[Q2M_ABASE ..]: slot s, register 16 h + 4 r + k = dword k
+// of the 16 bytes at 256 h + 64 kb + 16 r. A load's destination is a register the compiler knows nothing about, so it cannot copy, spill or reuse it
+// while the data is under way (as C++ values the ring was copied from slot to slot at the loop's back edge, ahead of the waits); the statement that
+// waits for a stage also moves it out, v_accvgpr_read register by register into the B operands — the gather k of (4 r + k) that the operands need anyway.
+// Every statement that writes the ring lists all of it as clobbered: nothing of the compiler's that lives across one can sit there (the kernel's own
+// accumulators live across all of them).
+#define Q2M_RING 3   /* genotype stage buffers of dotq2m512_tile = slots of the digit register ring */
+#define Q2M_ABASE 64 /* first accumulator register of the digit ring: 32 per slot, a[64:159] */
+#define Q2M_CL10(t) "a" #t "0", "a" #t "1", "a" #t "2", "a" #t "3", "a" #t "4", "a" #t "5", "a" #t "6", "a" #t "7", "a" #t "8", "a" #t "9"
+#define Q2M_RING_REGS \
+    "a64", "a65", "a66", "a67", "a68", "a69", Q2M_CL10(7), Q2M_CL10(8), Q2M_CL10(9), Q2M_CL10(10), Q2M_CL10(11), Q2M_CL10(12), Q2M_CL10(13), Q2M_CL10(14), Q2M_CL10(15)
+static_assert(Q2M_ABASE == 64 && Q2M_RING == 3, "Q2M_RING_REGS spells out a[64:159]");
+
+// zeros in every lane of a slot (once per tile: the lanes that never load keep them)
+template <int SLOT>
+__device__ __forceinline__ void q2m_zero_digits()
+{
+#define Q2M_Z4(i) "v_accvgpr_write_b32 a[%c[b]+" #i "], 0\n\tv_accvgpr_write_b32 a[%c[b]+" #i "+1], 0\n\tv_accvgpr_write_b32 a[%c[b]+" #i "+2], 0\n\tv_accvgpr_write_b32 a[%c[b]+" #i "+3], 0\n\t"
+    asm volatile(Q2M_Z4(0) Q2M_Z4(4) Q2M_Z4(8) Q2M_Z4(12) Q2M_Z4(16) Q2M_Z4(20) Q2M_Z4(24) Q2M_Z4(28) "s_nop 0" ::[b] "i"(Q2M_ABASE + 32 * SLOT) : Q2M_RING_REGS);
+#undef Q2M_Z4
+}
+
+// the eight digit loads of one stage into a slot (active: the lanes with m < HB_ND; the others keep what they hold). The base may be fresh from
+// v_readfirstlane: five wait states before the first load reads it.
+template <int SLOT>
+__device__ __forceinline__ void q2m_load_digits(unsigned voff, const int8_t *sbase, unsigned long long active)
+{
+    unsigned long long keep;
+    asm volatile("s_mov_b64 %[k], exec\n\ts_and_b64 exec, exec, %[a]\n\ts_nop 2\n\t"
+                 "global_load_dwordx4 a[%c[b]:%c[b]+3], %[v], %[s]\n\t"
+                 "global_load_dwordx4 a[%c[b]+4:%c[b]+7], %[v], %[s] offset:16\n\t"
+                 "global_load_dwordx4 a[%c[b]+8:%c[b]+11], %[v], %[s] offset:32\n\t"
+                 "global_load_dwordx4 a[%c[b]+12:%c[b]+15], %[v], %[s] offset:48\n\t"
+                 "global_load_dwordx4 a[%c[b]+16:%c[b]+19], %[v], %[s] offset:256\n\t"
+                 "global_load_dwordx4 a[%c[b]+20:%c[b]+23], %[v], %[s] offset:272\n\t"
+                 "global_load_dwordx4 a[%c[b]+24:%c[b]+27], %[v], %[s] offset:288\n\t"
+                 "global_load_dwordx4 a[%c[b]+28:%c[b]+31], %[v], %[s] offset:304\n\t"
+                 "s_mov_b64 exec, %[k]"
+                 : [k] "=&s"(keep)
+                 : [v] "v"(voff), [s] "s"(sbase), [a] "s"(active), [b] "i"(Q2M_ABASE + 32 * SLOT)
+                 : "memory", "scc", Q2M_RING_REGS);
+}
+
+// everything but the N newest vector-memory operations of the wave has landed; then the slot's digits as the B operands of the stage's two halves:
+// B[h][k] register r = dword 4 r + k of the lane's 64 digit bytes of half h (the closing s_nop: a register just written, then an MFMA reading it)
+template <int SLOT, int N>
+__device__ __forceinline__ void q2m_take_digits(hb_v4i (&B)[2][4])
+{
+#define Q2M_RD(k, r) "v_accvgpr_read_b32 %[o" #k #r "], a[%c[b]+4*" #r "+" #k "]\n\t"
+#define Q2M_RD4(k) Q2M_RD(k, 0) Q2M_RD(k, 1) Q2M_RD(k, 2) Q2M_RD(k, 3)
+#define Q2M_OUT(k, r) [o##k##r] "=v"(o[4 * k + r])
+#define Q2M_OUT4(k) Q2M_OUT(k, 0), Q2M_OUT(k, 1), Q2M_OUT(k, 2), Q2M_OUT(k, 3)
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        int o[16];
+        if (h == 0)
+            asm volatile("s_waitcnt vmcnt(%c[n])\n\t" Q2M_RD4(0) Q2M_RD4(1) Q2M_RD4(2) Q2M_RD4(3) "s_nop 1"
+                         : Q2M_OUT4(0), Q2M_OUT4(1), Q2M_OUT4(2), Q2M_OUT4(3)
+                         : [n] "i"(N), [b] "i"(Q2M_ABASE + 32 * SLOT)
+                         : "memory");
+        else
+            asm volatile(Q2M_RD4(0) Q2M_RD4(1) Q2M_RD4(2) Q2M_RD4(3) "s_nop 1"
+                         : Q2M_OUT4(0), Q2M_OUT4(1), Q2M_OUT4(2), Q2M_OUT4(3)
+                         : [b] "i"(Q2M_ABASE + 32 * SLOT + 16)
+                         : "memory");
+#pragma unroll
+        for (int k = 0; k < 4; k++) B[h][k] = hb_v4i{o[4 * k], o[4 * k + 1], o[4 * k + 2], o[4 * k + 3]};
+    }
+#undef Q2M_OUT4
+#undef Q2M_OUT
+#undef Q2M_RD4
+#undef Q2M_RD
+}
+
 template <bool SC, bool SWZ>
 __device__ __forceinline__ void dotq2m512_tile(const dq_view &v, char *smem, int b)
 {
     // SWZ: the DMA lanes are dealt so that the operand reads are bank-conflict free — tile piece: lane l = column l % 8, chunk l / 8 (slot = chunk * 8 + column:
-    // the 16 lanes of a read group take two runs of 128 consecutive bytes, the pieces 1152 bytes apart = 32 banks); digit piece j: lane l = plane l % 8,
-    // chunk 8 j + l / 8 (slot = chunk * 8 + plane: the seven planes of a read group are neighbours). The eight lanes that share a 128-byte line are then
-    // eight apart; without SWZ they are neighbours and the reads conflict four- and seven-fold.
+    // the 16 lanes of a read group take two runs of 128 consecutive bytes, the pieces 1152 bytes apart = 32 banks). The eight lanes that share a 128-byte
+    // line are then eight apart; without SWZ they are neighbours and the reads conflict four-fold.
     constexpr int XSL = SWZ ? 1152 : HBQ_SLOT;
-    constexpr int NXP = 8, NDP = 4, XB = NXP * XSL, BUF = XB + NDP * 1024, PER = NXP + NDP, NSC = SC ? 4 : 1;
-    static_assert((Q2M_NBUF - 1) * PER <= 63, "the in-flight DMA pieces must fit the 6-bit vmcnt");
+    constexpr int NXP = 8, NDL = 8, XB = NXP * XSL, PER = NXP + NDL, NSC = SC ? 4 : 1, RING = Q2M_RING;
+    static_assert(RING == 3, "the prologue and the counted waits below are written out for two stages in flight");
+    static_assert(RING * XB <= q2m512_lds(SWZ), "the genotype ring lives in the shape's recorded LDS allocation");
+    static_assert((RING - 1) * PER <= 63, "the in-flight DMA pieces and digit loads must fit the 6-bit vmcnt");
     const int lane = threadIdx.x;
     const int cg = b % v.ncg, sp = b / v.ncg;
     if (b == 0 && lane == 0) *v.gexp_out = *v.vexp_in;
@@ -346,59 +432,66 @@ __device__ __forceinline__ void dotq2m512_tile(const dq_view &v, char *smem, int
     const uint8_t *xg = v.X2 + (int64_t)cg * 64 * ld2;
     const int m = lane & 15, kb = lane >> 4;
     const unsigned voff = SWZ ? (unsigned)((lane & 7) * ld2 + (lane >> 3) * 16) : (unsigned)((lane >> 3) * ld2 + (lane & 7) * 16); // tile piece i: 8 columns x the stage's 128 bytes
-    unsigned doff[NDP];                                                                // digit piece j: planes 2 j + lane / 32 (clamped), chunk lane % 32 of the stage's 512 bytes
-#pragma unroll
-    for (int j = 0; j < NDP; j++)
-        doff[j] = SWZ ? (unsigned)(min(lane & 7, HB_ND - 1) * ld + (8 * j + (lane >> 3)) * 16) : (unsigned)(min(2 * j + (lane >> 5), HB_ND - 1) * ld + (lane & 31) * 16);
+    const unsigned doff = (unsigned)(min(m, HB_ND - 1) * ld + kb * 64); // this lane's digits: plane m, 64 bytes at 256 h + 64 kb of the stage's 512
+    const unsigned long long dact = 0x007f007f007f007full;              // the lanes that load digits: m < HB_ND
+    static_assert(HB_ND == 7, "dact marks seven planes");
     const unsigned lds0 = (unsigned)(uintptr_t)smem;
     auto uni_p = [](const int8_t *p) {
         const unsigned long long u = (unsigned long long)(uintptr_t)p;
         return reinterpret_cast<const int8_t *>((uintptr_t)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(u >> 32)) << 32) |
                                                             (unsigned)__builtin_amdgcn_readfirstlane((int)u)));
     };
+    // one stage into slot buf of both rings: PER operations on the wave's vmcnt queue (the genotypes non-temporal, the digits — re-read by every wave —
+    // cached: they stay in L2). buf is a constant wherever this is called (the stage loop is unrolled RING times): one branch remains.
     auto issue = [&](int st, int buf) {
         const int8_t *xs = uni_p(reinterpret_cast<const int8_t *>(xg) + (int64_t)st * 128);
         const int8_t *ds = uni_p(v.rq + (int64_t)st * 512);
-        const unsigned dst = (unsigned)__builtin_amdgcn_readfirstlane((int)(lds0 + (unsigned)buf * BUF));
+        const unsigned dst = (unsigned)__builtin_amdgcn_readfirstlane((int)(lds0 + (unsigned)buf * XB));
 #pragma unroll
         for (int i = 0; i < NXP; i++) hbq_dma16<true>(voff, xs + (int64_t)(8 * i) * ld2, dst + i * XSL);
-#pragma unroll
-        for (int j = 0; j < NDP; j++) hbq_dma16<false>(doff[j], ds, dst + XB + j * 1024);
+        if (buf == 0) q2m_load_digits<0>(doff, ds, dact);
+        else if (buf == 1) q2m_load_digits<1>(doff, ds, dact);
+        else q2m_load_digits<2>(doff, ds, dact);
+    };
+    // the counted wait for the stage in slot buf, ahead stages behind it staying outstanding, and its digits
+    auto take = [&](int buf, int ahead, hb_v4i (&B)[2][4]) {
+        auto in_slot = [&](auto slot) {
+            constexpr int S = decltype(slot)::value;
+            if (ahead >= 2) q2m_take_digits<S, 2 * PER>(B);
+            else if (ahead == 1) q2m_take_digits<S, PER>(B);
+            else q2m_take_digits<S, 0>(B);
+        };
+        if (buf == 0) in_slot(std::integral_constant<int, 0>());
+        else if (buf == 1) in_slot(std::integral_constant<int, 1>());
+        else in_slot(std::integral_constant<int, 2>());
     };
     hb_v4i C[4][NSC];
 #pragma unroll
     for (int ct = 0; ct < 4; ct++)
 #pragma unroll
         for (int k = 0; k < NSC; k++) C[ct][k] = hb_v4i{0, 0, 0, 0};
-    const int n = min(m, HB_ND - 1);
-    // operand reads: column 16 ct + m = piece 2 ct + (m >> 3), row (m & 7) of it, chunk 4 h + kb; digits of plane n: piece n / 2, lane slot (n & 1) * 32 + 16 h + 4 kb + r
-    // (+ 4 h chunks for the second half; SWZ: a chunk step is 8 slots)
+    // operand reads: column 16 ct + m = piece 2 ct + (m >> 3), row (m & 7) of it, chunk 4 h + kb (+ 4 h chunks for the second half; SWZ: a chunk step is 8 slots)
     const unsigned xlane = SWZ ? (unsigned)((m >> 3) * XSL + (kb * 8 + (m & 7)) * 16) : (unsigned)((m >> 3) * XSL + ((m & 7) * 8 + kb) * 16);
-    const unsigned dlane = SWZ ? (unsigned)(XB + n * 16) : (unsigned)(XB + (n >> 1) * 1024 + ((n & 1) * 32 + 4 * kb) * 16);
+    // (the zeros of a slot go ahead of its first request, so that the first stage leaves at once and the rest is written while it travels)
+    q2m_zero_digits<0>();
+    issue(st0, 0);
+    q2m_zero_digits<1>();
+    if (st0 + 1 < st1) issue(st0 + 1, 1);
+    q2m_zero_digits<2>();
+    for (int sb = st0; sb < st1; sb += RING) {
 #pragma unroll
-    for (int a = 0; a < Q2M_NBUF - 1; a++)
-        if (st0 + a < st1) issue(st0 + a, a);
-    int buf = 0;
-    for (int st = st0; st < st1; ++st) {
-        if (st + Q2M_NBUF - 1 < st1) issue(st + Q2M_NBUF - 1, (buf + Q2M_NBUF - 1) % Q2M_NBUF);
-        const int ahead = min(Q2M_NBUF - 1, st1 - 1 - st);
-        if (ahead >= 5) asm volatile("s_waitcnt vmcnt(%0)" ::"i"(Q2M_NBUF > 5 ? 5 * PER : 0) : "memory");
-        else if (ahead == 4) asm volatile("s_waitcnt vmcnt(%0)" ::"i"(Q2M_NBUF > 4 ? 4 * PER : 0) : "memory");
-        else if (ahead == 3) asm volatile("s_waitcnt vmcnt(%0)" ::"i"(Q2M_NBUF > 3 ? 3 * PER : 0) : "memory");
-        else if (ahead == 2) asm volatile("s_waitcnt vmcnt(%0)" ::"i"(Q2M_NBUF > 2 ? 2 * PER : 0) : "memory");
-        else if (ahead == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"i"(PER) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const char *bp = smem + buf * BUF;
+      for (int u = 0; u < RING; u++) { // stage sb + u lives in slot u of both rings
+        const int st = sb + u;
+        if (st >= st1) break;
+        if (st + RING - 1 < st1) issue(st + RING - 1, (u + RING - 1) % RING);
+        // stages still in flight behind this one: the counted wait lets exactly those stay outstanding (vector-memory loads, the DMA pieces among
+        // them, leave the counter in the order they were issued)
+        hb_v4i B[2][4];
+        take(u, min(RING - 1, st1 - 1 - st), B);
+        const char *bp = smem + u * XB;
 #pragma unroll
         for (int h = 0; h < 2; h++) {
-            hb_v4i D[4];
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const int ch = 16 * h + 4 * kb + r; // SWZ: chunk ch of the stage = piece ch / 8, slot (ch % 8) * 8 + plane
-                D[r] = SWZ ? *reinterpret_cast<const hb_v4i *>(bp + dlane + (ch >> 3) * 1024 + (ch & 7) * 128) : *reinterpret_cast<const hb_v4i *>(bp + dlane + (16 * h + r) * 16);
-            }
-            const hb_v4i B0 = hb_v4i{D[0].x, D[1].x, D[2].x, D[3].x}, B1 = hb_v4i{D[0].y, D[1].y, D[2].y, D[3].y},
-                         B2 = hb_v4i{D[0].z, D[1].z, D[2].z, D[3].z}, B3 = hb_v4i{D[0].w, D[1].w, D[2].w, D[3].w};
+            const hb_v4i B0 = B[h][0], B1 = B[h][1], B2 = B[h][2], B3 = B[h][3];
 #pragma unroll
             for (int ct = 0; ct < 4; ct++) {
                 const hb_v4i w = *reinterpret_cast<const hb_v4i *>(bp + 2 * ct * XSL + xlane + (SWZ ? 4 * h * 128 : 4 * h * 16));
@@ -421,10 +514,11 @@ __device__ __forceinline__ void dotq2m512_tile(const dq_view &v, char *smem, int
                 }
             }
         }
+        // (the next step's DMA overwrites the buffer read here: every LDS read of it has returned — the MFMAs consumed them)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        buf = (buf + 1 == Q2M_NBUF) ? 0 : buf + 1;
+      }
     }
-    int *tr = reinterpret_cast<int *>(smem); // [plane][64 columns]
+    int *tr = reinterpret_cast<int *>(smem); // [plane][64 columns] (the head of the genotype ring: every stage has landed and been read)
     if (m < HB_ND) {
 #pragma unroll
         for (int ct = 0; ct < 4; ct++) {
