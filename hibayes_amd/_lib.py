@@ -137,6 +137,14 @@ class EpslOut(C.Structure):
     ]
 
 
+class ImputeStats(C.Structure):
+    """hb_impute_stats: what one hb_impute_solve reports"""
+    _fields_ = [
+        ("width", C.c_int32), ("iterations", C.c_int32), ("blocks", C.c_int32), ("parts", C.c_int32), ("cached", C.c_int32), ("looks", C.c_int32),
+        ("max_residual", C.c_double), ("seconds", C.c_double), ("product_seconds", C.c_double), ("product_bytes", C.c_int64),
+    ]
+
+
 class SBayesArgs(C.Structure):
     _fields_ = [
         ("m", C.c_int32), ("sumstat", C.c_void_p), ("ld_sumstat", C.c_int64), ("ldm", C.c_void_p), ("ld_ldm", C.c_int64),
@@ -271,6 +279,8 @@ SYMBOLS = [
     # ssbrm(): the epsilon block src/Bayes.cpp:554-584, Gibbs() src/solver.cpp:131-140 (hb_epsl.hip)
     "hb_ctx_epsl_setup", "hb_ctx_epsl_step", "hb_ctx_epsl_state", "hb_ctx_epsl_debug_get", "hb_ctx_epsl_debug_set",
     "hb_epsl_check", "hb_epsl_plan", "hb_bayes_run_epsl", "hb_run_epsl", "hb_run_epsl_store",
+    # ssbrm()'s imputation, R/ssbayes.r:295-307, as a batched conjugate-gradient solve (hb_impute.hip)
+    "hb_impute_create", "hb_impute_solve", "hb_impute_destroy",
 ]
 
 
@@ -409,6 +419,10 @@ def lib():
     L.hb_bayes_run_epsl.argtypes = [C.POINTER(BayesArgs), C.POINTER(BayesOut), C.POINTER(PolyOut), C.POINTER(EpslOut)]
     L.hb_run_epsl.argtypes = [vp, C.POINTER(EpslOut)]
     L.hb_run_epsl_store.argtypes = [vp, i32]
+    L.hb_impute_create.argtypes = [i32, vp, vp, vp, i32, i32, vp, vp, vp, i32, C.POINTER(vp)]
+    L.hb_impute_solve.argtypes = [vp, vp, i64, i32, dbl, i32, vp, i64, C.POINTER(ImputeStats)]
+    L.hb_impute_destroy.argtypes = [vp]
+    L.hb_impute_destroy.restype = None
     L.hb_eig_upload.argtypes = [vp, i64, i32, i32, C.POINTER(vp), C.POINTER(i64)]
     L.hb_eig_reduce.argtypes = [vp, i64, i32, i32, vp, vp, C.POINTER(vp)]
     L.hb_eig_tau.argtypes = [vp, vp]

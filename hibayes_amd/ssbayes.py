@@ -190,11 +190,17 @@ def make_Ainv(s, d, one_parent="reference"):
 # --------------------------------------------------------------------------------------------
 # ssbrm(), R/ssbayes.r:115-351
 # --------------------------------------------------------------------------------------------
-def ssbrm_prepare(formula, data=None, M=None, M_id=None, pedigree=None, maf=0.01, one_parent="reference", chunk=512, verbose=False):
-    """ssbrm() up to the call of Bayes() (R/ssbayes.r:225-319), on the host: the formula, the ids, the pedigree, A^-1, the imputation
-    Mn = solve(A^-1_nn, -A^-1_ng M) through one sparse LU factor in chunks of `chunk` marker columns, Jn, and the stacking — genotyped
-    records first, then the non-genotyped ones. Returns a dict; nothing here touches a device."""
+def ssbrm_prepare(formula, data=None, M=None, M_id=None, pedigree=None, maf=0.01, one_parent="reference", chunk=512, verbose=False, *,
+                  impute="host", impute_tol=1e-12, device=0):
+    """ssbrm() up to the call of Bayes() (R/ssbayes.r:225-319): the formula, the ids, the pedigree, A^-1, the imputation
+    Mn = solve(A^-1_nn, -A^-1_ng M) in chunks of `chunk` marker columns, Jn, and the stacking — genotyped records first, then the
+    non-genotyped ones. Returns a dict.
+    `impute="host"` (default): one sparse LU factor on the host; nothing touches a device. `impute="device"`: a batched conjugate-gradient
+    solve on `device` (impute_device(), hb_impute.hip) to the relative residual `impute_tol`, J as one more column of the last chunk — no
+    factor, so it reaches pedigrees whose factor does not fit; the dict then also has "impute_stats"."""
     import re
+    if impute not in ("host", "device"):
+        raise ValueError("impute must be \"host\" or \"device\", not %r" % (impute,))
     import scipy.sparse as sp
     from scipy.sparse.linalg import splu
     if data is None:
@@ -294,15 +300,37 @@ def ssbrm_prepare(formula, data=None, M=None, M_id=None, pedigree=None, maf=0.01
     Ai_nn.sort_indices()
     import time
     t0 = time.perf_counter()
-    # (A^-1_nn is symmetric positive definite: a minimum-degree ordering of its own pattern and pivots on the diagonal keep the factor sparse)
-    lu = splu(Ai_nn, permc_spec="MMD_AT_PLUS_A", diag_pivot_thresh=0.0, options=dict(SymmetricMode=True))
     m = M.shape[1]
     Mn = np.empty((len(Mn_id), m), dtype=np.float64, order="F")
-    for c0 in range(0, m, int(chunk)):
-        c1 = min(m, c0 + int(chunk))
-        Mn[:, c0:c1] = lu.solve(-(Ai_ng @ M[:, c0:c1]))
     J = np.full(len(M_id), -1.0)
-    Jn = lu.solve(-(Ai_ng @ J))
+    impute_stats = None
+    if impute == "host":
+        # (A^-1_nn is symmetric positive definite: a minimum-degree ordering of its own pattern and pivots on the diagonal keep the factor sparse)
+        lu = splu(Ai_nn, permc_spec="MMD_AT_PLUS_A", diag_pivot_thresh=0.0, options=dict(SymmetricMode=True))
+        for c0 in range(0, m, int(chunk)):
+            c1 = min(m, c0 + int(chunk))
+            Mn[:, c0:c1] = lu.solve(-(Ai_ng @ M[:, c0:c1]))
+        Jn = lu.solve(-(Ai_ng @ J))
+    else:
+        from .impute import ImputeSystem
+        ck = max(1, int(chunk))
+        starts = list(range(0, m, ck)) or [0]
+        with ImputeSystem(Ai_nn, Ai_ng, device) as S:
+            for c0 in starts:
+                c1 = min(m, c0 + ck)
+                if c0 != starts[-1]:
+                    _, st = S.solve(M[:, c0:c1], impute_tol, out=Mn[:, c0:c1])
+                else:  # the last chunk takes J with it
+                    last, st = S.solve(np.asfortranarray(np.column_stack([M[:, c0:c1], J])), impute_tol)
+                    Mn[:, c0:c1] = last[:, :c1 - c0]
+                    Jn = np.ascontiguousarray(last[:, c1 - c0])
+                if impute_stats is None:
+                    impute_stats = st
+                else:
+                    for f in ("iterations", "max_residual", "product_seconds"):
+                        impute_stats[f] = max(impute_stats[f], st[f])
+                    for f in ("blocks", "looks", "seconds"):
+                        impute_stats[f] += st[f]
     impute_seconds = time.perf_counter() - t0
 
     # ---- the stacking, :310-319 ----
@@ -321,16 +349,18 @@ def ssbrm_prepare(formula, data=None, M=None, M_id=None, pedigree=None, maf=0.01
         "M": M, "Mn": Mn, "J": J, "Jn": Jn, "M_id": M_id, "Mn_id": Mn_id, "y_id": y_id, "y_id_comb": comb, "y_indx": y_indx,
         "n_genotyped_records": len(g_rec), "n_other_records": len(n_rec), "fixed_names": fixed_names, "rand_terms": list(rand_terms),
         "lhs": lhs, "rhs": rhs, "impute_seconds": impute_seconds,
+        **({} if impute_stats is None else {"impute_stats": impute_stats}),
     }
 
 
 def ssbrm(formula, data=None, M=None, M_id=None, pedigree=None, method="BayesCpi", map=None, Pi=None, fold=None, niter=None, nburn=None, thin=5,
           windsize=None, windnum=None, maf=0.01, dfvr=None, s2vr=None, vg=None, dfvg=None, s2vg=None, ve=None, dfve=None, s2ve=None,
           printfreq=100, seed=666666, threads=4, verbose=True, *, windindx=None, device=0, panel=0, store_alpha=True, store_epsilon=True,
-          gebv_samples=False, one_parent="reference", chunk=512):
+          gebv_samples=False, one_parent="reference", chunk=512, impute="host", impute_tol=1e-12):
     """Mirror of ssbrm() (reference R/ssbayes.r:115-351), with ibrm()'s conventions for `formula`, `data` and the keyword extras: the
     single-step model for a population of which only a part is genotyped. `pedigree`: three columns (id, sire, dam). The non-genotyped
-    individuals' genotypes are imputed from the pedigree on the host (set-up), the fit runs on the fp64 resident layout with the epsilon
+    individuals' genotypes are imputed from the pedigree in the set-up — on the host through a sparse factor, or with `impute="device"` by a
+    batched conjugate-gradient solve on the device (ssbrm_prepare()) —, the fit runs on the fp64 resident layout with the epsilon
     block — J, the Gibbs pass over the non-genotyped individuals, the variance of epsilon — on the device.
     Returns Bayes()'s fields plus Veps, J, epsilon {"id", "epsilon"}, g {"id", "gebv"} over the genotyped, then the non-genotyped
     individuals (the linear form of :325 applied to the posterior means; `gebv_samples=True` also returns the full MCMCsamples["g"]) and
@@ -371,7 +401,8 @@ def ssbrm(formula, data=None, M=None, M_id=None, pedigree=None, method="BayesCpi
                 fold = [0, 0.0001, 0.001, 0.01]
         else:
             Pi = [0.95, 0.05]
-    pr = ssbrm_prepare(formula, data, M, M_id, pedigree, maf=maf, one_parent=one_parent, chunk=chunk, verbose=verbose)
+    pr = ssbrm_prepare(formula, data, M, M_id, pedigree, maf=maf, one_parent=one_parent, chunk=chunk, verbose=verbose, impute=impute,
+                       impute_tol=impute_tol, device=device)
     has_eps = pr["n_other_records"] > 0
     kw = dict(y=pr["y"], X=pr["y_M"], model=method, Pi=Pi, fold=fold, C_=pr["X"], R=pr["R"], niter=niter, nburn=nburn, thin=thin, windindx=windindx,
               dfvr=dfvr, s2vr=s2vr, vg=vg, dfvg=dfvg, s2vg=s2vg, ve=ve, dfve=dfve, s2ve=s2ve, outfreq=printfreq, threads=threads, verbose=verbose,
@@ -415,4 +446,6 @@ def ssbrm(formula, data=None, M=None, M_id=None, pedigree=None, method="BayesCpi
     res["call"] = "%s ~ %s + J + M[pedigree]" % (pr["lhs"], pr["rhs"])
     res["model"] = "Single-step Bayesian model fit by [%s]" % method
     res["timing"]["impute_seconds"] = pr["impute_seconds"]
+    if "impute_stats" in pr:
+        res["timing"]["impute_stats"] = pr["impute_stats"]
     return res

@@ -727,6 +727,37 @@ int hb_ctx_epsl_state(hb_ctx *c, double *x, double *veps, double *q, double *J);
 int hb_ctx_epsl_debug_get(hb_ctx *c, double *b, double *x_old, double *rhs, int32_t *counts);
 int hb_ctx_epsl_debug_set(hb_ctx *c, int32_t sched_mode, int32_t row_mode);
 
+/* ssbrm()'s imputation on the device (R/ssbayes.r:295-307: Mn = solve(A^-1_nn, -A^-1_ng M), Jn beside it) without a factor: a batched
+ * conjugate-gradient solve with the Jacobi preconditioner, hb_impute.hip, DESIGN.md section 19. Additive under ABI 6.
+ * create (R/ssbayes.r:295-307, the two blocks of A^-1): A_nn, q x q, as canonical CSC with BOTH triangles stored, and A_ng, ng_rows x n_g, as
+ * canonical CSR, both 0-based. Validated before any device call, each case with its own text (HB_ERR_INVALID): indptr from 0 and not
+ * decreasing; indices sorted, unique and in range; finite values; ng_rows == q; a positive diagonal of A_nn; A_nn equal to its transpose in
+ * pattern and in value bits. Then the matrices are copied to `device`; without one: HB_ERR_NO_DEVICE, as every compute entry point. */
+typedef struct hb_impute hb_impute;
+int hb_impute_create(int32_t q, const int64_t *nn_indptr, const int32_t *nn_indices, const double *nn_data, int32_t ng_rows, int32_t n_g,
+                     const int64_t *ng_indptr, const int32_t *ng_indices, const double *ng_data, int32_t device, hb_impute **out);
+typedef struct hb_impute_stats {
+    int32_t width;          /* W: right-hand sides per block, a multiple of 64 (hb_imputeplan.hpp)                          */
+    int32_t iterations;     /* until every column had stopped; the largest over the blocks                                  */
+    int32_t blocks;         /* blocks of W columns solved one after the other                                               */
+    int32_t parts;          /* partial sums per column: a function of q alone                                               */
+    int32_t cached;         /* the plan expects the block of search directions to stay in the Infinity Cache                */
+    int32_t looks;          /* host looks at the stop words                                                                 */
+    double max_residual;    /* largest ||b - A_nn x|| / ||b|| over the columns, from one more product after the stop         */
+    double seconds;         /* wall time of the call                                                                        */
+    double product_seconds; /* HB_IMPUTE_PROFILE set: one launch of the product kernel alone, averaged over ten; else 0     */
+    int64_t product_bytes;  /* bytes one launch of the product kernel moves at this width                                   */
+} hb_impute_stats;
+/* solve (R/ssbayes.r:295-307, a chunk of columns): M, n_g x ncols column-major with leading dimension ld, into Mn, q x ncols column-major
+ * with leading dimension ld_out. A column stops at the first iteration with ||r|| <= tol ||b|| and is frozen there; a column with b = 0 is
+ * exactly 0. tol outside (0, 1) or max_iter < 1: HB_ERR_INVALID (checked first). A column still live after max_iter iterations, or p'Ap <= 0:
+ * HB_ERR_INVALID with the count in the text, and Mn is not a result. stats may be NULL. Two calls give the same bits, and a column's bits do
+ * not depend on the columns solved beside it. */
+int hb_impute_solve(hb_impute *h, const double *M, int64_t ld, int32_t ncols, double tol, int32_t max_iter, double *Mn, int64_t ld_out,
+                    hb_impute_stats *stats);
+/* destroy (R/ssbayes.r:295-307 needs the matrices no longer): frees the device copies; NULL is allowed */
+void hb_impute_destroy(hb_impute *h);
+
 /* One marker sweep (reference src/Bayes.cpp:586-816) plus the two reductions behind
  * :819 and :823.  Hyper-parameters come from the host, per-SNP draws happen on device. */
 typedef struct hb_sweep_in {

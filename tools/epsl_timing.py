@@ -6,6 +6,8 @@ set-up (one sparse LU factor of A^-1_nn, solves in column chunks) on the same pe
 
     python tools/epsl_timing.py [--q 100000 1000000] [--shapes 5x4 20x4 20x40 80x4] [--out profiles/epsl_timing.txt]
     python tools/epsl_timing.py --impute-only ...        (no GPU needed: the imputation's part alone)
+    python tools/epsl_timing.py --impute-device --q 20000 100000 1000000 --out profiles/impute_timing.txt
+                                                         (the device imputation, hb_impute.hip; up to --host-max beside the host's)
 
 A pedigree of `generations x family`: founders, then generations of equal size in which every sire of the previous generation has `family`
 offspring with dams drawn at random from it; the last-but-one tenth of the youngest generation is genotyped, a tenth of the rest of it has a
@@ -44,8 +46,11 @@ extern "C" void epsl_pass(int q, const int64_t *indptr, const int32_t *indices, 
 """
 
 
-def pedigree(total, generations, family, seed):
-    """(s, d): 1-based parents, parents first; `generations` generations after the founders, every one of total / (generations + 1)"""
+def pedigree(total, generations, family, seed, selfing=True):
+    """(s, d): 1-based parents, parents first; `generations` generations after the founders, every one of total / (generations + 1).
+    selfing=False draws the dams from the individuals that are not sires: no offspring then has one individual as both parents. (With the
+    default about one offspring in a thousand has, make_Ainv() gives that parent the reference's 1.5 where Henderson's rule has 2, and
+    A^-1_nn is no longer positive definite — the Gibbs pass does not mind, conjugate gradients do.)"""
     rng = np.random.default_rng(seed)
     size = max(2 * family, total // (generations + 1))
     s, d = [np.zeros(size, dtype=np.int64)], [np.zeros(size, dtype=np.int64)]
@@ -55,9 +60,70 @@ def pedigree(total, generations, family, seed):
         nsire = max(1, size // family)
         sires = rng.choice(prev, nsire, replace=False)
         s.append(np.repeat(sires, family)[:size] if nsire * family >= size else np.resize(np.repeat(sires, family), size))
-        d.append(rng.choice(prev, size))
+        d.append(rng.choice(prev if selfing else np.setdiff1d(prev, sires), size))
         first += size
     return np.concatenate(s), np.concatenate(d), size
+
+
+def impute_device_leg(a, say):
+    """The device imputation on the generated pedigrees (without selfing: see pedigree()): set-up (validation and upload) and solve, per block
+    width and column count; up to --host-max individuals also the host's route — the LU factor and its solve — on the same systems and columns.
+    Times are host clocks around calls that end in a synchronisation; the product kernel alone is timed by the library with device events
+    (HB_IMPUTE_PROFILE), its bytes are counted from the shapes: a row of W doubles per stored entry, Ap written, the matrix read."""
+    from hibayes_amd.impute import ImputeSystem
+    from scipy.sparse.linalg import splu
+    os.environ["HB_IMPUTE_PROFILE"] = "1"
+    if H.lib().hb_device_count() < 1:
+        raise SystemExit("epsl_timing.py --impute-device: no HIP device visible")
+    for total in a.q:
+        for shape in a.shapes:
+            gens, fam = [int(v) for v in shape.split("x")]
+            s, d, size = pedigree(total, gens, fam, 1, selfing=False)
+            N = s.size
+            geno = np.arange(N - size, N - size + size // 10)
+            is_g = np.zeros(N, dtype=bool)
+            is_g[geno] = True
+            Ai = H.make_Ainv(s, d, one_parent="henderson").tocsr()
+            n_indx = np.flatnonzero(~is_g)
+            Ann = Ai[n_indx][:, n_indx].tocsc()
+            Ann.sort_indices()
+            Ang = Ai[n_indx][:, geno].tocsr()
+            Ang.sort_indices()
+            q = Ann.shape[0]
+            say("pedigree %d x %d of %d: q_e = %d, %d genotyped, %d stored entries in A^-1_nn, %d in A^-1_ng; tol = %g"
+                % (gens, fam, N, q, geno.size, Ann.nnz, Ang.nnz, a.impute_tol))
+            lu = None
+            if q <= a.host_max:
+                t0 = time.perf_counter()
+                lu = splu(Ann, permc_spec="MMD_AT_PLUS_A", diag_pivot_thresh=0.0, options=dict(SymmetricMode=True))
+                say("    host: LU factor %.2f s (%d + %d stored entries in L + U)" % (time.perf_counter() - t0, lu.L.nnz, lu.U.nnz))
+            for cols in a.impute_cols_list:
+                M = np.asfortranarray(np.random.default_rng(2).integers(0, 3, size=(geno.size, cols)).astype(np.float64))
+                t0 = time.perf_counter()
+                with ImputeSystem(Ann, Ang) as S:
+                    t_setup = time.perf_counter() - t0
+                    S.solve(M[:, :1], a.impute_tol, 20000)  # (the first launches load the code object)
+                    runs = []
+                    for rep in range(a.impute_reps):
+                        x, st = S.solve(M, a.impute_tol, 20000)
+                        runs.append(st["seconds"])
+                best = min(runs)
+                say("    device, %d columns: set-up %.3f s, solve %.4f s (%s) = %.3f ms per column; W = %d, %d block(s), %d iterations, %d looks, p %s "
+                    "the cache rule; largest true residual %.3g" % (cols, t_setup, best, " ".join("%.4f" % r for r in runs), 1e3 * best / cols, st["width"],
+                                                                    st["blocks"], st["iterations"], st["looks"], "within" if st["cached"] else "beyond",
+                                                                    st["max_residual"]))
+                say("        = %.1f us per iteration of a block (three launches); the product kernel alone %.1f us per launch, %.1f MB counted: %.2f TB/s"
+                    % (1e6 * best / max(1, st["blocks"] * st["iterations"]), 1e6 * st["product_seconds"], st["product_bytes"] / 1e6,
+                       st["product_bytes"] / max(st["product_seconds"], 1e-12) / 1e12))
+                if lu is not None:
+                    t0 = time.perf_counter()
+                    xh = lu.solve(-(Ang @ M))
+                    t_solve = time.perf_counter() - t0
+                    say("        host solve of the same columns %.3f s = %.2f ms per column; largest |device - host| %.3g (largest |host| %.3g)"
+                        % (t_solve, 1e3 * t_solve / cols, float(np.max(np.abs(x - xh))), float(np.max(np.abs(xh)))))
+                    del xh
+                del x, M
+            del lu
 
 
 def main():
@@ -70,6 +136,11 @@ def main():
     ap.add_argument("--impute-cols", type=int, default=64)
     ap.add_argument("--impute-only", action="store_true")
     ap.add_argument("--no-impute", action="store_true")
+    ap.add_argument("--impute-device", action="store_true", help="the device imputation's leg alone")
+    ap.add_argument("--impute-cols-list", type=int, nargs="+", default=[64, 512])
+    ap.add_argument("--impute-tol", type=float, default=1e-12)
+    ap.add_argument("--impute-reps", type=int, default=2)
+    ap.add_argument("--host-max", type=int, default=25000, help="largest q_e at which the host's factor is run beside the device")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     lines = []
@@ -79,6 +150,12 @@ def main():
         lines.append(t)
 
     say("command: python tools/epsl_timing.py " + " ".join(sys.argv[1:]))
+    if a.impute_device:
+        impute_device_leg(a, say)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     gpu = not a.impute_only
     if gpu and H.lib().hb_device_count() < 1:
         raise SystemExit("epsl_timing.py: no HIP device visible (--impute-only needs none)")
