@@ -53,8 +53,6 @@ struct hb_comm {
     int rank = 0, world = 1, device = 0;
 };
 
-int hb_comm_allreduce_f64(hb_comm *c, double *buf, size_t count, hipStream_t st);
-
 extern "C" {
 
 int hb_comm_unique_id(void *id128)

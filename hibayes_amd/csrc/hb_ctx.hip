@@ -11,32 +11,6 @@
 #include <mutex>
 #include <unordered_set>
 
-// launch wrappers implemented in hb_kernels.hip
-int hbk_init_attrs();
-int hbk_stats(hb_ctx *c);
-int hbk_dot_all(hb_ctx *c);
-int hbk_dot_panels(hb_ctx *c, int reps);
-int hbk_reduce_ru(hb_ctx *c);
-int hbk_shift(hb_ctx *c, double a);
-int hbk_to_f32(hb_ctx *c);
-int hbk_cov_dot(hb_ctx *c, int i, double *dev_out);
-int hbk_cov_axpy(hb_ctx *c, int i, double a);
-int hbk_level_sums(hb_ctx *c, int term, double *dev_sums, int nlev);
-int hbk_level_axpy(hb_ctx *c, int term, const double *dev_delta);
-int hbk_windows(hb_ctx *c);
-int hbk_f64_to_i8(hb_ctx *c, const double *dsrc, int64_t lds, int ncols, int8_t *dst, int *dbad);
-int hbk_bed_decode(hb_ctx *c, const uint8_t *dbed, int64_t bpc, int nind, const int32_t *drows, int col0, int ncols);
-int hbk_generate(hb_ctx *c, uint64_t seed, int mono_every);
-int hbk_xalpha(hb_ctx *c, const double *dev_alpha, double *dev_out);
-int hbk_time_matvec(hb_ctx *c, int D, int reps, int as_pipeline, double *avg_us, int *launches);
-int hbk_probe_concurrency(hb_ctx *c, int *concurrent);
-int hbk_cov_step(hb_ctx *c, int i, double v, double vare, double z, double *beta_i);
-int hbk_lev_step(hb_ctx *c, int term, int q0, int qr, const double *zz, double *estR, const double *z, double vare, double *vrtmp,
-                 double *vr, double s2r_dfr, double chis);
-int hbk_xmat(hb_ctx *c, const int *didx, const double *dval, int nnz, double *dout);
-int hbk_pack2(hb_ctx *c);
-int hbk_unpack2(hb_ctx *c, int col0, int ncols, int8_t *dst);
-
 static thread_local std::string g_err;
 
 // contexts that were given genotypes (upload / decode / generate): hb_ldm_build refuses the others before any device work
@@ -683,6 +657,13 @@ int hb_ctx_switch_geometry(hb_ctx *c, int32_t pipeline, int32_t lookahead, int32
     // the stored band serves every geometry whose band fits into it (the captured sweeps are cached per geometry)
     if (c->L > c->Lg) c->gram_ready = false;
     return HB_OK;
+}
+int hb_ctx_force_geometry(hb_ctx *c, int32_t pipeline, int32_t lookahead, int32_t dotgroup)
+{
+    c->force_geometry = true;
+    const int rc = hb_ctx_switch_geometry(c, pipeline, lookahead, dotgroup);
+    c->force_geometry = false;
+    return rc;
 }
 extern "C" {
 

@@ -71,8 +71,6 @@ __global__ __launch_bounds__(1024) void k_gram_tiled(const int8_t *__restrict__ 
             }
 }
 
-int hbk_unpack2(hb_ctx *c, int col0, int ncols, int8_t *dst);
-
 // panels [pa, pb) of the band; Xv = where column 0 WOULD be (a window of the matrix may be all that exists: only the columns of
 // panels pa - Lg .. pb - 1 are read)
 static int gram_launch(hb_ctx *c, const int8_t *Xv, int pa, int pb)

@@ -26,8 +26,6 @@
 #include <cstdio>
 #include <cstring>
 
-int hbk_stats(hb_ctx *c);
-
 struct hb_poly {
     int n = 0;
     int64_t ld = 0;          // leading dimension of K in doubles, even

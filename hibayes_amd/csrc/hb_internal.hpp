@@ -244,7 +244,7 @@ struct hb_ctx {
     int timeout_ms = 3000;           // a device-side wait gives up after this long. 3 s for whoever drives the context directly (hb_ctx_sweep:
                                      // nothing replays an aborted sweep there); hb_run_step, which does replay, runs its sweeps with 100 ms
     bool timeout_env = false;        // HB_TIMEOUT_MS given: that value everywhere, hb_run_step does not shorten it
-    bool force_geometry = false;     // hb_run_step's fall-back to the per-panel kernels: hb_ctx_set_pipeline ignores env_pinned while set
+    bool force_geometry = false;     // hb_run_step's fall-back to the per-panel kernels (hb_ctx_force_geometry): hb_ctx_set_pipeline ignores env_pinned while set
     int inject_abort_panel = -1;     // debug hook (hb_ctx_debug_inject_abort): the next sweeps are aborted once chain_done reaches this panel
     int inject_abort_times = 0;
     hipStream_t s_dbg = nullptr;
@@ -255,12 +255,42 @@ struct hb_ctx {
 
 extern "C" int hb_ctx_snapshot(hb_ctx *c, int model_index, bool store, bool count_pip);
 extern "C" int hb_ctx_restore(hb_ctx *c);
-int hbk_set_timeout(hb_ctx *c);
+// launch wrappers implemented in hb_kernels.hip and the headers it includes: each declared here and nowhere else
+int hbk_init_attrs();
+int hbk_probe_concurrency(hb_ctx *c, int *concurrent);
+int hbk_stats(hb_ctx *c);
+int hbk_dot_all(hb_ctx *c);
+int hbk_dot_panels(hb_ctx *c, int reps);
+int hbk_reduce_ru(hb_ctx *c);
+int hbk_shift(hb_ctx *c, double a);
+int hbk_to_f32(hb_ctx *c);
+int hbk_cov_dot(hb_ctx *c, int i, double *dev_out);
+int hbk_cov_axpy(hb_ctx *c, int i, double a);
+int hbk_level_sums(hb_ctx *c, int term, double *dev_sums, int nlev);
+int hbk_level_axpy(hb_ctx *c, int term, const double *dev_delta);
+int hbk_cov_step(hb_ctx *c, int i, double v, double vare, double z, double *beta_i);
+int hbk_lev_step(hb_ctx *c, int term, int q0, int qr, const double *zz, double *estR, const double *z, double vare, double *vrtmp,
+                 double *vr, double s2r_dfr, double chis);
+int hbk_windows(hb_ctx *c);
+int hbk_f64_to_i8(hb_ctx *c, const double *dsrc, int64_t lds, int ncols, int8_t *dst, int *dbad);
+int hbk_bed_decode(hb_ctx *c, const uint8_t *dbed, int64_t bpc, int nind, const int32_t *drows, int col0, int ncols);
+int hbk_generate(hb_ctx *c, uint64_t seed, int mono_every);
+int hbk_xalpha(hb_ctx *c, const double *dev_alpha, double *dev_out);
+int hbk_xmat(hb_ctx *c, const int *didx, const double *dval, int nnz, double *dout);
+int hbk_pack2(hb_ctx *c);
+int hbk_unpack2(hb_ctx *c, int col0, int ncols, int8_t *dst);
+int hbk_time_matvec(hb_ctx *c, int D, int reps, int as_pipeline, double *avg_us, int *launches);
 int hbk_time_stream_read(hb_ctx *c, int reps, double *avg_ms, int64_t *bytes);
+int hbk_set_timeout(hb_ctx *c);
 int hbk_copy_segs(hb_ctx *c, const std::vector<hb_ctx::snap_seg> &segs, bool restore);
+// the sharded exchange of one run of a sweep (hb_run.hip)
+int hbk_delta_pack(hb_ctx *c, const double *r0, const double *u0, double *buf);
+int hbk_delta_unpack(hb_ctx *c, const double *r0, const double *u0, const double *buf);
+int hbk_abort_poison(hb_ctx *c, double *sums);
 
 int hb_sweep_enqueue(hb_ctx *c, const hb_sweep_in *in, bool timed);
 int hb_ctx_switch_geometry(hb_ctx *c, int32_t pipeline, int32_t lookahead, int32_t dotgroup); // hb_ctx_set_pipeline without touching home_lv / home_d (hb_run's per-sweep choice)
+int hb_ctx_force_geometry(hb_ctx *c, int32_t pipeline, int32_t lookahead, int32_t dotgroup);  // the same past HB_PIPELINE / HB_LOOKAHEAD / HB_DOTGROUP (hb_run's fall-back and its way back)
 extern "C" int hb_ctx_sweep_range(hb_ctx *c, const hb_sweep_in *in, int block, int nblocks);
 extern "C" int hb_ctx_sweep_begin(hb_ctx *c, const hb_sweep_in *in);
 extern "C" int hb_ctx_sweep_end(hb_ctx *c, hb_sweep_out *out);

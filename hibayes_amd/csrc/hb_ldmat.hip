@@ -23,9 +23,6 @@
 
 #pragma clang fp contract(off)
 
-int hbk_stats(hb_ctx *c);
-int hbk_unpack2(hb_ctx *c, int col0, int ncols, int8_t *dst);
-
 namespace {
 // ---- BigStat (src/tXXmat.cpp:43-77): mean = sum / ind, xx = sqrt(sum_k (x_k - mean)^2), the squares added in row order ----
 // One lane per column (set-up work: m lanes x n dependent adds). X points at column col0; the column sums are k_stats' exact

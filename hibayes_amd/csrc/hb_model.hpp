@@ -1,12 +1,13 @@
 // hb_model.hpp — the model layer that Bayes() and SBayesD() / SBayesS() of the reference share line for line, once: the model's
-// index, the checks of `Pi` and `fold` with the reference's texts, BayesR's class order, the hyper-parameter draws after a sweep,
-// the PIP rule and the summary statistics' population size. Plain C++ with nothing from HIP, so that it is tested on the CPU
+// index, the checks of `Pi` and `fold` with the reference's texts, BayesR's class order, the prior defaults, a sweep's parameters from
+// the chain's state, the hyper-parameter draws after a sweep, the progress line, the PIP rule and the summary statistics' population size. Plain C++ with nothing from HIP, so that it is tested on the CPU
 // (tests/test_model_host.py). A refusal comes back as a status with its text in `err`; the callers hand both to hb_fail.
 // hb_run.hip (individual level) and hb_sbayes.hip (summary level) interleave the three mixture checks with their other checks in
 // different orders — each calls them where it made these checks before, so an input with several faults reports the same one.
 #pragma once
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <string>
 #include <vector>
 #include "../../include/hibayes_gpu.h"
@@ -174,4 +175,76 @@ static inline int hb_sumstat_n(const double *ss, long long lds, int m)
     for (int k = 0; k < m; k++)
         if (std::isfinite(ss[3 * lds + k])) { s += ss[3 * lds + k]; c++; }
     return (int)(s / std::max(1, c));
+}
+
+// ---- prior defaults, src/Bayes.cpp:327-374 and, the same expressions, src/SBayesD.cpp:117-170 ----
+struct hb_prior_args { // the caller's has_* / value pairs, and what the run knows by now
+    int has_vg, has_ve, has_dfve, has_s2vg, has_s2ve;
+    double vg, ve, dfve, s2vg, s2ve;
+    double dfvara, vary, h2;
+    int nr;            // environmental random effects, which share the residual's half of var(y) (0 at the summary level)
+    double Pi0, sumvx;
+};
+struct hb_priors {
+    double vara, vare, dfvare, s2vara, varg, s2varg, s2vare, lambda2, lambda, shape0 = 1.1, rate0;
+};
+// vara_fold[0 .. n_fold) is filled too. The expressions are the reference's, operand for operand.
+static inline hb_priors hb_prior_defaults(const hb_prior_args &p, const double *fold, int n_fold, double *vara_fold)
+{
+    hb_priors d;
+    d.vara = p.has_vg ? p.vg : ((p.dfvara - 2) / p.dfvara) * p.vary * p.h2;
+    d.vare = p.has_ve ? p.ve : p.vary * (1 - p.h2) / (p.nr + 1);
+    d.dfvare = p.has_dfve ? p.dfve : -2;
+    d.s2vara = p.has_s2vg ? p.s2vg : d.vara * (p.dfvara - 2) / p.dfvara;
+    d.varg = d.vara / ((1 - p.Pi0) * p.sumvx);
+    d.s2varg = d.s2vara / ((1 - p.Pi0) * p.sumvx);
+    d.s2vare = p.has_s2ve ? p.s2ve : 0;
+    const double R2 = (p.dfvara - 2) / p.dfvara;
+    d.lambda2 = 2 * (1 - R2) / (R2)*p.sumvx;
+    d.lambda = std::sqrt(d.lambda2);
+    d.rate0 = (d.shape0 - 1) / d.lambda2;
+    for (int j = 0; j < n_fold; j++) vara_fold[j] = (d.vara / ((1 - p.Pi0) * p.sumvx)) * fold[j];
+    return d;
+}
+
+// ---- a sweep's parameters from the chain's state (hb_sweep_in) ----
+// Pi, fold and vara_fold have n_fold entries, in the device's class order. thin < 1: never a thinned record (the summary level keeps its records on the host).
+static inline hb_sweep_in hb_sweep_params(int model_index, int n_fold, const double *Pi, const double *fold, const double *vara_fold, double vare,
+                                          double varg, double s2varg_df, double dfvara, double lambda, double lambda2, int iter, int nburn, int thin,
+                                          bool always_in)
+{
+    hb_sweep_in in{};
+    in.model_index = model_index;
+    in.n_fold = n_fold;
+    in.iter = iter;
+    in.vare = vare;
+    in.varg = varg;
+    in.s2varg_df = s2varg_df;
+    in.dfvara = dfvara;
+    for (int j = 0; j < n_fold; j++) {
+        in.logpi[j] = std::log(Pi[j]);
+        in.fold[j] = fold[j];
+        in.vara_fold[j] = vara_fold[j];
+    }
+    in.lambda = lambda;
+    in.lambda2 = lambda2;
+    in.count_pip = (iter >= nburn) && !always_in;
+    in.store = thin >= 1 && (iter >= nburn) && ((iter + 1 - nburn) % thin == 0);
+    return in;
+}
+
+// ---- the progress line of iteration iter (0-based), src/Bayes.cpp:884-914 and src/SBayesD.cpp:514-537 ----
+// pi in the caller's class order (cls_of[]); extras: the model's own columns, preformatted with their trailing blanks (lambda for BayesL, va vb for
+// BSLMM, veps for the epsilon block); vt: the denominator of h2; seconds: spent in the loop so far, from which the time left is extrapolated
+static inline std::string hb_progress_line(int iter, int niter, long long NnzSnp, const double *Pi, const int *cls_of, int n_fold, const char *extras,
+                                           double vara, double vare, double vt, double seconds)
+{
+    const int tt = (int)std::floor(seconds / (iter + 1) * (niter - iter));
+    double pc[HB_MAX_FOLD] = {0};
+    for (int j = 0; j < n_fold; j++) pc[cls_of[j]] = Pi[j];
+    char buf[1024]; // (hb_line's own limit)
+    int off = snprintf(buf, sizeof(buf), " %d %lld ", iter + 1, NnzSnp);
+    for (int j = 0; j < n_fold; j++) off += snprintf(buf + off, sizeof(buf) - off, "%.4f ", pc[j]);
+    snprintf(buf + off, sizeof(buf) - off, "%s%.4f %.4f %.4f %02dh%02dm%02ds", extras, vara, vare, vara / vt, tt / 3600, tt % 3600 / 60, tt % 3600 % 60);
+    return buf;
 }

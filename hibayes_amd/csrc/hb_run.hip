@@ -20,14 +20,6 @@
 #include <cstring>
 #include <map>
 
-int hbk_delta_pack(hb_ctx *c, const double *r0, const double *u0, double *buf);
-int hbk_delta_unpack(hb_ctx *c, const double *r0, const double *u0, const double *buf);
-int hbk_reduce_ru(hb_ctx *c);
-int hbk_abort_poison(hb_ctx *c, double *sums);
-int hbk_xalpha(hb_ctx *c, const double *dev_alpha, double *dev_out);
-extern "C" int hb_comm_world(const hb_comm *c);
-extern "C" int hb_comm_rank(const hb_comm *c);
-
 namespace {
 
 // arma::var, N-1 (two-pass)
@@ -85,8 +77,7 @@ struct hb_run {
     int wide_lv = 2;           // look-ahead groups of the point-mass models' wide geometry (HB_WIDE_LV=3: 3)
     bool no_adaptive_r = false, no_auto_bits = false; // HB_NO_ADAPTIVE_R, HB_NO_AUTO_BITS
     int pipeline_setup = -1;   // sharded runs: the context's pipeline switch as the ranks agreed on it in setup (checked at every step)
-    int aborts = 0;            // sweeps replayed so far
-    int abort_win_start = 0, abort_win_count = 0, slow_timeout = 0; // three aborts within 64 iterations: a slow device, the run's time-out is raised
+    hb_replay_state replay;    // sweeps replayed so far, and what the run has learnt about the device's waits (hb_runplan.hpp)
     hb_regime regime{};        // geometry by regime (plan_regime, hb_runplan.hpp): choose (Lv, D) per sweep from the previous sweep's moves
     int geo_cur = 0;           // 0: the wide geometry — (2 | 3, 7) for BayesB / C, (2, 2) for BayesR; 1: the narrow one — (2, 2), (2, 1)
     double last_events_pp = 0;
@@ -190,12 +181,24 @@ struct hb_run {
     int encode_random_effects();
     int take_model_args();
     int configure_device();
+    int take_context();
     int open_exchange();
     int marker_statistics();
+    int layout_and_regime();
     int prior_defaults();
     void console() const;
     int start_chain();
     int step();
+    // step's parts, in the order it calls them
+    int draw_before_sweep(hb_stream &hs);
+    int choose_geometry();
+    int sweep_with_replay(const hb_sweep_in &in, hb_sweep_out *so);
+    int enqueue_sweep(const hb_sweep_in &in);
+    int exchange_run(bool last);
+    int take_sweep_results(hb_sweep_out *so);
+    void draw_after_sweep(hb_stream &hs, const hb_sweep_out &so);
+    int store_sample();
+    void progress_line() const;
     int finish(hb_bayes_out *o);
 };
 
@@ -513,9 +516,8 @@ int hb_run::take_model_args()
     return HB_OK;
 }
 
-// the context, its geometry, the exchange, the marker statistics, the resident layout, the Gram blocks and the regime: every decision is
-// hb_runplan.hpp's, asked as soon as its facts are known and applied here
-int hb_run::configure_device()
+// the caller's context, or one of the run's own with its geometry and the genotypes
+int hb_run::take_context()
 {
     int rc;
     if (a.ctx) {
@@ -557,6 +559,15 @@ int hb_run::configure_device()
     }
     a.X_i8 = nullptr;
     a.X_f64 = nullptr;
+    return HB_OK;
+}
+
+// the context, its geometry, the exchange, the marker statistics, the resident layout, the Gram blocks and the regime: every decision is
+// hb_runplan.hpp's, asked as soon as its facts are known and applied here
+int hb_run::configure_device()
+{
+    int rc = take_context();
+    if (rc) return rc;
     HB_HIP(hipSetDevice(c->device));
     if (poly && a.Ki) { // nk = n: K is read as n x n (:222)
         rc = hb_ctx_poly_setup(c, a.Kival, a.Ki, n, 0);
@@ -577,8 +588,14 @@ int hb_run::configure_device()
 
     rc = open_exchange();
     if (!rc) rc = marker_statistics();
-    if (rc) return rc;
-    // resident layout
+    if (!rc) rc = layout_and_regime();
+    return rc;
+}
+
+// the resident layout, the Gram blocks, and whether and between which geometries the run follows the regime
+int hb_run::layout_and_regime()
+{
+    int rc;
     auto layout = [&](size_t free_bytes) {
         return plan_layout(a.genotype_bits, own_ctx, rowmode, a.precise, model_index, n_fold, c->P, c->pipeline, c->xmin, c->xmax, no_auto_bits,
                            free_bytes, c->m_pad, c->ld, wide_lv);
@@ -695,22 +712,14 @@ int hb_run::marker_statistics()
 int hb_run::prior_defaults()
 {
     int rc;
-    // ---- prior defaults, :327-374 ----
-    vara_ = a.has_vg ? a.vg : ((dfvara_ - 2) / dfvara_) * vary * h2;
-    vare_ = a.has_ve ? a.ve : vary * (1 - h2) / (nr + 1);
-    dfvare_ = a.has_dfve ? a.dfve : -2;
-    s2vara_ = a.has_s2vg ? a.s2vg : vara_ * (dfvara_ - 2) / dfvara_;
-    varg = vara_ / ((1 - Pi[0]) * sumvx);
-    s2varg_ = s2vara_ / ((1 - Pi[0]) * sumvx);
-    s2vare_ = a.has_s2ve ? a.s2ve : 0;
-    const double R2 = (dfvara_ - 2) / dfvara_;
-    lambda2 = 2 * (1 - R2) / (R2)*sumvx;
-    lambda = std::sqrt(lambda2);
-    rate0 = (shape0 - 1) / lambda2;
+    // ---- prior defaults, :327-374 (hb_model.hpp) ----
     vara_fold.assign(n_fold, 0.0);
     fold_snp_num.assign(n_fold, 0.0);
     pi_sum.assign(n_fold, 0.0);
-    for (int j = 0; j < n_fold; j++) vara_fold[j] = (vara_ / ((1 - Pi[0]) * sumvx)) * fold_[j];
+    const hb_priors pr = hb_prior_defaults(hb_prior_args{a.has_vg, a.has_ve, a.has_dfve, a.has_s2vg, a.has_s2ve, a.vg, a.ve, a.dfve, a.s2vg, a.s2ve,
+                                                         dfvara_, vary, h2, nr, Pi[0], sumvx}, fold_.data(), n_fold, vara_fold.data());
+    vara_ = pr.vara, vare_ = pr.vare, dfvare_ = pr.dfvare, s2vara_ = pr.s2vara, varg = pr.varg, s2varg_ = pr.s2varg, s2vare_ = pr.s2vare;
+    lambda2 = pr.lambda2, lambda = pr.lambda, shape0 = pr.shape0, rate0 = pr.rate0;
     {
         std::vector<double> g0(m, 0.0), vl(m, varg);
         std::vector<uint8_t> t0v(m, 0);
@@ -848,7 +857,7 @@ int hb_run::start_chain()
     return HB_OK;
 }
 
-// one iteration of the loop at src/Bayes.cpp:477-917
+// one iteration of the loop at src/Bayes.cpp:477-917, in the reference's order; the parts follow
 int hb_run::step()
 {
     if (done || iter >= niter) {
@@ -856,17 +865,35 @@ int hb_run::step()
         return HB_OK;
     }
     const auto t0 = hb_clk::now();
-    int rc;
     HB_HIP(hipSetDevice(c->device));
     if (a.interrupt && a.interrupt(a.interrupt_user)) return hb_fail(HB_ERR_INTERRUPT, "interrupted");
     hb_stream hs(a.seed, hb_sub(HB_PURPOSE_HOST, (uint64_t)iter), 0);
+    HB_TRY(draw_before_sweep(hs)); // :479-584
+    // ---------------- marker sweep on the device, :586-816 ----------------
+    const hb_sweep_in in = hb_sweep_params(model_index, n_fold, Pi.data(), fold_.data(), vara_fold.data(), vare_, varg, s2varg_ * dfvara_, dfvara_, lambda,
+                                           lambda2, iter, nburn, thin, always_in);
+    hb_sweep_out so{};
+    HB_TRY(choose_geometry());
+    HB_TRY(sweep_with_replay(in, &so));
+    HB_TRY(take_sweep_results(&so));
+    draw_after_sweep(hs, so); // :603-823
+    if (iter >= nburn) nzct++; // :826-845 (the per-marker counters themselves live on the device)
+    if (in.store && count < n_records) HB_TRY(store_sample()); // :848-882
+    loop_seconds += hb_since(t0);
+    if (a.verbose && a.outfreq > 0 && (iter + 1) % a.outfreq == 0) progress_line(); // :884-914
+    iter++;
+    if (count == n_records || iter >= niter) done = true; // :916
+    return HB_OK;
+}
 
+// the draws and enqueues before the sweep, in the reference's order on the host stream hs (that order is part of the chain)
+int hb_run::draw_before_sweep(hb_stream &hs)
+{
     // sample intercept, :479-482
     const double ng = (double)n_glob; // (= n unless the individuals are sharded)
     const double mu_ = -(sum_r / ng + std::sqrt(vare_ / ng) * hs.norm());
     mu -= mu_;
-    rc = hb_ctx_residual_shift(c, mu_);
-    if (rc) return rc;
+    HB_TRY(hb_ctx_residual_shift(c, mu_));
 
     // covariates (:484-494) and environmental random effects (:496-516): enqueued as device kernels. Their deviates do not
     // depend on the data, so they are drawn here first, in the reference's order — one normal per covariate, then per term
@@ -880,156 +907,137 @@ int hb_run::step()
             for (int q = 0; q < nlev[t]; q++) zl_[lev_first[t] + q] = hs.norm();
             ch_[t] = hs.chisq(nlev[t] + dfr);
         }
-        rc = hb_ctx_blocks_step(c, vare_, zb_.data(), zl_.data(), ch_.data(), dfr, s2r);
-        if (rc) return rc;
+        HB_TRY(hb_ctx_blocks_step(c, vare_, zb_.data(), zl_.data(), ch_.data(), dfr, s2r));
     }
     // BSLMM's polygenic block (:518-552), enqueued like the blocks above: its normals are drawn on the device, its chisq (:547) here, at the
-    // reference's place in the host stream; vb and the check of :533 come back with the sweep's fetch. Before the snapshot below: a replayed
-    // sweep restarts from the residual this block left.
+    // reference's place in the host stream; vb and the check of :533 come back with the sweep's fetch. Before the sweep's snapshot
+    // (sweep_with_replay): a replayed sweep restarts from the residual this block left.
     if (poly) {
         const double chis = hs.chisq(dfvara_ + (double)n);
-        rc = hb_ctx_poly_step(c, vare_, iter == 0 ? vara_ : -1.0, a.seed, iter, chis, s2vara_ * dfvara_); // (vbtmp = vara_, :333)
-        if (rc) return rc;
+        HB_TRY(hb_ctx_poly_step(c, vare_, iter == 0 ? vara_ : -1.0, a.seed, iter, chis, s2vara_ * dfvara_)); // (vbtmp = vara_, :333)
     }
     // the single-step epsilon block (:554-584), enqueued the same way and at the same place: the J draw's normal (:559) and the chisq of :579
     // from the host stream here, the rows' normals on the device; veps and J come back with the sweep's fetch
     if (epsl) {
         const double zJ = hs.norm();
         const double chis = hs.chisq(dfvara_ + (double)qe);
-        rc = hb_ctx_epsl_step(c, vare_, iter == 0 ? vara_ : -1.0, a.seed, iter, zJ, chis, s2vara_ * dfvara_); // (vepstmp = vara_, :332)
-        if (rc) return rc;
+        HB_TRY(hb_ctx_epsl_step(c, vare_, iter == 0 ? vara_ : -1.0, a.seed, iter, zJ, chis, s2vara_ * dfvara_)); // (vepstmp = vara_, :332)
     }
+    return HB_OK;
+}
 
-    // ---------------- marker sweep on the device, :586-816 ----------------
-    hb_sweep_in in{};
-    in.model_index = model_index;
-    in.n_fold = n_fold;
-    in.iter = iter;
-    in.vare = vare_;
-    in.varg = varg;
-    in.s2varg_df = s2varg_ * dfvara_;
-    in.dfvara = dfvara_;
-    for (int j = 0; j < n_fold; j++) {
-        in.logpi[j] = std::log(Pi[j]);
-        in.fold[j] = fold_[j];
-        in.vara_fold[j] = vara_fold[j];
+// geometry by regime (hb_runplan.hpp), when the context is ours or its owner asked for it
+int hb_run::choose_geometry()
+{
+    if (!regime.on) return HB_OK;
+    const int want = regime_next(regime, geo_cur, last_events_pp); // (moves per panel of the previous sweep on this shard)
+    if (want != geo_cur) {
+        HB_TRY(hb_ctx_switch_geometry(c, 1, regime.Lv[want], regime.D[want]));
+        geo_cur = want;
     }
-    in.lambda = lambda;
-    in.lambda2 = lambda2;
-    in.count_pip = (iter >= nburn) && !always_in;
-    in.store = (iter >= nburn) && ((iter + 1 - nburn) % thin == 0);
-    hb_sweep_out so{};
-    // geometry by regime (hb_runplan.hpp), when the context is ours or its owner asked for it
-    if (regime.on) {
-        const int want = regime_next(regime, geo_cur, last_events_pp); // (moves per panel of the previous sweep on this shard)
-        if (want != geo_cur) {
-            rc = hb_ctx_switch_geometry(c, 1, regime.Lv[want], regime.D[want]);
-            if (rc) return rc;
-            geo_cur = want;
-        }
+    return HB_OK;
+}
+
+namespace {
+// Whatever way a sweep ends, the context gets back the wait bound and the geometry it came with (a caller-owned context
+// outlives the run): a scope guard, not a line after the loop that the error returns inside it would skip.
+struct restore_ctx {
+    hb_ctx *c;
+    int timeout_ms;
+    int geo[4] = {0, 0, 0, 0};
+    bool fell_back = false;
+    ~restore_ctx()
+    {
+        c->timeout_ms = timeout_ms;
+        if (fell_back) (void)hb_ctx_force_geometry(c, geo[0], geo[1], geo[2]);
     }
-    // The sweep, in sync_blocks runs of mat-vec groups (1: the whole sweep). After each run the shards sum their residual
-    // deltas (n doubles; u moves by the negative) — and, after the last one, the 16 scalar sums — all enqueued on the sweep
-    // stream behind the run itself; the iteration's only host synchronisation is the fetch below.
-    // A sweep whose pipeline gave up waiting (HB_ERR_ABORTED: every wait is bounded) is replayed from the state
-    // saved here: effects, residual, u and the posterior counters, a few MB copied by one kernel. The draws are counter-based, so the
-    // replay is the same chain. A second failure of the same sweep replays it on the event-ordered per-panel kernels, which wait
-    // for nothing on the device; sharded, the abort reaches every rank through the exchange and all of them replay.
+};
+} // namespace
+
+// The sweep, and its replay when it aborts.
+// A sweep whose pipeline gave up waiting (HB_ERR_ABORTED: every wait is bounded) is replayed from the state
+// saved here: effects, residual, u and the posterior counters, a few MB copied by one kernel. The draws are counter-based, so the
+// replay is the same chain. A second failure of the same sweep replays it on the event-ordered per-panel kernels, which wait
+// for nothing on the device; sharded, the abort reaches every rank through the exchange and all of them replay. The policy — the wait bounds,
+// when to fall back, when to give up, when a device counts as slow — is hb_runplan.hpp's ("replaying an aborted sweep"); it is asked and applied here.
+int hb_run::sweep_with_replay(const hb_sweep_in &in, hb_sweep_out *so)
+{
     // (advisor finding, round 5) the replay decision was agreed by all ranks in setup on the context's pipeline switch as it was then; a caller that flips
     // it on one rank afterwards (hb_ctx_set_pipeline between steps) would make that rank's decision differ and the others hang in the exchange: refuse loudly.
     // (The adaptive geometry changes Lv and D, never this switch; the replay's own fallback flips it inside this function and puts it back.)
     if (pipeline_setup >= 0 && (c->pipeline ? 1 : 0) != pipeline_setup)
         return hb_fail(HB_ERR_INVALID, "the context's pipeline switch changed during a sharded run (the ranks agreed on their replay decision with the setting at set-up)");
-    const bool recover = recover_on && c->pipeline && !rowmode;
-    // Whatever way this iteration ends, the context gets back the wait bound and the geometry it came with (a caller-owned context
-    // outlives the run): a scope guard, not a line after the loop that the error returns inside it would skip.
-    struct restore_ctx {
-        hb_ctx *c;
-        int timeout_ms;
-        int geo[4] = {0, 0, 0, 0};
-        bool fell_back = false;
-        ~restore_ctx()
-        {
-            c->timeout_ms = timeout_ms;
-            if (fell_back) {
-                c->force_geometry = true;
-                (void)hb_ctx_switch_geometry(c, geo[0], geo[1], geo[2]);
-                c->force_geometry = false;
-            }
-        }
-    } guard{c, c->timeout_ms};
-    // A sweep that is replayed when it times out may give up early: a healthy hand-off takes microseconds, the device's own pauses a
-    // millisecond, so 100 ms instead of the context's 3 s — unless HB_TIMEOUT_MS fixed the bound, or the run has
-    // learnt that this device is slow (three aborts within 64 iterations raise slow_timeout). Without recovery the context's bound stays.
-    if (recover && !c->timeout_env) c->timeout_ms = std::max(100, slow_timeout);
-    if (recover) {
-        rc = hb_ctx_snapshot(c, model_index, in.store != 0, in.count_pip != 0);
-        if (rc) return rc;
-    }
+    const bool recover = replay_enabled(recover_on, c->pipeline, rowmode);
+    restore_ctx guard{c, c->timeout_ms};
+    c->timeout_ms = replay_first_wait_ms(recover, c->timeout_env, c->timeout_ms, replay);
+    if (recover) HB_TRY(hb_ctx_snapshot(c, model_index, in.store != 0, in.count_pip != 0));
     for (int attempt = 0;; attempt++) {
-        for (int b = 0; b < sync_blocks; b++) {
-            if (sharded) {
-                HB_HIP(hipMemcpyAsync(r0, c->r, sizeof(double) * n, hipMemcpyDeviceToDevice, c->stream));
-                HB_HIP(hipMemcpyAsync(u0, c->u, sizeof(double) * n, hipMemcpyDeviceToDevice, c->stream));
-            }
-            rc = hb_ctx_sweep_range(c, &in, b, sync_blocks);
-            if (rc) return rc;
-            if (sharded) {
-                const bool last = b == sync_blocks - 1;
-                rc = hbk_delta_pack(c, r0, u0, xbuf);
-                if (rc) return rc;
-                // (the sums ride along every time — the message has one shape — but only the last run's are the sweep's)
-                HB_HIP(hipMemcpyAsync(xbuf + (size_t)n, c->acc, sizeof(double) * HB_ACC_N, hipMemcpyDeviceToDevice, c->stream));
-                rc = hbk_abort_poison(c, xbuf + (size_t)n);
-                if (rc) return rc;
-                rc = exchange();
-                if (rc) return rc;
-                rc = hbk_delta_unpack(c, r0, u0, xbuf);
-                if (rc) return rc;
-                if (last) {
-                    HB_HIP(hipMemcpyAsync(c->acc, xbuf + (size_t)n, sizeof(double) * HB_ACC_N, hipMemcpyDeviceToDevice, c->stream));
-                    rc = hbk_reduce_ru(c);
-                    if (rc) return rc;
-                }
-            }
-        }
-        rc = hb_ctx_sweep_end(c, &so);
-        if (rc != HB_ERR_ABORTED || !recover || attempt >= 3) break;
-        aborts++;
-        // a second time-out of the same sweep: the event-ordered per-panel kernels, which wait for nothing on the device (the switch is
-        // forced past HB_PIPELINE / HB_LOOKAHEAD / HB_DOTGROUP: a tuning variable must not turn the fall-back into a third try of the
-        // pipeline that just stalled twice)
+        HB_TRY(enqueue_sweep(in));
+        const int rc = hb_ctx_sweep_end(c, so);
+        if (rc != HB_ERR_ABORTED) return rc;
+        const hb_replay_step next = replay_after_abort(recover, attempt, guard.fell_back, iter, c->timeout_ms, replay);
+        if (!next.replay) return rc;
+        replay = next.state;
+        // the switch to the per-panel kernels is forced past HB_PIPELINE / HB_LOOKAHEAD / HB_DOTGROUP: a tuning variable must not turn the
+        // fall-back into a third try of the pipeline that just stalled twice
         bool per_panel = guard.fell_back;
-        if (attempt >= 1 && !guard.fell_back) {
+        if (next.to_per_panel) {
             (void)hb_ctx_get_pipeline(c, &guard.geo[0], &guard.geo[1], &guard.geo[2], &guard.geo[3]);
-            c->force_geometry = true;
-            const int rc2 = hb_ctx_switch_geometry(c, 0, 0, 1);
-            c->force_geometry = false;
-            if (rc2) return rc2;
+            HB_TRY(hb_ctx_force_geometry(c, 0, 0, 1));
             guard.fell_back = true;
             per_panel = c->pipeline == 0;
         }
         fprintf(stderr, "hibayes_gpu: iteration %d: %s — state restored, replaying the sweep%s\n", iter + 1, hb_last_error(),
                 per_panel ? " on the per-panel kernels" : "");
-        rc = hb_ctx_restore(c);
-        if (rc) return rc;
-        // (the replay waits 3 s: a wait that was merely slow — a shared or profiled GPU — then gets through)
-        c->timeout_ms = std::max(c->timeout_ms, 3000);
-        // a run that keeps aborting is on a slow device, not in a stall (those come once in a few thousand sweeps): wait longer from now on
-        if (iter - abort_win_start > 64) { abort_win_start = iter; abort_win_count = 0; }
-        if (++abort_win_count >= 3) slow_timeout = std::min(3000, std::max(100, slow_timeout) * 4);
+        HB_TRY(hb_ctx_restore(c));
+        c->timeout_ms = next.timeout_ms;
     }
-    if (rc) return rc;
-    events_sum += so.n_events;
-    last_events_pp = so.n_events / ((double)std::max(1, world) * std::max(1, c->npanels));
-    miss_sum += so.n_cache_miss;
-    redo_sum += so.n_redo;
-    sum_r = so.sum_r;
-    sum_r2 = so.sum_r2;
+}
+
+// One attempt at the sweep, in sync_blocks runs of mat-vec groups (1: the whole sweep). After each run the shards sum their residual
+// deltas (n doubles; u moves by the negative) — and, after the last one, the 16 scalar sums — all enqueued on the sweep
+// stream behind the run itself; the iteration's only host synchronisation is the fetch that follows (hb_ctx_sweep_end).
+int hb_run::enqueue_sweep(const hb_sweep_in &in)
+{
+    for (int b = 0; b < sync_blocks; b++) {
+        if (sharded) {
+            HB_HIP(hipMemcpyAsync(r0, c->r, sizeof(double) * n, hipMemcpyDeviceToDevice, c->stream));
+            HB_HIP(hipMemcpyAsync(u0, c->u, sizeof(double) * n, hipMemcpyDeviceToDevice, c->stream));
+        }
+        HB_TRY(hb_ctx_sweep_range(c, &in, b, sync_blocks));
+        if (sharded) HB_TRY(exchange_run(b == sync_blocks - 1));
+    }
+    return HB_OK;
+}
+
+// the sharded exchange of one run: pack, poison, exchange, unpack, and the sums after the last
+int hb_run::exchange_run(bool last)
+{
+    HB_TRY(hbk_delta_pack(c, r0, u0, xbuf));
+    // (the sums ride along every time — the message has one shape — but only the last run's are the sweep's)
+    HB_HIP(hipMemcpyAsync(xbuf + (size_t)n, c->acc, sizeof(double) * HB_ACC_N, hipMemcpyDeviceToDevice, c->stream));
+    HB_TRY(hbk_abort_poison(c, xbuf + (size_t)n));
+    HB_TRY(exchange());
+    HB_TRY(hbk_delta_unpack(c, r0, u0, xbuf));
+    if (last) {
+        HB_HIP(hipMemcpyAsync(c->acc, xbuf + (size_t)n, sizeof(double) * HB_ACC_N, hipMemcpyDeviceToDevice, c->stream));
+        HB_TRY(hbk_reduce_ru(c));
+    }
+    return HB_OK;
+}
+
+// the sweep's results into the chain's state
+int hb_run::take_sweep_results(hb_sweep_out *so)
+{
+    events_sum += so->n_events;
+    last_events_pp = so->n_events / ((double)std::max(1, world) * std::max(1, c->npanels));
+    miss_sum += so->n_cache_miss;
+    redo_sum += so->n_redo;
+    sum_r = so->sum_r;
+    sum_r2 = so->sum_r2;
     if (rowmode) { // the three n-long reductions over all shards (the sweep's own ones saw this shard's rows only)
         if (c->row_failed) return hb_fail(HB_ERR_COMM, "row-sharded mode: an all-reduce inside the sweep failed");
-        rc = row_sums(&sum_r, &sum_r2, &so.var_u);
-        if (rc) return rc;
+        HB_TRY(row_sums(&sum_r, &sum_r2, &so->var_u));
     }
     if (nc + nr) { // the block state arrived with the sweep's fetch
         const double *h = c->h_blk;
@@ -1038,100 +1046,86 @@ int hb_run::step()
         std::copy(h + nc + n_levels, h + nc + n_levels + nr, vrtmp.begin());
         std::copy(h + nc + n_levels + nr, h + nc + n_levels + 2 * nr, vr.begin());
     }
-
     if (poly) {
         const double *ps = hb_poly_host_state(c);
         if (ps[2] != 0.0)
             return hb_fail(HB_ERR_INVALID, "matrix is not positive definite, try to specify parameter 'lambda' with a small value, eg: 0.001 or bigger"); // :533
         vb = ps[0];
     }
-
     if (epsl) {
         const double *es = hb_epsl_host_state(c);
         veps = es[0];
         eps_J = es[2];
     }
+    return HB_OK;
+}
 
-    // hyper-parameters after the sweep (hb_model.hpp)
+// hyper-parameters after the sweep (hb_model.hpp), then the two variances
+void hb_run::draw_after_sweep(hb_stream &hs, const hb_sweep_out &so)
+{
     hb_draw_hyper(hs, hb_hyper_prior{model_index, n_fold, fixpi, dfvara_, s2varg_, shape0, rate0, fold_.data()},
                   hb_hyper_sums{so.sum_g2, so.sum_vargL, so.class_count, (double)m_global, (double)nvar0},
                   hb_hyper_state{varg, lambda, lambda2, NnzSnp, Pi.data(), vara_fold.data(), fold_snp_num.data()});
     if (poly) va = varg; // :715
-    vara_ = so.var_u;                                                       // :819
-    vare_ = (sum_r2 + s2vare_ * dfvare_) / hs.chisq(ng + dfvare_);  // :823
+    vara_ = so.var_u;                                                                 // :819
+    vare_ = (sum_r2 + s2vare_ * dfvare_) / hs.chisq((double)n_glob + dfvare_);  // :823
+}
 
-    if (iter >= nburn) { // :826-845 (the per-marker counters themselves live on the device)
-        nzct++;
+// thinned store, :848-882
+int hb_run::store_sample()
+{
+    s_mu[count] = mu;
+    mu_sum += mu;
+    if (!fixpi)
+        for (int j = 0; j < n_fold; j++) {
+            s_pi[(size_t)count * n_fold + j] = Pi[j];
+            pi_sum[j] += Pi[j];
+        }
+    s_Vg[count] = vara_;
+    s_Ve[count] = vare_;
+    if (poly) { // :854-858
+        s_Va[count] = va;
+        s_Vb[count] = vb;
+        HB_TRY(hbk_poly_accumulate(c));
     }
-
-    // thinned store, :848-882
-    if (in.store && count < n_records) {
-        s_mu[count] = mu;
-        mu_sum += mu;
-        if (!fixpi)
-            for (int j = 0; j < n_fold; j++) {
-                s_pi[(size_t)count * n_fold + j] = Pi[j];
-                pi_sum[j] += Pi[j];
-            }
-        s_Vg[count] = vara_;
-        s_Ve[count] = vare_;
-        if (poly) { // :854-858
-            s_Va[count] = va;
-            s_Vb[count] = vb;
-            rc = hbk_poly_accumulate(c);
-            if (rc) return rc;
-        }
-        if (epsl) { // :873-877
-            s_Veps[count] = veps;
-            s_J[count] = eps_J;
-            rc = hbk_epsl_accumulate(c, store_eps ? s_eps.data() + (size_t)count * qe : nullptr);
-            if (rc) return rc;
-        }
-        vara_sum += vara_;
-        vare_sum += vare_;
-        if (a.store_alpha) {
-            rc = hb_ctx_get_effects(c, s_alpha.data() + (size_t)count * m, nullptr, nullptr);
-            if (rc) return rc;
-        }
-        for (int i = 0; i < nc; i++) {
-            s_beta[(size_t)count * nc + i] = beta[i];
-            beta_sum[i] += beta[i];
-        }
-        double vt = vara_ + vare_;
-        for (int t = 0; t < nr; t++) {
-            vt += vr[t];
-            s_Vr[(size_t)count * nr + t] = vr[t];
-            vr_sum[t] += vr[t];
-        }
-        for (int q = 0; q < n_levels; q++) {
-            s_r[(size_t)count * n_levels + q] = estR[q];
-            estR_sum[q] += estR[q];
-        }
-        s_h2[count] = vara_ / vt;
-        hsq_sum += vara_ / vt;
-        count++;
+    if (epsl) { // :873-877
+        s_Veps[count] = veps;
+        s_J[count] = eps_J;
+        HB_TRY(hbk_epsl_accumulate(c, store_eps ? s_eps.data() + (size_t)count * qe : nullptr));
     }
-    loop_seconds += hb_since(t0);
-
-    if (a.verbose && a.outfreq > 0 && (iter + 1) % a.outfreq == 0) { // :884-914
-        const int tt = (int)std::floor(loop_seconds / (iter + 1) * (niter - iter));
-        double vt = vara_ + vare_;
-        for (int t = 0; t < nr; t++) vt += vr[t];
-        char pis[256] = {0};
-        size_t off = 0;
-        std::vector<double> pc(n_fold);
-        for (int j = 0; j < n_fold; j++) pc[cls_of[j]] = Pi[j]; // (the caller's class order)
-        for (int j = 0; j < n_fold && off < sizeof(pis) - 16; j++) off += snprintf(pis + off, sizeof(pis) - off, "%.4f ", pc[j]);
-        char lam[32] = {0};
-        if (model == "BayesL") snprintf(lam, sizeof(lam), "%.4f ", lambda);
-        if (poly) snprintf(lam, sizeof(lam), "%.4f %.4f ", va, vb); // :901
-        if (epsl) snprintf(lam + strlen(lam), sizeof(lam) - strlen(lam), "%.4f ", veps); // :908
-        line(" %d %lld %s%s%.4f %.4f %.4f %02dh%02dm%02ds", iter + 1, NnzSnp, pis, lam, vara_, vare_, vara_ / vt, tt / 3600,
-             tt % 3600 / 60, tt % 3600 % 60);
+    vara_sum += vara_;
+    vare_sum += vare_;
+    if (a.store_alpha) HB_TRY(hb_ctx_get_effects(c, s_alpha.data() + (size_t)count * m, nullptr, nullptr));
+    for (int i = 0; i < nc; i++) {
+        s_beta[(size_t)count * nc + i] = beta[i];
+        beta_sum[i] += beta[i];
     }
-    iter++;
-    if (count == n_records || iter >= niter) done = true; // :916
+    double vt = vara_ + vare_;
+    for (int t = 0; t < nr; t++) {
+        vt += vr[t];
+        s_Vr[(size_t)count * nr + t] = vr[t];
+        vr_sum[t] += vr[t];
+    }
+    for (int q = 0; q < n_levels; q++) {
+        s_r[(size_t)count * n_levels + q] = estR[q];
+        estR_sum[q] += estR[q];
+    }
+    s_h2[count] = vara_ / vt;
+    hsq_sum += vara_ / vt;
+    count++;
     return HB_OK;
+}
+
+// the console line, :884-914 (hb_model.hpp formats it)
+void hb_run::progress_line() const
+{
+    double vt = vara_ + vare_;
+    for (int t = 0; t < nr; t++) vt += vr[t];
+    char lam[32] = {0};
+    if (model == "BayesL") snprintf(lam, sizeof(lam), "%.4f ", lambda);
+    if (poly) snprintf(lam, sizeof(lam), "%.4f %.4f ", va, vb); // :901
+    if (epsl) snprintf(lam + strlen(lam), sizeof(lam) - strlen(lam), "%.4f ", veps); // :908
+    line("%s", hb_progress_line(iter, niter, NnzSnp, Pi.data(), cls_of.data(), n_fold, lam, vara_, vare_, vt, loop_seconds).c_str());
 }
 
 // posterior assembly, src/Bayes.cpp:919-1040
@@ -1271,7 +1265,7 @@ int hb_run::finish(hb_bayes_out *o)
     o->loop_seconds = loop_seconds;
     o->iters_done = iter;
     o->mean_events = iter > 0 ? events_sum / iter : 0;
-    o->sweeps_replayed = aborts;
+    o->sweeps_replayed = replay.aborts;
     o->resident_bits = c ? c->layout : 0;
     line("Posterior parameters:");
     line("    Mu %f", Mu);
@@ -1325,7 +1319,7 @@ int hb_run_state(hb_run *r, hb_run_info *info)
     info->mean_events = r->iter > 0 ? r->events_sum / r->iter : 0.0;
     info->mean_misses = r->iter > 0 ? r->miss_sum / r->iter : 0.0;
     info->mean_redo = r->iter > 0 ? r->redo_sum / r->iter : 0.0;
-    info->sweeps_replayed = r->aborts;
+    info->sweeps_replayed = r->replay.aborts;
     info->resident_bits = r->c ? r->c->layout : 0;
     info->lambda2 = r->lambda2;
     info->loop_seconds = r->loop_seconds;

@@ -1,7 +1,8 @@
 // hb_runplan.hpp — the configuration one run gives plan_sweep (hb_plan.hpp): panel, geometry, resident layout, and whether and where the geometry
-// follows the regime. The one statement of these decisions: hb_ctx_create and hb_pipeline_geometry (hb_ctx.hip) and hb_run's set-up and step
+// follows the regime; and what follows a sweep that aborted. The one statement of these decisions: hb_ctx_create and hb_pipeline_geometry (hb_ctx.hip) and hb_run's set-up and step
 // (hb_run.hip) ask here and apply the answer. Pure functions of small integers and booleans, in the order in which a run learns the facts; no
-// HIP, no getenv, no hb_ctx: plain g++ -std=c++17, and tests/test_host_logic.py prints every stage against tests/golden/run_plan_table.json.
+// HIP, no getenv, no hb_ctx: plain g++ -std=c++17, and tests/test_host_logic.py prints every stage against tests/golden/run_plan_table.json
+// (the replay's against tests/golden/replay_plan_table.json).
 // They are part of the chain's definition: a run on 2-bit genotypes is the int8 run bit for bit only if both take the same geometry in every sweep.
 #pragma once
 #include "hb_plan.hpp"
@@ -124,4 +125,48 @@ static inline int regime_next(const hb_regime &r, int cur, double moves_per_pane
     if (cur == 1 && moves_per_panel < r.to_wide) return 0;
     if (cur == 0 && moves_per_panel > r.to_narrow) return 1;
     return cur;
+}
+
+// ---- replaying an aborted sweep ----
+// A sweep whose pipeline gave up waiting (HB_ERR_ABORTED: every wait on the device is bounded) is replayed from the state saved
+// before it. hb_run's step() asks here what follows and applies it: snapshot, restore, the switch of geometry, the line on stderr.
+struct hb_replay_state {
+    int aborts = 0;                    // sweeps replayed so far (hb_bayes_out.sweeps_replayed)
+    int win_start = 0, win_count = 0;  // the 64-iteration window: the iteration that opened it, the aborts in it
+    int slow_timeout = 0;              // ms; three aborts within a window: a slow device, not a stall — the run's sweeps wait longer from then on
+};
+
+// recovery at all: HB_RECOVER not switched off, on the persistent pipeline (the per-panel kernels wait for nothing on the device), individuals not sharded
+static inline bool replay_enabled(bool recover_on, int pipeline, bool rowmode) { return recover_on && pipeline && !rowmode; }
+
+// The wait bound a sweep starts with. A sweep that is replayed when it times out may give up early: a healthy hand-off takes microseconds, the
+// device's own pauses a millisecond, so 100 ms instead of the context's 3 s — unless HB_TIMEOUT_MS fixed the bound (timeout_env), or the run has
+// learnt that this device is slow. Without recovery the context's bound stays.
+static inline int replay_first_wait_ms(bool recover, bool timeout_env, int ctx_timeout_ms, const hb_replay_state &s)
+{
+    return recover && !timeout_env ? std::max(100, s.slow_timeout) : ctx_timeout_ms;
+}
+
+struct hb_replay_step {
+    bool replay;          // restore and run the sweep again; false: the abort is the run's failure
+    bool to_per_panel;    // first switch to the event-ordered per-panel kernels
+    int timeout_ms;       // the replay's wait bound
+    hb_replay_state state;
+};
+
+// What follows the abort of attempt `attempt` (0: the sweep's first try) in iteration `iter`, with the wait bound timeout_ms in force; fell_back: an
+// earlier replay of this sweep already switched to the per-panel kernels.
+static inline hb_replay_step replay_after_abort(bool recover, int attempt, bool fell_back, int iter, int timeout_ms, const hb_replay_state &s)
+{
+    if (!recover || attempt >= 3) return hb_replay_step{false, false, timeout_ms, s}; // at most three replays: the fourth failure ends the run
+    hb_replay_step d{true, false, timeout_ms, s};
+    d.state.aborts++;
+    // a second time-out of the same sweep: the per-panel kernels, once
+    d.to_per_panel = attempt >= 1 && !fell_back;
+    // (the replay waits 3 s: a wait that was merely slow — a shared or profiled GPU — then gets through)
+    d.timeout_ms = std::max(timeout_ms, 3000);
+    // a run that keeps aborting is on a slow device, not in a stall (those come once in a few thousand sweeps): wait longer from now on
+    if (iter - d.state.win_start > 64) { d.state.win_start = iter; d.state.win_count = 0; }
+    if (++d.state.win_count >= 3) d.state.slow_timeout = std::min(3000, std::max(100, d.state.slow_timeout) * 4);
+    return d;
 }

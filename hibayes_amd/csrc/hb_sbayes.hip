@@ -88,23 +88,15 @@ static int sbayes_run(const hb_sbayes_args *args, hb_ldm *H, hb_sbayes_out *o, b
     const double yy = arma_sum(yyi.data(), m) / count_y;
     const double vary = yy / (n - 1);
     const double h2 = 0.5;
-    // ---- priors, :117-170 ----
+    // ---- priors, :117-170 (hb_model.hpp) ----
     const double dfvara_ = a.has_dfvg ? a.dfvg : 4;
     if (dfvara_ <= 2) return hb_fail(HB_ERR_INVALID, "dfvg should not be less than 2.");
-    double vara_ = a.has_vg ? a.vg : ((dfvara_ - 2) / dfvara_) * vary * h2;
-    double vare_ = a.has_ve ? a.ve : vary * (1 - h2);
-    const double dfvare_ = a.has_dfve ? a.dfve : -2;
-    const double s2vara_ = a.has_s2vg ? a.s2vg : vara_ * (dfvara_ - 2) / dfvara_;
-    const double sumvx = arma_sum(vx.data(), m);
-    double varg = vara_ / ((1 - Pi[0]) * sumvx);
-    const double s2varg_ = s2vara_ / ((1 - Pi[0]) * sumvx);
-    const double s2vare_ = a.has_s2ve ? a.s2ve : 0;
     if (niter < nburn) return hb_fail(HB_ERR_INVALID, "Number of total iteration ('niter') shold be larger than burn-in ('nburn').");
-    const double R2 = (dfvara_ - 2) / dfvara_;
-    double lambda2 = 2 * (1 - R2) / (R2)*sumvx, lambda = std::sqrt(lambda2);
-    const double shape0 = 1.1, rate0 = (shape0 - 1) / lambda2;
     std::vector<double> vara_fold(n_fold), fold_snp_num(n_fold, 0.0), pi_sum(n_fold, 0.0);
-    for (int j = 0; j < n_fold; j++) vara_fold[j] = (vara_ / ((1 - Pi[0]) * sumvx)) * fold_[j];
+    const hb_priors pr = hb_prior_defaults(hb_prior_args{a.has_vg, a.has_ve, a.has_dfve, a.has_s2vg, a.has_s2ve, a.vg, a.ve, a.dfve, a.s2vg, a.s2ve,
+                                                         dfvara_, vary, h2, 0, Pi[0], arma_sum(vx.data(), m)}, fold_.data(), n_fold, vara_fold.data());
+    double vara_ = pr.vara, vare_ = pr.vare, varg = pr.varg, lambda2 = pr.lambda2, lambda = pr.lambda;
+    const double dfvare_ = pr.dfvare, s2vara_ = pr.s2vara, s2varg_ = pr.s2varg, s2vare_ = pr.s2vare, shape0 = pr.shape0, rate0 = pr.rate0;
     int nw = 0;
     if (a.windindx)
         for (int i = 0; i < m; i++) {
@@ -211,23 +203,8 @@ static int sbayes_run(const hb_sbayes_args *args, hb_ldm *H, hb_sbayes_out *o, b
     for (iter = 0; iter < niter; iter++) {
         if (a.interrupt && a.interrupt(a.interrupt_user)) return hb_fail(HB_ERR_INTERRUPT, "interrupted");
         hb_stream hs(a.seed, hb_sub(HB_PURPOSE_HOST, (uint64_t)iter), 0);
-        hb_sweep_in in{};
-        in.model_index = model_index;
-        in.n_fold = n_fold;
-        in.iter = iter;
-        in.vare = vare_;
-        in.varg = varg;
-        in.s2varg_df = s2varg_ * dfvara_;
-        in.dfvara = dfvara_;
-        for (int j = 0; j < n_fold; j++) {
-            in.logpi[j] = std::log(Pi[j]);
-            in.fold[j] = fold_[j];
-            in.vara_fold[j] = vara_fold[j];
-        }
-        in.lambda = lambda;
-        in.lambda2 = lambda2;
-        in.count_pip = (iter >= nburn) && !always_in;
-        in.store = 0;
+        const hb_sweep_in in = hb_sweep_params(model_index, n_fold, Pi.data(), fold_.data(), vara_fold.data(), vare_, varg, s2varg_ * dfvara_, dfvara_,
+                                               lambda, lambda2, iter, nburn, 0 /* never a device record */, always_in);
         *R.h_in = in;
         HB_HIP(hipMemcpyAsync(d.d_in, R.h_in, sizeof(hb_sweep_in), hipMemcpyHostToDevice, d.stream));
         if (sparse) { // varei = varediff[i] * vara_ + vare_ (:285) and the truncation's bound (:388)
@@ -276,17 +253,9 @@ static int sbayes_run(const hb_sbayes_args *args, hb_ldm *H, hb_sbayes_out *o, b
             count++;
         }
         if (a.verbose && a.outfreq > 0 && (iter + 1) % a.outfreq == 0) { // :514-537
-            const double el = hb_since(t_loop);
-            const int tt = (int)std::floor(el / (iter + 1) * (niter - iter));
-            char pis[256] = {0};
-            size_t off = 0;
-            std::vector<double> pc(n_fold);
-            for (int j = 0; j < n_fold; j++) pc[cls_of[j]] = Pi[j];
-            for (int j = 0; j < n_fold && off < sizeof(pis) - 16; j++) off += snprintf(pis + off, sizeof(pis) - off, "%.4f ", pc[j]);
             char lam[32] = {0};
             if (model == "BayesL") snprintf(lam, sizeof(lam), "%.4f ", lambda);
-            line(" %d %lld %s%s%.4f %.4f %.4f %02dh%02dm%02ds", iter + 1, NnzSnp, pis, lam, vara_, vare_, vara_ / (vara_ + vare_), tt / 3600,
-                 tt % 3600 / 60, tt % 3600 % 60);
+            line("%s", hb_progress_line(iter, niter, NnzSnp, Pi.data(), cls_of.data(), n_fold, lam, vara_, vare_, vara_ + vare_, hb_since(t_loop)).c_str());
         }
         if (count == n_records) {
             iter++;

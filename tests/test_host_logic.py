@@ -542,6 +542,114 @@ def test_every_run_plan_equals_the_recorded_decisions(tmp_path):
             assert (v == "2") == (bits == 2 and own == 1), k
 
 
+_REPLAYPLAN_PROGRAM = r"""
+#include "hb_runplan.hpp"
+#include <cstdio>
+
+static void put(const hb_replay_step &d)
+{
+    printf("%d %d %d | %d %d %d %d\n", (int)d.replay, (int)d.to_per_panel, d.timeout_ms, d.state.aborts, d.state.win_start, d.state.win_count, d.state.slow_timeout);
+}
+
+// a run with recovery on, no HB_TIMEOUT_MS and a context bound of 3000 ms: sweeps[k] = {iteration, aborts of that sweep}
+static void sequence(const char *name, const int (*sweeps)[2], int count)
+{
+    hb_replay_state st{};
+    for (int k = 0; k < count; k++) {
+        const int iter = sweeps[k][0];
+        int bound = replay_first_wait_ms(true, false, 3000, st);
+        bool fell_back = false;
+        for (int attempt = 0; attempt < sweeps[k][1]; attempt++) {
+            const hb_replay_step d = replay_after_abort(true, attempt, fell_back, iter, bound, st);
+            printf("seq %s %d %d %d | %d -> ", name, k, iter, attempt, bound);
+            put(d);
+            if (!d.replay) break;
+            fell_back = fell_back || d.to_per_panel;
+            bound = d.timeout_ms;
+            st = d.state;
+        }
+    }
+}
+
+int main()
+{
+    for (int on = 0; on < 2; on++) for (int pl = 0; pl < 2; pl++) for (int row = 0; row < 2; row++)
+        printf("on %d %d %d | %d\n", on, pl, row, (int)replay_enabled(on, pl, row));
+    for (int rec = 0; rec < 2; rec++) for (int env = 0; env < 2; env++) for (int ctx : {100, 3000, 5000}) for (int slow : {0, 400, 1600, 3000}) {
+        hb_replay_state st{2, 40, 1, slow};
+        const int first = replay_first_wait_ms(rec, env, ctx, st);
+        printf("first %d %d %d %d | %d\n", rec, env, ctx, slow, first);
+        // an abort at iteration 50 of a run whose window opened at 40 with one abort: the bound in force is the sweep's first one at attempt 0, a replay's after it
+        for (int fb = 0; fb < 2; fb++) for (int attempt = 0; attempt <= 4; attempt++) {
+            printf("after %d %d %d %d %d %d | ", rec, env, fb, attempt, ctx, slow);
+            put(replay_after_abort(rec, attempt, fb, 50, attempt == 0 ? first : (first > 3000 ? first : 3000), st));
+        }
+    }
+    static const int escalates[7][2] = {{0, 1}, {10, 1}, {20, 1}, {30, 1}, {40, 1}, {50, 1}, {60, 1}};       // 100 -> 400 -> 1600 -> 3000, capped
+    static const int reset_at_65[5][2] = {{0, 1}, {30, 1}, {65, 1}, {66, 1}, {67, 1}};                       // more than 64 iterations: a new window
+    static const int holds_at_64[3][2] = {{0, 1}, {30, 1}, {64, 1}};                                         // 64 iterations: the same window
+    static const int two_a_window[6][2] = {{0, 1}, {5, 1}, {200, 1}, {205, 1}, {400, 1}, {464, 1}};          // never three: no escalation
+    static const int one_sweep[2][2] = {{7, 4}, {8, 1}};                                                     // the fourth failure of a sweep ends the run
+    static const int stays_raised[4][2] = {{0, 1}, {1, 1}, {2, 1}, {500, 2}};                                // a new window keeps the raised bound
+    sequence("escalates", escalates, 7);
+    sequence("reset_at_65", reset_at_65, 5);
+    sequence("holds_at_64", holds_at_64, 3);
+    sequence("two_a_window", two_a_window, 6);
+    sequence("one_sweep", one_sweep, 2);
+    sequence("stays_raised", stays_raised, 4);
+}
+"""
+
+
+def test_every_replay_decision_equals_the_recorded_policy(tmp_path):
+    """hb_runplan.hpp's "replaying an aborted sweep" (plain C++, compiled here with g++) decides what follows a sweep whose pipeline gave up waiting:
+    whether recovery is on at all, the wait bound a sweep starts with, and after an abort whether to replay, whether to fall back to the per-panel
+    kernels first, the replay's bound and what the run has learnt about the device. Against tests/golden/replay_plan_table.json, which was recorded
+    from the statements as they stood inside hb_run::step() before they became these functions: every combination of recover, HB_TIMEOUT_MS given
+    and fallen back, attempts 0-4, context bounds of 100, 3000 and 5000 ms, and runs of aborts by iteration number. The rows the policy is quoted
+    by are asserted literally as well, read off that code: they guard the recording itself."""
+    import json
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    src, exe = tmp_path / "replayplan.cpp", tmp_path / "replayplan"
+    src.write_text(_REPLAYPLAN_PROGRAM)
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(root, "hibayes_amd", "csrc"), str(src), "-o", str(exe)])
+    got = {}
+    for line in subprocess.check_output([str(exe)]).decode().splitlines():
+        k, v = line.split(" | ", 1)
+        stage, key = k.split(" ", 1)
+        got.setdefault(stage, {})[key] = v
+    want = json.load(open(os.path.join(root, "tests", "golden", "replay_plan_table.json")))
+    assert {k: len(v) for k, v in want.items()} == {"on": 8, "first": 48, "after": 480, "seq": 31}
+    assert set(got) == set(want)
+    for stage, rows in want.items():
+        assert list(got[stage]) == list(rows), "the domains differ: %s" % stage
+        wrong = ["%s: %s, recorded %s" % (k, got[stage][k], w) for k, w in rows.items() if got[stage][k] != w]
+        assert not wrong, "%d rows of '%s' differ from the record, the first:\n%s" % (len(wrong), stage, "\n".join(wrong[:20]))
+
+    # ---- the literal rows ----
+    assert [k for k, v in got["on"].items() if v == "1"] == ["1 1 0"]  # HB_RECOVER on, the persistent pipeline, individuals not sharded
+    for ctx in (100, 3000, 5000):  # the first try waits 100 ms — unless HB_TIMEOUT_MS fixed the bound, the run learnt better, or nothing replays
+        assert got["first"]["1 0 %d 0" % ctx] == "100" and got["first"]["1 0 %d 1600" % ctx] == "1600"
+        assert {got["first"]["%d %d %d 400" % (rec, env, ctx)] for rec, env in ((0, 0), (0, 1), (1, 1))} == {str(ctx)}
+    for k, v in got["after"].items():  # (the state before: 2 sweeps replayed, one abort in the window that iteration 40 opened; the abort is at 50)
+        rec, env, fb, attempt, ctx, slow = (int(x) for x in k.split())
+        first = max(100, slow) if rec and not env else ctx
+        if not rec or attempt >= 3:  # the fourth failure of a sweep ends the run, and so does the first without recovery
+            assert v == "0 0 %d | 2 40 1 %d" % (first if attempt == 0 else max(first, 3000), slow), k
+        else:  # a replay waits 3 s or the bound in force; the second time-out of a sweep falls back, once
+            assert v == "1 %d %d | 3 40 2 %d" % (attempt >= 1 and not fb, max(first, 3000), slow), k
+
+    def slow_after(name):  # per sweep and attempt: (the bound the sweep started with or the replay had, slow_timeout afterwards)
+        return [(int(v.split()[0]), int(v.split()[-1])) for k, v in got["seq"].items() if k.startswith(name + " ")]
+
+    assert slow_after("escalates") == [(100, 0), (100, 0), (100, 400), (400, 1600), (1600, 3000), (3000, 3000), (3000, 3000)]
+    assert slow_after("reset_at_65") == [(100, 0)] * 4 + [(100, 400)] and slow_after("holds_at_64") == [(100, 0), (100, 0), (100, 400)]
+    assert {s for _, s in slow_after("two_a_window")} == {0}
+    assert [v.split(" | ")[0] for k, v in got["seq"].items() if k.startswith("one_sweep 0 ")] == ["100 -> 1 0 3000", "3000 -> 1 1 3000", "3000 -> 1 0 3000", "3000 -> 0 0 3000"]
+    assert got["seq"]["stays_raised 3 500 0"] == "400 -> 1 0 3000 | 4 500 1 400"
+
+
 _MATVECPLAN_PROGRAM = r"""
 #include "hb_matvecplan.hpp"
 #include <cstdio>

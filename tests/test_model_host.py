@@ -94,6 +94,44 @@ int main()
             in >> lds >> m;
             std::vector<double> ss = vec(in);
             printf("%d\n", hb_sumstat_n(ss.data(), lds, m));
+        } else if (what == "prior") { // has_vg has_ve has_dfve has_s2vg has_s2ve vg ve dfve s2vg s2ve dfvara vary h2 nr Pi0 sumvx fold..
+            hb_prior_args p{};
+            in >> p.has_vg >> p.has_ve >> p.has_dfve >> p.has_s2vg >> p.has_s2ve;
+            p.vg = num(in), p.ve = num(in), p.dfve = num(in), p.s2vg = num(in), p.s2ve = num(in);
+            p.dfvara = num(in), p.vary = num(in), p.h2 = num(in);
+            in >> p.nr;
+            p.Pi0 = num(in), p.sumvx = num(in);
+            std::vector<double> fold = vec(in), vf(fold.size(), -1.0);
+            const hb_priors d = hb_prior_defaults(p, fold.data(), (int)fold.size(), vf.data());
+            put("d", {d.vara, d.vare, d.dfvare, d.s2vara, d.varg, d.s2varg, d.s2vare, d.lambda2, d.lambda, d.shape0, d.rate0});
+            put("vara_fold", vf);
+            printf("\n");
+        } else if (what == "sweep") { // model Pi.. fold.. vara_fold.. vare varg s2varg_df dfvara lambda lambda2 iter nburn thin always_in
+            int model, iter, nburn, thin, always_in;
+            in >> model;
+            std::vector<double> Pi = vec(in), fold = vec(in), vf = vec(in);
+            const double vare = num(in), varg = num(in), s2df = num(in), dfvara = num(in), lambda = num(in), lambda2 = num(in);
+            in >> iter >> nburn >> thin >> always_in;
+            const hb_sweep_in s = hb_sweep_params(model, (int)Pi.size(), Pi.data(), fold.data(), vf.data(), vare, varg, s2df, dfvara, lambda, lambda2, iter,
+                                                  nburn, thin, always_in != 0);
+            printf("%d %d %lld %d %d", s.model_index, s.n_fold, (long long)s.iter, s.count_pip, s.store);
+            put("scalars", {s.vare, s.varg, s.s2varg_df, s.dfvara, s.lambda, s.lambda2});
+            put("logpi", std::vector<double>(s.logpi, s.logpi + HB_MAX_FOLD));
+            put("fold", std::vector<double>(s.fold, s.fold + HB_MAX_FOLD));
+            put("vara_fold", std::vector<double>(s.vara_fold, s.vara_fold + HB_MAX_FOLD));
+            printf("\n");
+        } else if (what == "line") { // iter niter NnzSnp Pi.. cls_of.. extras ('_' for a blank, '-' for none) vara vare vt seconds
+            int iter, niter;
+            long long nnz;
+            in >> iter >> niter >> nnz;
+            std::vector<double> Pi = vec(in), cl = vec(in);
+            std::vector<int> cls_of(cl.begin(), cl.end());
+            std::string extras;
+            in >> extras;
+            if (extras == "-") extras.clear();
+            std::replace(extras.begin(), extras.end(), '_', ' ');
+            const double vara = num(in), vare = num(in), vt = num(in), seconds = num(in);
+            printf("[%s]\n", hb_progress_line(iter, niter, nnz, Pi.data(), cls_of.data(), (int)Pi.size(), extras.c_str(), vara, vare, vt, seconds).c_str());
         }
     }
     return 0;
@@ -338,3 +376,81 @@ def test_population_size_is_the_truncated_mean_of_the_finite_n(driver):
         return "n %d %d %s" % (lds, m, _v([x for row in rows for x in row]))
     got = [int(x) for x in driver([case([100.0, 101.0, 103.0]), case([100.0, nan, 103.0, inf, -inf]), case([nan, nan, inf]), case([250.5, 250.5], lds=5)])]
     assert got == [int((100.0 + 101.0 + 103.0) / 3), int((100.0 + 103.0) / 2), 0, 250]
+
+
+def _f(part):
+    """the doubles of one '|name x x ..' part of a driver line, from their hex"""
+    return [float.fromhex(x) for x in part.split()[1:]]
+
+
+# ---- prior defaults, src/Bayes.cpp:327-374 / src/SBayesD.cpp:117-170 ----
+def _priors(has, val, dfvara, vary, h2, nr, pi0, sumvx, fold):
+    """the reference's expressions, operand for operand (restated here, not taken from the header)"""
+    import math
+    vara = val["vg"] if has["vg"] else ((dfvara - 2) / dfvara) * vary * h2
+    vare = val["ve"] if has["ve"] else vary * (1 - h2) / (nr + 1)
+    dfvare = val["dfve"] if has["dfve"] else -2.0
+    s2vara = val["s2vg"] if has["s2vg"] else vara * (dfvara - 2) / dfvara
+    varg = vara / ((1 - pi0) * sumvx)
+    s2varg = s2vara / ((1 - pi0) * sumvx)
+    s2vare = val["s2ve"] if has["s2ve"] else 0.0
+    R2 = (dfvara - 2) / dfvara
+    lambda2 = 2 * (1 - R2) / (R2) * sumvx
+    shape0 = 1.1
+    return [vara, vare, dfvare, s2vara, varg, s2varg, s2vare, lambda2, math.sqrt(lambda2), shape0, (shape0 - 1) / lambda2], [(vara / ((1 - pi0) * sumvx)) * f for f in fold]
+
+
+def test_prior_defaults_are_the_references_expressions(driver):
+    import itertools
+    import math
+    names = ("vg", "ve", "dfve", "s2vg", "s2ve")
+    val = dict(vg=3.7, ve=0.9, dfve=5.5, s2vg=0.0123, s2ve=0.77)
+    dfvara, vary, h2, pi0, sumvx = 4.5, 215.2144812894398, 0.5, 0.95, 321.987654321
+    fold = [0.0, 1e-4, 1e-3, 1e-2]
+    cases = [(dict(zip(names, bits)), nr) for bits in itertools.product((0, 1), repeat=5) for nr in (0, 2)]
+    lines = ["prior %s %s %s %s %s %d %s %s %s" % (" ".join(str(has[k]) for k in names), " ".join(_h(val[k]) for k in names), _h(dfvara), _h(vary), _h(h2),
+                                                    nr, _h(pi0), _h(sumvx), _v(fold)) for has, nr in cases]
+    for line, (has, nr) in zip(driver(lines), cases):
+        _, d, vf = line.split("|")
+        want_d, want_vf = _priors(has, val, dfvara, vary, h2, nr, pi0, sumvx, fold)
+        assert _f(d) == want_d, (has, nr)
+        assert _f(vf) == want_vf, (has, nr)
+    # the random effects share the residual's half of var(y): with two of them the default is a third of it, not all
+    assert _priors(dict.fromkeys(names, 0), val, dfvara, vary, h2, 2, pi0, sumvx, fold)[0][1] == vary * 0.5 / 3 != vary * 0.5
+
+
+def test_sweep_parameters_are_the_chains_state_field_by_field(driver):
+    import math
+    Pi, fold, vf = [0.5, 0.25, 0.125, 0.125], [0.0, 1e-4, 1e-3, 1e-2], [0.0, 2.1e-7, 2.1e-6, 2.1e-5]
+    vare, varg, s2df, dfvara, lam, lam2 = 107.6, 0.0021, 0.0123 * 4.5, 4.5, 7.5, 56.25
+    nburn = 10
+
+    def case(it, thin=3, always_in=0):
+        return "sweep 6 %s %s %s %s %s %s %s %s %s %d %d %d %d" % (_v(Pi), _v(fold), _v(vf), _h(vare), _h(varg), _h(s2df), _h(dfvara), _h(lam), _h(lam2), it, nburn,
+                                                                  thin, always_in)
+    its = [nburn - 1, nburn, nburn + 1, nburn + 2, nburn + 3, nburn + 5]
+    out = driver([case(it) for it in its] + [case(nburn + 2, thin=0), case(nburn + 2, always_in=1), case(nburn + 2, thin=1), case(nburn - 1, thin=1)])
+    pad = lambda xs: list(xs) + [0.0] * (8 - len(xs))
+    for line, it in zip(out, its):
+        head, sc, lp, fo, vfo = line.split("|")
+        assert head.split() == ["6", "4", str(it), str(int(it >= nburn)), str(int(it >= nburn and (it + 1 - nburn) % 3 == 0))], it
+        assert _f(sc) == [vare, varg, s2df, dfvara, lam, lam2]
+        assert _f(lp) == pad([math.log(p) for p in Pi]) and _f(fo) == pad(fold) and _f(vfo) == pad(vf)
+    assert [line.split("|")[0].split()[3:] for line in out[:6]] == [["0", "0"], ["1", "0"], ["1", "0"], ["1", "1"], ["1", "0"], ["1", "1"]]
+    # never a record (the summary level), every marker always in (no PIP counts), every iteration after the burn-in, none before
+    assert [line.split("|")[0].split()[3:] for line in out[6:]] == [["1", "0"], ["0", "1"], ["1", "1"], ["0", "0"]]
+
+
+def test_progress_lines_are_the_references_format(driver):
+    def case(it, niter, nnz, Pi, cls_of, extras, vara, vare, vt, seconds):
+        return "line %d %d %d %s %s %s %s %s %s %s" % (it, niter, nnz, _v(Pi), _v(cls_of), extras.replace(" ", "_") or "-", _h(vara), _h(vare), _h(vt), _h(seconds))
+    out = driver([
+        case(4, 100, 37, [0.95, 0.05], [0, 1], "", 1.23456, 2.5, 1.23456 + 2.5, 2.0),                                    # BayesCpi
+        case(0, 6, 512, [0.5, 0.125, 0.0625, 0.3125], [0, 2, 3, 1], "", 10.0, 30.0, 40.0, 0.25),                         # BayesR, fold = [0, 1e-2, 1e-4, 1e-3]
+        case(11, 12, 1024, [0.0, 1.0], [0, 1], "7.5000 ", 0.5, 1.5, 2.5, 600.0),                                         # BayesL; vt with a random effect's variance
+        case(9, 1000, 3, [0.9, 0.1], [0, 1], "0.1000 0.2000 0.3000 ", 2.0, 2.0, 4.0, 100.0),                             # extras, 9910 s left
+    ])
+    assert out == ["[ 5 37 0.9500 0.0500 1.2346 2.5000 0.3306 00h00m38s]",
+                   "[ 1 512 0.5000 0.3125 0.1250 0.0625 10.0000 30.0000 0.2500 00h00m01s]",
+                   "[ 12 1024 0.0000 1.0000 7.5000 0.5000 1.5000 0.2000 00h00m50s]",
+                   "[ 10 3 0.9000 0.1000 0.1000 0.2000 0.3000 2.0000 2.0000 0.5000 02h45m10s]"]
