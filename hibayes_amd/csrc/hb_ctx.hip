@@ -1089,7 +1089,7 @@ extern "C" int hb_ctx_debug_get_mirrors(hb_ctx *c, int32_t *slot, int32_t *bound
     if (rc) return rc;
     HB_HIP(hipStreamSynchronize(c->stream));
     const size_t s = (size_t)c->upd_slot, ld = (size_t)c->ld;
-    const bool fx = c->precise == 2;
+    const bool fx = c->precise == 2 && c->layout != 64; // (fixed_point()'s rule: the fp64 resident layout maintains no digit planes)
     if (slot) *slot = c->upd_slot;
     if (bound_index) *bound_index = c->upd_mbi;
     if (ndigits) *ndigits = fx ? HB_ND : 0;

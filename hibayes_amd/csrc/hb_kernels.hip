@@ -114,6 +114,12 @@ __global__ void k_sum_partials(const double *__restrict__ partial, int pstride, 
     out[j] = s;
 }
 
+// the sums of a sweep on the per-panel kernels start from zero: stores from a kernel, as k_sweep_init's on the pipeline
+__global__ void k_zero_acc(double *__restrict__ acc)
+{
+    if (threadIdx.x < HB_ACC_N) acc[threadIdx.x] = 0.0;
+}
+
 #include "hb_pre.hpp"
 #include "hb_chain_panel.hpp"
 #include "hb_chain_persist.hpp"
@@ -412,7 +418,9 @@ static int enqueue_sweep_kernels(hb_ctx *c, int model, int n_fold, bool timed)
     const int kp = kpad_for(model, n_fold);
     const int L = c->Lv, np = c->npanels; // per-panel launches: lag Lv with one panel per mat-vec
     hipStream_t sA = c->stream, sB = timed ? c->stream : c->s_chain, sC = timed ? c->stream : c->s_upd;
-    HB_HIP(hipMemsetAsync(c->acc, 0, sizeof(double) * HB_ACC_N, sA));
+    // (not a memset: the second sweep of a context, which replays the captured graph, came back with a 16-byte pattern of non-zero denormals in
+    // the sums no kernel adds to — class counts past the model's classes, tests/test_gpu_real_sweep.py — and so under every sum that one does)
+    hipLaunchKernelGGL(k_zero_acc, dim3(1), dim3(64), 0, sA, c->acc);
     const bool fx = fixed_point(c);
     const bool real = c->layout == 64; // fp64 columns (hb_real.hip): k_dot_real, k_chain on the fp64 Gram block, k_update_real
     if (real && (L != 0 || c->NB != 1 || !c->gramd)) return hb_fail(HB_ERR_INVALID, "the fp64 resident layout runs at lag 0 on its own Gram blocks (hb_ctx_build_gram)");

@@ -11,6 +11,7 @@ import pytest
 import hibayes_amd as H
 from hibayes_amd.engine import Context
 from oracle import oracle as O
+from real_restatement import fma, stats_real
 
 pytestmark = pytest.mark.gpu
 
@@ -298,3 +299,139 @@ def test_refusals_name_the_layout():
             assert ei.value.status == 4 and "fp64 resident layout" in str(ei.value)
         c.upload(np.rint(X).astype(np.int8))      # integer genotypes put the context back on the int8 columns
         assert c.layout()[0] == 8
+
+
+# ---- 10. the statistics at the edges of their row pairs ----
+def vx_bound(X, var_ref):
+    """What k_stats_real may be off by, per column, from its two passes (u = eps / 2 the unit roundoff, eps below absorbs second-order terms).
+    Pass one gives mean_d = mean + dm with |dm| <= n u mean|x|: n - 1 additions in some order and the division. Pass two forms t_i = fl(mean_d -
+    x_i), a2 = sum t_i^2 and a3 = sum t_i, and for ANY mean_d the identity sum (x_i - mean_d)^2 - (sum (x_i - mean_d))^2 / n = S = sum (x_i - mean)^2
+    holds exactly: dm itself cancels, only roundings remain. With T = S + n dm^2 = sum (mean_d - x_i)^2: the roundings of the t_i (2 u T), a2's n
+    fused terms in some order (n u T), a3's sum ((n + 1) u sum |t_i| <= (n + 1) u sqrt(n T), which enters as 2 |dm| times that) and the three
+    operations of the last line (3 u T) — together below 8 n eps (T + |dm| sqrt(n T)), over n - 1. T / (n - 1) is the variance plus mean^2
+    (n eps)^2-sized terms."""
+    n = X.shape[0]
+    dm = n * EPS * np.abs(X).mean(0)
+    T = (n - 1) * var_ref + n * dm * dm
+    return 8 * n * EPS * (T + dm * np.sqrt(n * T)) / (n - 1)
+
+
+@pytest.mark.parametrize("n", [2, 3, 255, 257, 511, 513])
+def test_statistics_at_odd_n_constant_columns_and_a_large_mean(n):
+    """k_stats_real reads pairs of rows; at odd n the second element of the last pair is the zero padding row, which both passes guard with
+    r0 + 1 < n. Without the second guard a (mean - 0)^2 enters the variance: caught here at every odd n. Without the first the padding's 0
+    would be among the extremes of a constant column and the rule mn == mx would not fire — but that cannot be seen from outside: the correction
+    term then brings the variance of a constant column to exactly 0 by itself (all t_i are one number; a host emulation of the kernel's order
+    of sums found no constant and no odd n below 3 100 where it does not), and the extremes go nowhere else on this layout. The assertion on
+    the constant columns therefore pins the result, not the guard. n = 511, 513 are either side of one trip of the 512-row loop. Columns: a constant 0.37 and a
+    constant 1.0 (vx == 0.0 exactly, counted in nvar0), 1e6 + N(0, 1e-3) (the two-pass bound holds; the one-pass n S2 - S1^2 formula, evaluated
+    here in doubles, misses the variance by orders of magnitude more than that bound), and a column that differs from 0.37 in its last row only.
+    xpx: n fused terms in some order, n eps sum x^2."""
+    rng = np.random.default_rng(n)
+    m = 70
+    X = dosages(rng, n, m) if n >= 6 else rng.uniform(0, 2, (n, m))
+    for j in range(m):
+        if X[:, j].min() == X[:, j].max():
+            X[0, j] += 0.25
+    X[:, 11] = 0.37
+    X[:, 12] = 1.0
+    X[:, 13] = 1e6 + rng.normal(0, 1e-3, n)
+    X[:, 14] = 0.37
+    X[n - 1, 14] = 0.38
+    with Context(n, m, panel=64) as c:
+        c.upload_real(X)
+        xpx, vx, sumvx, nvar0 = c.marker_stats()
+    rx, rv = stats_real(X)
+    assert np.all(np.abs(xpx - rx) <= n * EPS * (X * X).sum(0))
+    assert vx[11] == 0.0 and vx[12] == 0.0 and nvar0 == 2 and rv[11] == 0.0 and rv[12] == 0.0
+    bound = vx_bound(X, rv)
+    err = np.abs(vx - rv)
+    print("n=%d: max vx err / bound = %.3g; column 1e6 + N(0, 1e-3): rel err %.3g, bound %.3g" % (n, np.max(err / np.maximum(bound, 1e-300)),
+                                                                                          err[13] / rv[13], bound[13] / rv[13]))
+    assert np.all(err <= bound), (n, np.flatnonzero(err > bound).tolist())
+    assert vx[14] > 0 and bound[13] < 1e-9 * rv[13]
+    s1, s2 = X[:, 13].sum(), (X[:, 13] * X[:, 13]).sum()
+    onepass = (n * s2 - s1 * s1) / (n * (n - 1.0))
+    assert abs(onepass - rv[13]) > 1e3 * bound[13]
+
+
+# ---- 11. X alpha and the GEBV sample matrix on the layout ----
+@pytest.mark.parametrize("n", [2, 255, 257])
+def test_matvec_and_matmul_on_the_real_layout(n):
+    """hb_ctx_matvec (k_xalpha_real) and Context.matmul (k_xmat_real) at m = 300: 320 padded columns, two column blocks of k_xalpha_real, whose
+    block sums meet in atomics — a bound, nnz eps sum |x| |a| (a chain of at most nnz fused terms, then one addition). k_xmat_real has no atomics:
+    per record acc = 0; acc = fma(x_j, a_j, acc) over the columns that carry an effect in any of the pass's eight records, in ascending column
+    order — bit for bit at every n here (n = 257: a second workgroup with one live pair of rows), and the same bound. alpha with 0, 1, 5, 6,
+    7, 8 and 40 non-zeros; 1, 8, 9 and 17 records, record sets of 5, 6, 7, 41 and 3 columns (nnz % 4 = 1, 2, 3, 1, 3: the last batch of four
+    reads its columns through min(e0 + k, nnz - 1) and skips the moves at or past nnz), and at 17 records a whole pass of eight empty ones."""
+    rng = np.random.default_rng(n)
+    m = 300
+    X = dosages(rng, n, m) if n >= 6 else rng.uniform(0, 2, (n, m))
+    X[0, 7] = 1e-310
+    X[n - 1, 290] = -0.0
+    absX = np.abs(X)
+    with Context(n, m, panel=64) as c:
+        c.upload_real(X)
+        assert c.layout()[0] == 64
+        for nnz in (0, 1, 5, 6, 7, 8, 40):
+            alpha = np.zeros(m)
+            cols = np.sort(np.concatenate([rng.choice(256, nnz // 2, replace=False), 256 + rng.choice(m - 256, nnz - nnz // 2, replace=False)]))
+            alpha[cols] = rng.normal(size=nnz)
+            out = np.full(n, np.nan)
+            H._lib.check(c.L.hb_ctx_matvec(c.h, alpha.ctypes.data, out.ctypes.data))
+            want = wide_dot(X.T.copy(), alpha[:, None])[:, 0]
+            lim = nnz * EPS * (absX @ np.abs(alpha))
+            assert np.all(np.abs(out - want) <= lim), (n, nnz)
+            if nnz == 0:
+                assert not out.any()
+        for R, sizes in ((1, [5]), (8, [6]), (9, [7, 8]), (17, [41, 0, 3])):
+            A = np.zeros((m, R))
+            for b, k in enumerate(sizes):
+                cols = rng.choice(m, k, replace=False)
+                recs = np.arange(8 * b, min(R, 8 * b + 8))
+                for j in cols:                                  # every column of the pass's set in one of its records at least, in half of the others
+                    on = rng.random(recs.size) < 0.5
+                    on[rng.integers(recs.size)] = True
+                    A[j, recs[on]] = rng.normal(size=int(on.sum()))
+                assert (np.abs(A[:, recs]).sum(1) != 0).sum() == k
+            out = c.matmul(A)
+            out2 = c.matmul(A)
+            assert out.tobytes() == out2.tobytes()
+            for b in range(len(sizes)):
+                recs = np.arange(8 * b, min(R, 8 * b + 8))
+                support = np.flatnonzero(np.abs(A[:, recs]).sum(1) != 0)
+                for r in recs:
+                    acc = np.zeros(n)
+                    for j in support:
+                        acc = fma(X[:, j], A[j, r], acc)
+                    assert out[:, r].tobytes() == acc.tobytes(), (n, R, int(r), "k_xmat_real in list order")
+                    want = wide_dot(X.T.copy(), A[:, r:r + 1])[:, 0]
+                    assert np.all(np.abs(out[:, r] - want) <= max(1, len(support)) * EPS * (absX @ np.abs(A[:, r]))), (n, R, int(r))
+            if R == 17:
+                assert not out[:, 8:16].any()
+
+
+# ---- 12. genotype_bits = 64 from int8 input ----
+def test_int8_columns_converted_on_the_device_at_odd_n():
+    """k_i8_to_real: every code -128 .. 127 at n = 257 becomes the same number as a double, and the padding rows stay out of the statistics: a
+    constant column of 5s and one of -3s have vx == 0.0 exactly (a padding 0 among the extremes would give them a variance), xpx is the exact
+    integer, vx holds the two-pass bound."""
+    rng = np.random.default_rng(12)
+    n, m = 257, 70
+    X8 = rng.integers(-128, 128, size=(n, m)).astype(np.int8)
+    X8[:256, 0] = np.arange(-128, 128)
+    X8[:, 9] = 5
+    X8[:, 10] = -3
+    X8 = np.asfortranarray(X8)
+    with Context(n, m, panel=64) as c:
+        c.upload(X8)
+        c.set_layout(64)
+        assert c.layout()[0] == 64
+        back = c.download_real()
+        xpx, vx, _, nvar0 = c.marker_stats()
+    Xf = X8.astype(np.float64)
+    assert back.tobytes() == np.asfortranarray(Xf).tobytes()
+    assert np.array_equal(xpx, (X8.astype(np.int64) ** 2).sum(0).astype(np.float64))
+    assert vx[9] == 0.0 and vx[10] == 0.0 and nvar0 == 2
+    rx, rv = stats_real(Xf)
+    assert np.all(np.abs(vx - rv) <= vx_bound(Xf, rv))
