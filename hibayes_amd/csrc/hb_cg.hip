@@ -29,7 +29,9 @@ namespace {
 constexpr int CG_T = 256;            // threads per workgroup, every kernel of this unit
 constexpr int CG_W = CG_T / 64;      // waves per workgroup = dense columns per workgroup
 
-// workgroup-wide sum in a fixed order, the result in every thread; red holds CG_W entries
+// workgroup-wide sum in a fixed order, the result in every thread; red holds CG_W entries. Not hb_wave.hpp's block_sum: this one
+// is for CG_W = 4 waves alone and starts from r0, not from 0 + r0 (a sum of negative zeros keeps its sign), and the unit's
+// bit-for-bit tests rest on the sums it gives today.
 __device__ __forceinline__ double block_sum(double v, double *red)
 {
     v = wave_sum(v);

@@ -59,7 +59,8 @@ inline void mv_plan(int s, int *cpc, int *nchunk)
     *nchunk = (s + *cpc - 1) / *cpc;
 }
 
-// the sum of red[0 .. ET) in a fixed tree; every thread of the workgroup returns it
+// the sum of red[0 .. ET) in a fixed tree; every thread of the workgroup returns it. Not hb_wave.hpp's block_sum: a tree in shared
+// memory over the threads, no wave shuffles — another order, and the recorded decompositions the tests compare with were made with it.
 __device__ __forceinline__ double block_sum(double v, double *red)
 {
     red[threadIdx.x] = v;

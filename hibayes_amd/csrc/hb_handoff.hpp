@@ -1,4 +1,4 @@
-// hb_handoff.hpp — the hand-off words of the persistent pipeline: flag block, agent-scope loads / write-through stores, bounded waits, the abort log; wave and block reductions.
+// hb_handoff.hpp — the hand-off words of the persistent pipeline: flag block, agent-scope loads / write-through stores, bounded waits, the abort log (the wave and block sums are hb_wave.hpp's).
 // Part of the one translation unit hb_kernels.hip (the kernels share device globals and the views defined before them);
 // included there in this order, not compiled on its own.
 #pragma once
@@ -105,21 +105,3 @@ __device__ __forceinline__ bool wait_ge(unsigned *flags, int word, unsigned want
         __builtin_amdgcn_s_sleep(SLEEP);
     }
 }
-
-// ---------------------------------------------------------------------------------------------
-// reductions
-// ---------------------------------------------------------------------------------------------
-// block-wide sum, result valid in every thread; red must hold blockDim.x/64 entries
-template <typename T>
-__device__ __forceinline__ T block_sum(T v, T *red)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-    v = wave_sum(v);
-    __syncthreads();
-    if (lane == 0) red[w] = v;
-    __syncthreads();
-    T s = 0;
-    for (int i = 0; i < nw; i++) s += red[i];
-    return s;
-}
-

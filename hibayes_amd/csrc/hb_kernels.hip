@@ -14,20 +14,21 @@
 //
 // ONE translation unit, by role in included files (round 5; the kernels share device globals — the wait bound, the abort log —
 // and the view structs, which separate objects could only share through relocatable device code):
-//   hand-offs        hb_handoff.hpp        flag block, sc1 loads / write-through stores, bounded waits, reductions
+//   hand-offs        hb_handoff.hpp        flag block, sc1 loads / write-through stores, bounded waits
+//                    hb_wave.hpp           wave and block sums, HB_INF (every unit with kernels includes it)
 //   mat-vec          hb_matvec.hpp         k_dot, k_dotq (int8 columns)        hb_dotq2.hpp   k_dotq2 / k_dotq2r / k_dotq2m (2-bit)
 //                    hb_update.hpp         the residual update rows that ride in the launches, and their dense form
-//   chains           hb_pre.hpp            k_pre (thresholds, deviates)
-//                    hb_chain_panel.hpp    k_chain (one kernel per panel)
+//   per marker       hb_pre.hpp            pre_marker (thresholds, deviates), BayesL's draw, k_windows: shared with hb_sbayes_sparse.hip
+//   chains           hb_chain_panel.hpp    k_chain (one kernel per panel)
 //                    hb_chain_persist.hpp  k_chain_persist, k_hotlist          hb_chain_group.hpp  k_chain_group, k_fwd
 //                    hb_chain_dense.hpp    k_chain_dense, k_fold_dense         hb_warm.hpp         k_gate, k_warm
 //   host blocks      hb_blocks.hpp         intercept / covariates / random effects, delta pack / unpack
-//                    hb_reduce.hpp         var(u), yadj.yadj, BayesL's variances, GWAS windows
+//                    hb_reduce.hpp         var(u), yadj.yadj, BayesL's variances
 //   ingest / egress  hb_stats.hpp          xpx, vx                              hb_ingest.hpp  f64 check, .bed decode, X alpha, GEBV, generator
 //   summary level    hb_sbayes.hpp         SBayesD on a dense LD matrix
 //   host plans       hb_plan.hpp           which chain, k_fwd and warmers a sweep runs (plan_sweep: no HIP, tested on the CPU)
 //                    hb_matvecplan.hpp     which kernel, tiling and LDS a mat-vec launch gets (plan_matvec: the same), the shapes' lists and LDS formulas
-//   this file        sweep start (k_sweep_init, k_quant0), the launch tables, the launchers, graph capture, probes, thin wrappers for hb_ctx.hip
+//   this file        sweep start (k_sweep_init, k_quant0, k_pre), the launch tables, the launchers, graph capture, probes, thin wrappers for hb_ctx.hip
 #include "hb_internal.hpp"
 #include "hb_plan.hpp"
 #include "hb_rng.hpp"
@@ -37,9 +38,8 @@
 #include <map>
 #include <mutex>
 
-#define HB_INF __builtin_huge_val()
-
 #include "hb_handoff.hpp"
+#include "hb_pre.hpp"
 #include "hb_stats.hpp"
 #include "hb_update.hpp"
 #include "hb_matvec.hpp"
@@ -114,13 +114,29 @@ __global__ void k_sum_partials(const double *__restrict__ partial, int pstride, 
     out[j] = s;
 }
 
+// k_pre: pre_marker under the sweep's one residual variance, for the markers [m_offset, m_offset + m) of the whole marker set
+struct pre_view {
+    int m, m_pad;
+    int64_t m_offset;
+    uint64_t seed;
+    const double *xpx, *vx, *g, *vargL;
+    double *thr, *invv, *sdz;
+    int kpad; // thresholds written per marker (1, 3 or 7)
+};
+
+__global__ __launch_bounds__(256) void k_pre(const hb_sweep_in *__restrict__ pin, pre_view v)
+{
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= v.m_pad) return;
+    pre_marker<false>(pin, v, j, pin->vare, v.m_offset + j);
+}
+
 // the sums of a sweep on the per-panel kernels start from zero: stores from a kernel, as k_sweep_init's on the pipeline
 __global__ void k_zero_acc(double *__restrict__ acc)
 {
     if (threadIdx.x < HB_ACC_N) acc[threadIdx.x] = 0.0;
 }
 
-#include "hb_pre.hpp"
 #include "hb_chain_panel.hpp"
 #include "hb_chain_persist.hpp"
 #include "hb_chain_group.hpp"

@@ -16,9 +16,8 @@
 #include "hb_internal.hpp"
 #include "hb_mma.hpp"
 
-#define HBR_INF __builtin_huge_val()
-
-// block-wide sum of 256 threads in a fixed order, valid in every thread; red: 4 doubles
+// block-wide sum of 256 threads in a fixed order, valid in every thread; red: 4 doubles. Not hb_wave.hpp's block_sum: the wave sums
+// are added as (r0 + r1) + (r2 + r3), not in wave order, and the layout's bit-for-bit tests rest on the sums that order gives.
 __device__ __forceinline__ double real_block_sum(double v, double *red)
 {
     v = wave_sum(v);
@@ -34,7 +33,7 @@ __device__ __forceinline__ double real_block_sum(double v, double *red)
 __global__ __launch_bounds__(256) void k_real_check(const double *__restrict__ X, int64_t count, int *__restrict__ bad)
 {
     bool b = false;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x) b |= !(fabs(X[i]) < HBR_INF);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x) b |= !(fabs(X[i]) < HB_INF);
     if (__any(b) && (threadIdx.x & 63) == 0) atomicExch(bad, 1);
 }
 
@@ -56,7 +55,7 @@ __global__ __launch_bounds__(256) void k_stats_real(const double *__restrict__ X
     __shared__ double ext[2][4];
     const int j = blockIdx.x, tid = threadIdx.x;
     const double *col = X + (int64_t)j * ld;
-    double s1 = 0.0, s2 = 0.0, mn = HBR_INF, mx = -HBR_INF;
+    double s1 = 0.0, s2 = 0.0, mn = HB_INF, mx = -HB_INF;
     for (int64_t r0 = (int64_t)tid * 2; r0 < ld; r0 += 512) { // (the padding rows hold zeros: only the extremes need the row count)
         const d2 v = *reinterpret_cast<const d2 *>(col + r0);
         s1 += v.x + v.y;

@@ -1,4 +1,4 @@
-// hb_reduce.hpp — end-of-sweep reductions (src/Bayes.cpp:819, :823), BayesL's per-marker variances, GWAS windows.
+// hb_reduce.hpp — end-of-sweep reductions (src/Bayes.cpp:819, :823), BayesL's per-marker variances (the draw is hb_pre.hpp's).
 // Part of the one translation unit hb_kernels.hip (the kernels share device globals and the views defined before them);
 // included there in this order, not compiled on its own.
 #pragma once
@@ -141,11 +141,8 @@ __global__ __launch_bounds__(256) void k_bayesl_post(const hb_sweep_in *__restri
 {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= m || vx[j] == 0.0) return;
-    const uint64_t sub = hb_sub(HB_PURPOSE_MARKER, (uint64_t)pin->iter);
-    hb_stream st(seed, sub, (uint64_t)(m_offset + j) * HB_BLK_PER_MARKER + 2);
-    const double vargi = 1.0 / st.invgauss(sqrt(pin->vare) * pin->lambda / fabs(g[j]), pin->lambda2);
     // (src/Bayes.cpp:730 keeps vargi >= 0, src/SBayesD.cpp:377 only vargi > 0: `strict` is the summary-level rule)
-    if (strict ? vargi > 0.0 : vargi >= 0.0) vargL[j] = vargi;
+    bayesl_post_marker(pin, seed, m_offset + j, pin->vare, g[j], &vargL[j], strict);
 }
 
 __global__ __launch_bounds__(1024) void k_sum_vec(const double *__restrict__ x, int n, double *__restrict__ out)
@@ -156,12 +153,3 @@ __global__ __launch_bounds__(1024) void k_sum_vec(const double *__restrict__ x, 
     s = block_sum(s, red);
     if (threadIdx.x == 0) *out = s;
 }
-
-__global__ void k_windows(uint8_t *__restrict__ wflag, double *__restrict__ wppa, int nw)
-{
-    const int w = blockIdx.x * blockDim.x + threadIdx.x;
-    if (w >= nw) return;
-    wppa[w] += (double)wflag[w];
-    wflag[w] = 0;
-}
-

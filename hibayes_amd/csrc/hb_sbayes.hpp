@@ -1,6 +1,8 @@
 // hb_sbayes.hpp — device side of the summary-level sampler on a dense LD matrix (reference src/SBayesD.cpp:251-470).
 // Included by hb_kernels.hip (it reuses k_pre — the same six conditionals restated as thresholds on q = rhs^2 — k_bayesl_post,
-// the wave helpers and the Philox layer); the host loop is hb_sbayes.hip.
+// the wave helpers and the Philox layer); the host loop is hb_sbayes.hip. The sparse sampler (hb_sbayes_sparse.hip) takes the
+// per-marker arithmetic from the same header, hb_pre.hpp; its k_ss_group repeats k_sb_group's round scaffolding in its own text:
+// moved into shared functions it gave the same bits but 2 - 3 us more per group launch (profiles/sbayes_shared_refactor.txt).
 //
 // The reference keeps the right-hand sides of ALL markers in Gram space: r_hat = xy - n ldm g, and after marker i moves
 // r_hat += n (g_old - g_new) ldm[:, i] (an m-long daxpy, :262-266) before marker i + 1 reads r_hat[i + 1]. Here a sweep runs in

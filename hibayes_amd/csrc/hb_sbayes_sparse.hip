@@ -1,8 +1,9 @@
 // hb_sbayes_sparse.hip — device side of the summary-level sampler on a SPARSE LD matrix: SBayesS() of the reference
 // (src/SBayesS.cpp:277-600) from the handle's device CSC (hb_ldm_device_csc: int64 column pointers, int32 rows sorted inside a
-// column, fp64 values). The host loop is hb_sbayes.hip (hb_sbayes_run_sparse). A unit of its own: it brings its own copies of the kernels
-// it shares with hb_kernels.hip (k_pre's thresholds, k_bayesl_post), so that the chain kernels' unit gains no instantiation; the
-// wave helpers are hb_wave.hpp's.
+// column, fp64 values). The host loop is hb_sbayes.hip (hb_sbayes_run_sparse). A unit of its own, so that the chain kernels' unit gains
+// no instantiation; what it shares with hb_kernels.hip it includes: the per-marker coefficients, BayesL's draw and the windows' kernel
+// (hb_pre.hpp), the wave and block sums (hb_wave.hpp). k_ss_group keeps its own text of k_sb_group's round scaffolding (hb_sbayes.hpp
+// says why).
 //
 // SBayesS() is not SBayesD() with zeros: marker i is sampled under its own residual variance varei = varediff[i] vara + vare
 // (:285), BayesC / BayesCpi / BayesR effects with g^2 vx > vary are redrawn, at most 101 times (:388-398, :489-499), and a move
@@ -23,27 +24,11 @@
 // One sweep = 2 ceil(m / 512) + 3 launches (+ 1 for BayesL), captured once and replayed.
 #include "hb_sbayes_sparse.hpp"
 #include "hb_plan.hpp"
-#include "hb_rng.hpp"
-#include "hb_wave.hpp"
-
-#define HB_INF __builtin_huge_val()
+#include "hb_pre.hpp"
 
 namespace {
 
-// block-wide sum, result valid in every thread; red must hold blockDim.x / 64 entries
-__device__ __forceinline__ double block_sum(double v, double *red)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-    v = wave_sum(v);
-    __syncthreads();
-    if (lane == 0) red[w] = v;
-    __syncthreads();
-    double s = 0;
-    for (int i = 0; i < nw; i++) s += red[i];
-    return s;
-}
-
-// The inclusion test on q = rhs^2. k_pre's threshold form "q >= thr" comes from multiplying s1 - s0 >= log((1 - U) / U) by
+// The inclusion test on q = rhs^2. pre_marker's threshold form "q >= thr" comes from multiplying s1 - s0 >= log((1 - U) / U) by
 // 2 v varei, which the reference's own chain can make NEGATIVE: on an indefinite (thresholded) matrix g' ldm g, and with it the
 // sweep's Vg and then Ve, can be drawn below zero (src/SBayesS.cpp:531, :538). The reference goes on — the inequality turns round
 // (sg < 0: included <=> q <= thr), and where log(varg lhs + 1), sqrt(varei / v) or the right-hand side itself is NaN,
@@ -76,55 +61,8 @@ struct ss_view {
     int kpad;
 };
 
-// the boundary between BayesR's classes <= c and > c as a threshold on q = rhs^2 (hb_pre.hpp's bayesr_threshold)
-__device__ double ss_bayesr_threshold(int K, int c, const double *a, const double *b, double logT)
-{
-    auto h = [&](double q, double &dh) {
-        double mA = -HB_INF, mB = -HB_INF;
-        for (int i = 0; i < K; i++) {
-            const double s = a[i] + b[i] * q;
-            if (i <= c) mA = fmax(mA, s); else mB = fmax(mB, s);
-        }
-        double sA = 0, sB = 0, dA = 0, dB = 0;
-        for (int i = 0; i < K; i++) {
-            const double s = a[i] + b[i] * q;
-            if (i <= c) { const double w = s == mA ? 1.0 : exp(s - mA); sA += w; dA += b[i] * w; }
-            else        { const double w = s == mB ? 1.0 : exp(s - mB); sB += w; dB += b[i] * w; }
-        }
-        dh = dB / sB - dA / sA;
-        return (mB + (sB == 1.0 ? 0.0 : log(sB))) - (mA + (sA == 1.0 ? 0.0 : log(sA))) - logT;
-    };
-    double dh;
-    double h0 = h(0.0, dh);
-    if (!(h0 < 0.0)) return 0.0;
-    if (!(dh > 0.0)) return HB_INF;
-    double lo = 0.0, hi = -h0 / dh;
-    if (!(hi > 0.0)) hi = 1.0;
-    double hh = h(hi, dh);
-    int guard = 0;
-    while (hh < 0.0 && guard++ < 200) {
-        lo = hi;
-        hi *= 2.0;
-        hh = h(hi, dh);
-    }
-    if (hh < 0.0) return HB_INF;
-    double q = hi;
-    for (int it = 0; it < 100; it++) {
-        double d;
-        const double hv = h(q, d);
-        if (hv < 0.0) lo = q; else hi = q;
-        const double step = hv / d;
-        if (fabs(step) <= 4e-16 * fabs(q)) break;
-        double qn = q - step;
-        if (!(qn > lo && qn < hi)) qn = 0.5 * (lo + hi);
-        if (fabs(qn - q) <= 4e-16 * fabs(qn) || hi - lo <= 4e-16 * hi) { q = qn; break; }
-        q = qn;
-    }
-    return q;
-}
-
-// k_pre with the marker's own varei = varediff[i] vara + vare (:285, :307, :331, :372, :423, :456) where k_pre has vare; also
-// the sweep's start: every row's place in its column back to 0, no marker redrawn yet
+// pre_marker with the marker's own varei = varediff[i] vara + vare (src/SBayesS.cpp:285) where k_pre has vare; also the sweep's start:
+// every row's place in its column back to 0, no marker redrawn yet, every sign +1
 __global__ __launch_bounds__(256) void k_ss_pre(const hb_sweep_in *__restrict__ pin, ss_view v)
 {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
@@ -135,83 +73,9 @@ __global__ __launch_bounds__(256) void k_ss_pre(const hb_sweep_in *__restrict__ 
     }
     v.cursor[j] = 0;
     v.sgn[j] = 1.0;
-    const int kp = v.kpad;
-    const bool active = (j < v.m) && (v.vx[j] != 0.0);
-    if (!active) {
-        for (int c = 0; c < kp; c++) {
-            v.thr[(int64_t)c * v.m_pad + j] = HB_INF;
-            v.invv[(int64_t)c * v.m_pad + j] = 0.0;
-            v.sdz[(int64_t)c * v.m_pad + j] = 0.0;
-        }
-        v.varei[j] = 0.0;
-        return;
-    }
-    const int model = pin->model_index;
-    const double vare = v.varediff[j] * v.ex[0] + pin->vare;
+    const double vare = pre_active(v, j) ? v.varediff[j] * v.ex[0] + pin->vare : 0.0;
     v.varei[j] = vare;
-    const uint64_t sub = hb_sub(HB_PURPOSE_MARKER, (uint64_t)pin->iter);
-    const uint64_t base = (uint64_t)j * HB_BLK_PER_MARKER;
-    const double xx = v.xpx[j];
-    const double gold = v.g[j];
-    const double z = hb_normal_blk(v.seed, sub, base + 1);
-
-    if (model == 6) {
-        const int K = pin->n_fold;
-        const double U = hb_uniform_blk(v.seed, sub, base + 0);
-        const double logT = log((1.0 - U) / U);
-        double a[HB_MAX_FOLD], b[HB_MAX_FOLD];
-        a[0] = pin->logpi[0];
-        b[0] = 0.0;
-        const double lhs = xx / vare;
-        for (int c = 1; c < K; c++) {
-            const double vf = pin->vara_fold[c];
-            const double vv = xx + vare / vf; // :462, :487
-            a[c] = -0.5 * log(vf * lhs + 1.0) + pin->logpi[c];
-            b[c] = 0.5 / (vv * vare);
-            v.invv[(int64_t)(c - 1) * v.m_pad + j] = 1.0 / vv;
-            v.sdz[(int64_t)(c - 1) * v.m_pad + j] = sqrt(vare / vv) * z;
-        }
-        double prev = 0.0;
-        for (int c = 0; c < K - 1; c++) { // boundaries are nested: thr_0 <= thr_1 <= ...
-            prev = fmax(prev, ss_bayesr_threshold(K, c, a, b, logT));
-            v.thr[(int64_t)c * v.m_pad + j] = prev;
-        }
-        for (int c = K - 1; c < kp; c++) {
-            v.thr[(int64_t)c * v.m_pad + j] = HB_INF;
-            v.invv[(int64_t)c * v.m_pad + j] = 0.0;
-            v.sdz[(int64_t)c * v.m_pad + j] = 0.0;
-        }
-        return;
-    }
-
-    double varg = pin->varg;
-    if (model == 2 || model == 3) { // per-marker variance, :308 / :332 — drawn from g of the previous sweep
-        hb_stream st(v.seed, sub, base + 4);
-        varg = (gold * gold + pin->s2varg_df) / st.chisq(pin->dfvara + 1.0);
-    }
-    double vv;
-    if (model == 5) vv = xx + 1.0 / v.vargL[j]; // :427 (and sqrt(varei / v), :428)
-    else vv = xx + vare / varg;                 // :289, :313, :346, :386
-    double thr = -HB_INF;
-    if (model == 3 || model == 4) {
-        const double U = hb_uniform_blk(v.seed, sub, base + 0);
-        const double logdetV = log(varg * (xx / vare) + 1.0), w = 2.0 * vv * vare;
-        if (logdetV != logdetV || w != w) {
-            thr = -HB_INF; // s1 is NaN (a negative or NaN variance): `uniform < acceptProb` is false, the marker is in (:380-383)
-        } else {
-            thr = w * (log((1.0 - U) / U) + 0.5 * logdetV - pin->logpi[1] + pin->logpi[0]);
-            if (thr != thr) thr = HB_INF; // inf - inf when both log(pi) are -inf: never include
-            else if (w < 0.0) v.sgn[j] = -1.0;
-        }
-    }
-    v.thr[j] = thr;
-    v.invv[j] = 1.0 / vv;
-    v.sdz[j] = sqrt(vare / vv) * z;
-    for (int c = 1; c < kp; c++) {
-        v.thr[(int64_t)c * v.m_pad + j] = HB_INF;
-        v.invv[(int64_t)c * v.m_pad + j] = 0.0;
-        v.sdz[(int64_t)c * v.m_pad + j] = 0.0;
-    }
+    pre_marker<true>(pin, v, j, vare, j);
 }
 
 // BayesL: vargL_j <- 1 / InvGauss(sqrt(varei_j) lambda / |g_j|, lambda^2), kept when > 0 (:430-431)
@@ -219,10 +83,7 @@ __global__ __launch_bounds__(256) void k_ss_bayesl_post(const hb_sweep_in *__res
 {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= v.m || v.vx[j] == 0.0) return;
-    const uint64_t sub = hb_sub(HB_PURPOSE_MARKER, (uint64_t)pin->iter);
-    hb_stream st(v.seed, sub, (uint64_t)j * HB_BLK_PER_MARKER + 2);
-    const double vargi = 1.0 / st.invgauss(sqrt(v.varei[j]) * pin->lambda / fabs(v.g[j]), pin->lambda2);
-    if (vargi > 0.0) v.vargL[j] = vargi;
+    bayesl_post_marker(pin, v.seed, j, v.varei[j], v.g[j], &v.vargL[j], 1);
 }
 
 template <int K1>
@@ -502,14 +363,6 @@ __global__ void k_ss_varediff(const int32_t *__restrict__ cnt, int m, double *__
     if (j < m) out[j] = ((double)m - (double)cnt[j]) / (double)m; // :140
 }
 
-__global__ void k_ss_windows(uint8_t *__restrict__ wflag, double *__restrict__ wppa, int nw)
-{
-    const int w = blockIdx.x * blockDim.x + threadIdx.x;
-    if (w >= nw) return;
-    wppa[w] += (double)wflag[w];
-    wflag[w] = 0;
-}
-
 } // namespace
 
 // ---- launchers (hb_sbayes.hip owns the buffers: struct hb_ss_dev) ----
@@ -538,7 +391,7 @@ int hbk_ss_enqueue_sweep(hb_ss_dev *s, int model, int n_fold)
 int hbk_ss_windows(hb_ss_dev *s)
 {
     hb_sb_dev *d = &s->b;
-    if (d->nw) hipLaunchKernelGGL(k_ss_windows, dim3((d->nw + 255) / 256), dim3(256), 0, d->stream, d->wflag, d->wppa, d->nw);
+    if (d->nw) hipLaunchKernelGGL(k_windows, dim3((d->nw + 255) / 256), dim3(256), 0, d->stream, d->wflag, d->wppa, d->nw);
     HB_HIP(hipGetLastError());
     return HB_OK;
 }

@@ -1,7 +1,10 @@
-// hb_wave.hpp — what every unit with kernels uses of one 64-lane wave: the shuffle sum, a lane's double read as a scalar, and the
-// short vector types of the MFMA operands and 16-byte loads. One text for the chain kernels' unit and the units beside it.
+// hb_wave.hpp — what every unit with kernels uses of one 64-lane wave: the shuffle sum and the block sum built on it, a lane's double
+// read as a scalar, the short vector types of the MFMA operands and 16-byte loads, and HB_INF. One text for the chain kernels' unit
+// and the units beside it.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#define HB_INF __builtin_huge_val()
 
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
@@ -24,6 +27,21 @@ __device__ __forceinline__ long long wave_sum(long long v)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
+}
+
+// block-wide sum, result valid in every thread; red must hold blockDim.x/64 entries. The wave sums are added in wave order: the
+// order that the bit-for-bit tests of the sweeps and of both summary-level samplers rest on.
+template <typename T>
+__device__ __forceinline__ T block_sum(T v, T *red)
+{
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+    v = wave_sum(v);
+    __syncthreads();
+    if (lane == 0) red[w] = v;
+    __syncthreads();
+    T s = 0;
+    for (int i = 0; i < nw; i++) s += red[i];
+    return s;
 }
 
 __device__ __forceinline__ double readlane_f64(double v, int k)
