@@ -281,6 +281,8 @@ SYMBOLS = [
     "hb_epsl_check", "hb_epsl_plan", "hb_bayes_run_epsl", "hb_run_epsl", "hb_run_epsl_store",
     # ssbrm()'s imputation, R/ssbayes.r:295-307, as a batched conjugate-gradient solve (hb_impute.hip)
     "hb_impute_create", "hb_impute_solve", "hb_impute_destroy",
+    # make_grm(inverse=TRUE): solve() -> solver_chol(), src/solver.cpp:159-202 (dpotrf, dpotri, the mirror), hb_chol.hip
+    "hb_chol_factor", "hb_chol_invert_factor", "hb_spd_inverse", "hb_chol_plan",
 ]
 
 
@@ -436,6 +438,10 @@ def lib():
     L.hb_eig_release.restype = None
     L.hb_eig_destroy.argtypes = [vp]
     L.hb_eig_destroy.restype = None
+    L.hb_chol_factor.argtypes = [vp, i64, i32, i32, dbl, C.POINTER(i32)]
+    L.hb_chol_invert_factor.argtypes = [vp, i64, i32, i32]
+    L.hb_spd_inverse.argtypes = [vp, i64, i32, i32, dbl, C.POINTER(i32)]
+    L.hb_chol_plan.argtypes = [i32, i32] + [vp] * 8
     _lib = L
     return L
 

@@ -34,7 +34,7 @@ def make_grm(M, lambda_=0.0, inverse=False, eigen=False, verbose=True, *, device
     """Mirror of make_grm() (reference src/rm.cpp:5-53). `M` is the n x m genotype matrix (int8 preferred, or integer-valued floats)
     or an engine.Context with the genotypes already resident. Returns G, or with eigen=True the pair (eigenvalues, eigenvectors) in
     numpy.linalg.eigh's ascending order. As in the reference, `lambda_` is added to the diagonal before the decomposition (:46) and
-    is not part of the plain G. inverse=True (solve(), :39-42) is not implemented.
+    is not part of the plain G. inverse=True (solve(), :39-42) is not routed through make_grm(): grm_inverse() (hibayes_amd/chol.py) returns it.
     eigen_solver: "host" (default) decomposes G with numpy.linalg.eigh; "device" with hibayes_amd.eig — G goes from hb_grm_build straight
     into the reduction and never visits the host. keep_on_device=True (eigen_solver="device" only) returns an eig.EigVectors handle
     (.values, .toarray(), .close()) instead of the pair, for Context.poly_setup(). tridiagonal (eigen_solver="device" only): "host" (default)
@@ -47,7 +47,7 @@ def make_grm(M, lambda_=0.0, inverse=False, eigen=False, verbose=True, *, device
     if keep_on_device and not (eigen and eigen_solver == "device"):
         raise ValueError("make_grm: keep_on_device=True goes with eigen=True, eigen_solver=\"device\"")
     if inverse:
-        raise NotImplementedError("make_grm(inverse=True) is not implemented: only G and its eigen-decomposition are")
+        raise NotImplementedError("make_grm(inverse=True) (solve(), src/rm.cpp:39-42) is not routed through make_grm(): call grm_inverse()")
     from .engine import Context
     own = not isinstance(M, Context)
     if own:

@@ -497,7 +497,7 @@ int hb_cg_run_sparse(const hb_cg_args *args, hb_ldm *ldm, hb_cg_out *out);
  * two builds agree bit for bit. G_host: n x n column-major or NULL; G_dev: NULL, or receives a device copy (leading dimension n) that
  * the caller releases with hb_grm_free. flags: HB_GRM_RAW = the centred cross-product Z Z' itself, no scaling and no lambda.
  * All markers monomorphic (mean diagonal 0; the reference returns NaN): HB_ERR_INVALID. The n x n matrix not fitting on the device:
- * HB_ERR_HIP with "out of memory" in the text. The inverse is not part of the library; the eigen-decomposition is hb_eig_* below.
+ * HB_ERR_HIP with "out of memory" in the text. The inverse (make_grm(inverse = TRUE)) is hb_spd_inverse on G_dev, further below; the eigen-decomposition is hb_eig_*.
  * ------------------------------------------------------------------------------------ */
 #define HB_GRM_RAW 1
 int hb_grm_build(hb_ctx *c, double lambda, int32_t flags, double *G_host, double **G_dev);
@@ -556,6 +556,32 @@ int hb_eig_download(const double *M_dev, int64_t ld_dev, int32_t n, int32_t devi
 void hb_eig_release(double *M_dev);
 /* Ends the borrowing of A_dev and frees the handle's panels (src/rm.cpp:46-52 keeps nothing either). NULL is allowed. */
 void hb_eig_destroy(hb_eig *h);
+
+/* ------------------------------------------------------------------------------------
+ * The inverse behind make_grm(inverse = TRUE) (reference src/rm.cpp:39-42: solve() -> solver_chol(), src/solver.cpp:159-202: LAPACK dpotrf('L'),
+ * dpotri('L') and the mirror) on the device: a right-looking blocked Cholesky, the factor's inverse (dtrtri) and the
+ * product (dlauum), GEMM-shaped on the fp64 matrix cores. Matrices are n x n column-major fp64 device matrices of the interface above
+ * (hb_eig_upload / hb_eig_download / hb_eig_release) or hb_grm_build's G_dev (lda = n). No floating-point atomics: two runs on the same matrix
+ * agree bit for bit; no kernel waits for another workgroup. Refused before any device is asked for, HB_ERR_INVALID: a null pointer, n < 1,
+ * lda < n, a non-finite lambda. Without a device: HB_ERR_NO_DEVICE. A work buffer that does not fit: HB_ERR_HIP with "out of memory" in the
+ * text. solver_lu() (src/solver.cpp:204-249), the route the reference takes when dpotrf fails, stays with the caller (*info > 0).
+ * ------------------------------------------------------------------------------------ */
+/* dpotrf('L') in place: the lower triangle of A_dev + lambda*I becomes L; the strict upper triangle is neither read nor written.
+ * *info = 0, or k > 0: the leading minor of order k is not positive definite (or its pivot is not finite); A_dev is then as the
+ * factorisation left it. Returns HB_OK in both cases. */
+int hb_chol_factor(double *A_dev, int64_t lda, int32_t n, int32_t device, double lambda, int32_t *info);
+/* dtrtri('L','N') in place on hb_chol_factor's result */
+int hb_chol_invert_factor(double *L_dev, int64_t lda, int32_t n, int32_t device);
+/* solver_chol() (src/solver.cpp:159-202): A_dev <- (A_dev + lambda*I)^-1, both triangles, from A_dev's lower triangle. Works in a
+ * buffer of its own: with *info > 0 (HB_OK) A_dev is untouched bit for bit, so the caller can take solver_lu()'s route. The result
+ * equals its transpose bit for bit. Allocates bytes[2] of hb_chol_plan for the call: a second n x n matrix and an n x 256 block column. */
+int hb_spd_inverse(double *A_dev, int64_t lda, int32_t n, int32_t device, double lambda, int32_t *info);
+/* The plan of hb_cholplan.hpp for the tests, a pure function of n that needs no device: *nb the panel width, *ldw the work buffer's leading
+ * dimension (even), bytes[3] what hb_chol_factor, hb_chol_invert_factor and hb_spd_inverse allocate, and per panel of the factorisation
+ * (*nsteps of them; cap: the length of every array, ceil(n / 64) suffices) its first column k0, its width, the 64-row tiles of the panel
+ * below its diagonal block and the 64 x 64 tiles of the trailing matrix's lower triangle. */
+int hb_chol_plan(int32_t n, int32_t cap, int32_t *nb, int64_t *ldw, int64_t *bytes, int32_t *nsteps, int32_t *k0, int32_t *width, int32_t *row_tiles,
+                 int64_t *tri_tiles);
 
 /* ====================================================================================
  * Fine-grained engine API.  hb_bayes_run() is built on it; the parity tests and bench.py
