@@ -1101,6 +1101,42 @@ extern "C" int hb_ctx_debug_get_mirrors(hb_ctx *c, int32_t *slot, int32_t *bound
     return HB_OK;
 }
 
+extern "C" int hb_ctx_debug_get_cert(hb_ctx *c, int32_t *ok, int32_t *Lg, int32_t *ga, int32_t *gB, int32_t *gcmax)
+{
+    int rc = check_cols(c, 0, 0, "hb_ctx_debug_get_cert");
+    if (rc) return rc;
+    HB_HIP(hipStreamSynchronize(c->stream));
+    // (gram_ready: an upload or a wider geometry since the build leaves arrays no sweep will use — the next one builds the band again first)
+    const bool have = c->gcert_ok && c->gram_ready && c->layout != 64 && c->ga && c->gB && c->gcmax;
+    if (ok) *ok = have ? 1 : 0;
+    if (Lg) *Lg = c->Lg;
+    if (!have) return HB_OK;
+    const size_t bytes = sizeof(int32_t) * (size_t)c->m_pad;
+    if (ga) HB_HIP(hipMemcpy(ga, c->ga, bytes, hipMemcpyDeviceToHost));
+    if (gB) HB_HIP(hipMemcpy(gB, c->gB, bytes, hipMemcpyDeviceToHost));
+    if (gcmax) HB_HIP(hipMemcpy(gcmax, c->gcmax, bytes, hipMemcpyDeviceToHost));
+    return HB_OK;
+}
+
+extern "C" int hb_ctx_debug_get_opening(hb_ctx *c, int32_t *nslot, double *kappa, double *candf, int32_t *has_opn, float *thr0f, int32_t *opn,
+                                        int32_t *slot_of, int32_t *hotpack)
+{
+    int rc = check_cols(c, 0, 0, "hb_ctx_debug_get_opening");
+    if (rc) return rc;
+    if (c->hot_ns < 0) return hb_fail(HB_ERR_INVALID, "hb_ctx_debug_get_opening: no pipelined sweep has run on this context");
+    HB_HIP(hipStreamSynchronize(c->stream));
+    const size_t mp = (size_t)c->m_pad;
+    if (nslot) *nslot = c->hot_ns;
+    if (kappa) *kappa = c->kappa;
+    if (candf) *candf = c->candf;
+    if (has_opn) *has_opn = c->hot_opn ? 1 : 0;
+    if (thr0f) HB_HIP(hipMemcpy(thr0f, c->thr0f, sizeof(float) * mp, hipMemcpyDeviceToHost));
+    if (opn && c->hot_opn) HB_HIP(hipMemcpy(opn, c->opn, sizeof(int4) * mp, hipMemcpyDeviceToHost));
+    if (slot_of) HB_HIP(hipMemcpy(slot_of, c->hot_slot, sizeof(int32_t) * mp, hipMemcpyDeviceToHost));
+    if (hotpack) HB_HIP(hipMemcpy(hotpack, c->hot_list, sizeof(int32_t) * (size_t)c->npanels * 256, hipMemcpyDeviceToHost));
+    return HB_OK;
+}
+
 int hb_ctx_residual_sums(hb_ctx *c, double *sum_r, double *sum_r2)
 {
     int rc = check_cols(c, 0, 0, "hb_ctx_residual_sums");

@@ -106,6 +106,8 @@ struct hb_ctx {
     unsigned int *flags = nullptr; // [0] chain_done (panels whose moves are published), [1] abort
     unsigned int *h_flags = nullptr;
     int *hot_slot = nullptr, *hot_list = nullptr, *hot_n = nullptr; // per-sweep row-cache lists (k_hotlist): hot_list is packed, 256 ints per panel
+    int hot_ns = -1;                                                 // the nslot the last pipelined sweep's k_hotlist was given (-1: none has run), ...
+    bool hot_opn = false;                                            // ... and whether it wrote the opn records (hb_ctx_debug_get_opening)
     float *thr0f = nullptr;                                          // per-sweep opening filter of the chain (k_hotlist)
     int4 *opn = nullptr;                                             // per-sweep, 16 bytes per marker: {candidate threshold (double), opening filter (float), gB}: what k_chain_group's opening needs that no other workgroup of the sweep writes — staged in its LDS a group ahead (k_hotlist writes it)
     int64_t ld = 0; // bytes per genotype column on device (multiple of 256)

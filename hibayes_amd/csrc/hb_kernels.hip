@@ -553,6 +553,9 @@ __global__ void k_inject_abort(unsigned *flags, unsigned panel)
 // move when it starts, so its corrections start from zero and its version ring from slot 0. `first` also prepares the
 // per-sweep data (k_pre, k_hotlist, zeroed sums), `last` closes the sweep (BayesL's variances, the residual's sums).
 // env_alone: HB_CHAIN_ALONE, read once per sweep by hb_sweep_enqueue.
+// the rows of the chain's row cache k_hotlist lays its lists out for
+static int hotlist_nslot(const hb_ctx *c, int kp) { return std::max(0, persist_nslot(c->P, std::min(c->L, HB_LBMAX), kp)); }
+
 static int enqueue_sweep_pipeline(hb_ctx *c, int model, int n_fold, int pb, int pe, bool first, bool last, bool env_alone)
 {
     const int kp = kpad_for(model, n_fold);
@@ -596,7 +599,9 @@ static int enqueue_sweep_pipeline(hb_ctx *c, int model, int n_fold, int pb, int 
         pre_view pvw{c->m, c->m_pad, c->m_offset, c->seed, c->xpx, c->vx, c->g, c->vargL, c->thr, c->invv, c->sdz, kp};
         hipLaunchKernelGGL(k_pre, dim3((c->m_pad + 255) / 256), dim3(256), 0, sA, c->d_in, pvw);
     }
-    const int ns = std::max(0, persist_nslot(c->P, std::min(c->L, HB_LBMAX), kp));
+    // (the per-panel chain is launched with persist_nslot(P, L, kp) below: the same number, since plan_sweep gives a band beyond HB_LBMAX to the
+    // group chain only — tests/test_opening_host.py walks the plans for it)
+    const int ns = hotlist_nslot(c, kp);
     // (the hot lists are rebuilt for every range: they hold the effects as they are when the range starts)
     hipLaunchKernelGGL(k_hotlist, dim3(c->npanels), dim3(c->P), 0, sA, c->d_in, c->vx, c->g, c->thr, c->xpx, c->kappa, c->P, ns, c->hot_slot,
                        c->hot_list, c->thr0f, c->tracker, (c->gcert_ok && c->gB) ? c->opn : nullptr, c->gB, c->candf);
@@ -748,6 +753,9 @@ int hb_sweep_enqueue(hb_ctx *c, const hb_sweep_in *in, bool timed)
     if (c->pipeline) {
         const int ngroups = (pe - pb + c->D - 1) / c->D;
         c->upd_slot = ngroups & 1, c->upd_mbi = pb / c->D + ngroups - 1;
+        // (what hb_ctx_debug_get_opening reports: k_hotlist's arguments in enqueue_sweep_pipeline, whether launched now or replayed from a graph)
+        c->hot_ns = hotlist_nslot(c, kpad_for(in->model_index, in->n_fold));
+        c->hot_opn = c->gcert_ok && c->gB;
     }
     const bool first = c->rng_pe ? c->rng_first : true, last = c->rng_pe ? c->rng_last : true;
     const bool env_alone = getenv("HB_CHAIN_ALONE") != nullptr; // (tools/chain_timeline.py sets it in the middle of a run)

@@ -139,6 +139,29 @@ class Context:
         return {"slot": slot.value, "bound_index": h.value, "r": r, "r32": r32, "rq": rq if nd.value else None,
                 "vexp": ve.value if nd.value else None, "mb": mb}
 
+    def cert(self):
+        """Debug read-out: the group chain's certificate as build_gram() left it, as a dict — ok (False: there is none, the arrays are None), Lg
+        (the band it was built over), ga, gB, gcmax (m_pad int32 each: G[k][j] = ga[k] gB[j] + c[k][j], |c[k][j]| <= gcmax[k])."""
+        m_pad = -(-self.m // self.panel) * self.panel
+        a = [np.zeros(m_pad, dtype=np.int32) for _ in range(3)]
+        ok, lg = C.c_int32(), C.c_int32()
+        check(self.L.hb_ctx_debug_get_cert(self.h, C.byref(ok), C.byref(lg), *[x.ctypes.data for x in a]))
+        ga, gB, gcmax = a if ok.value else (None, None, None)
+        return {"ok": bool(ok.value), "Lg": lg.value, "ga": ga, "gB": gB, "gcmax": gcmax}
+
+    def opening(self):
+        """Debug read-out: what k_hotlist wrote for the chain of the last pipelined sweep, as a dict — nslot, kappa, candf, thr0f (m_pad
+        floats), opn (m_pad x 4 int32 records, None where none were written), slot_of (m_pad int32) and hotpack (npanels x 256 int32)."""
+        P = self.panel
+        npan = -(-self.m // P)
+        thr0f, opn = np.zeros(npan * P, dtype=np.float32), np.zeros((npan * P, 4), dtype=np.int32)
+        slot_of, hotpack = np.zeros(npan * P, dtype=np.int32), np.zeros((npan, 256), dtype=np.int32)
+        ns, has, ka, cf = C.c_int32(), C.c_int32(), C.c_double(), C.c_double()
+        check(self.L.hb_ctx_debug_get_opening(self.h, C.byref(ns), C.byref(ka), C.byref(cf), C.byref(has), thr0f.ctypes.data, opn.ctypes.data,
+                                              slot_of.ctypes.data, hotpack.ctypes.data))
+        return {"nslot": ns.value, "kappa": ka.value, "candf": cf.value, "thr0f": thr0f, "opn": opn if has.value else None,
+                "slot_of": slot_of, "hotpack": hotpack}
+
     def build_gram(self):
         s = C.c_double()
         check(self.L.hb_ctx_build_gram(self.h, C.byref(s)))

@@ -880,6 +880,23 @@ int hb_ctx_debug_get_pre(hb_ctx *c, int32_t *kpad, double *thr, double *invv, do
  * after group or panel h). Synchronises the context's stream and changes nothing; any of the pointers may be NULL. */
 int hb_ctx_debug_get_mirrors(hb_ctx *c, int32_t *slot, int32_t *bound_index, double *r, float *r32, int32_t *ndigits, int8_t *rq,
                              int32_t *vexp, double *mb);
+/* Debug read-out for the kernel-level tests (tests/test_gpu_opening.py): the certificate of the group chain as hb_ctx_build_gram() left it —
+ * G[k][j] = ga[k] gB[j] + c[k][j] with |c[k][j]| <= gcmax[k] over the stored band, ga = rint(s / 256), gB = rint(256 s / n), s the column sum.
+ * *ok: 1 when the arrays stand for the band the next sweep would run on; 0 — a success, with ga, gB and gcmax left untouched — where there is
+ * no certificate: HB_CERT=0, a row-sharded context, the fp64 resident layout, before a Gram build, and after an upload or a wider geometry
+ * until the band is built again. *Lg: the band the arrays were built over (blocks l = 0..Lg per panel). ga, gB, gcmax: m_pad int32 each
+ * (m_pad = the markers rounded up to whole panels). Synchronises the context's stream and changes nothing; any of the pointers may be NULL. */
+int hb_ctx_debug_get_cert(hb_ctx *c, int32_t *ok, int32_t *Lg, int32_t *ga, int32_t *gB, int32_t *gcmax);
+/* Debug read-out for the kernel-level tests (tests/test_gpu_opening.py): what the chain of the context's last pipelined sweep was given for its
+ * opening. *nslot: the rows of the row cache the lists were laid out for; *kappa, *candf: the prediction's and the candidates' factors;
+ * *has_opn: 1 when the 16-byte records were written (a certificate existed), else 0 with opn left untouched. thr0f: m_pad floats, the entry
+ * threshold rounded down to float (NaN: monomorphic marker, -inf: marker in the model); opn: m_pad x 4 int32, {candidate threshold (a double,
+ * low word first), the filter word, gB}; slot_of: m_pad int32, a marker's place in the row cache in units of 64 ints (-1: none, -2: monomorphic);
+ * hotpack: npanels x 256 int32, per panel [0] rows that fit, [1] rows listed, [2] whole rows among those that fit, [3] the shift in pieces,
+ * [4 ...] the listed markers (words beyond [4 + [1]) are undefined). Synchronises the context's stream and changes nothing; any of the
+ * pointers may be NULL. Fails before the first pipelined sweep. */
+int hb_ctx_debug_get_opening(hb_ctx *c, int32_t *nslot, double *kappa, double *candf, int32_t *has_opn, float *thr0f, int32_t *opn,
+                             int32_t *slot_of, int32_t *hotpack);
 
 #ifdef __cplusplus
 }
