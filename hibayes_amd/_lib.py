@@ -284,6 +284,8 @@ SYMBOLS = [
     "hb_impute_create", "hb_impute_solve", "hb_impute_destroy",
     # make_grm(inverse=TRUE): solve() -> solver_chol(), src/solver.cpp:159-202 (dpotrf, dpotri, the mirror), hb_chol.hip
     "hb_chol_factor", "hb_chol_invert_factor", "hb_spd_inverse", "hb_chol_plan",
+    # window PVE: README item (8), after the GEBV step of R/bayes.r:303-308 (hb_pve.hip)
+    "hb_ctx_window_var", "hb_pve_plan",
 ]
 
 
@@ -445,6 +447,8 @@ def lib():
     L.hb_chol_invert_factor.argtypes = [vp, i64, i32, i32]
     L.hb_spd_inverse.argtypes = [vp, i64, i32, i32, dbl, C.POINTER(i32)]
     L.hb_chol_plan.argtypes = [i32, i32] + [vp] * 8
+    L.hb_ctx_window_var.argtypes = [vp, vp, i64, i32, vp, i32, vp, i64, vp]
+    L.hb_pve_plan.argtypes = [vp, i64, i32, i32, vp, i32, vp, i32, i64, i32] + [vp] * 7
     _lib = L
     return L
 

@@ -398,7 +398,7 @@ def ibrm(formula, data=None, M=None, M_id=None, method="BayesCpi", map=None, Pi=
          niter=None, nburn=None, thin=5, windsize=None, windnum=None, dfvr=None, s2vr=None, vg=None,
          dfvg=None, s2vg=None, ve=None, dfve=None, s2ve=None, printfreq=100, seed=666666,
          threads=4, verbose=True, *, windindx=None, device=0, panel=0, precise=2,
-         store_alpha=True, comm=None, m_global=None, m_offset=0, gebv_samples=None, lambda_=0.0, eigen_solver="host", tridiagonal="host"):
+         store_alpha=True, comm=None, m_global=None, m_offset=0, gebv_samples=None, lambda_=0.0, eigen_solver="host", tridiagonal="host", pve=False):
     """Mirror of ibrm() (reference R/bayes.r:121-320). `formula` is a string such as
     "T1 ~ 1" or "T1 ~ season + bwt + (1 | loc) + (1 | dam)"; `data` a dict of columns or a
     pandas DataFrame whose first column holds the individual ids; `M` the n_all x m genotype
@@ -415,7 +415,13 @@ def ibrm(formula, data=None, M=None, M_id=None, method="BayesCpi", map=None, Pi=
     hibayes_amd.eig: the genotypes of the fit are uploaded once, the matrix and its eigenvectors stay on the device and the sampler runs on
     that context (the draws z_j are addressed by eigenvector index, so the chain is another equally valid realisation, not the host route's).
     `tridiagonal`: with eigen_solver="device" only — "host" (default) or "device", the stage between the reduction and the back-transformation
-    (make_grm's keyword of the same name)."""
+    (make_grm's keyword of the same name).
+    `pve`: also return res["pve"] = window_pve(...) — the variance explained by every window (windindx, or the windows cut by windsize /
+    windnum; without either, by every marker) in every stored record of the effects (without store_alpha: in their posterior mean), over
+    all genotyped individuals and relative to var(y) of the fit; see hibayes_amd.window_pve. Where the windows were cut here, the table
+    WIND / CHR / NUM / START / END comes with it. Not under a sharded run: a window's breeding values would have to be summed over the shards."""
+    if pve and comm is not None and comm.world > 1:
+        raise ValueError("ibrm: pve=True is not available in a sharded run (comm.world > 1): a window's breeding values would have to be summed over the shards")
     if eigen_solver not in ("host", "device"):
         raise ValueError("ibrm: eigen_solver must be \"host\" or \"device\", not %r" % (eigen_solver,))
     from .eig import check_tridiagonal
@@ -486,6 +492,7 @@ def ibrm(formula, data=None, M=None, M_id=None, method="BayesCpi", map=None, Pi=
                 fold = [0, 0.0001, 0.001, 0.01]
         else:
             Pi = [0.95, 0.05]
+    windinfo = None
     if (windsize is not None or windnum is not None) and windindx is None:
         if method in ("BayesA", "BayesRR", "BayesL"):
             raise ValueError("can not implement GWAS analysis for the method: " + method)
@@ -504,6 +511,13 @@ def ibrm(formula, data=None, M=None, M_id=None, method="BayesCpi", map=None, Pi=
             if bp.max() < windsize:
                 raise ValueError("Maximum of physical position is smaller than wind size.")
             windindx = cutwind_by_bp(chrom, bp, windsize)
+        if pve:  # (the table the summary-level sbrm() returns with its windows, R/sbayes.r:231-234)
+            nwin = int(windindx.max())
+            windinfo = {"WIND": ["wind%d" % (w + 1) for w in range(nwin)],
+                        "CHR": [chrom[np.flatnonzero(windindx == w + 1)[0]] for w in range(nwin)],
+                        "NUM": [int((windindx == w + 1).sum()) for w in range(nwin)],
+                        "START": [float(bp[windindx == w + 1].min()) for w in range(nwin)],
+                        "END": [float(bp[windindx == w + 1].max()) for w in range(nwin)]}
     y = np.array([float(cols[lhs][i]) for i in rows])
     Mfit = M[rows, :]
     Kival = Ki = fit_ctx = None
@@ -549,6 +563,12 @@ def ibrm(formula, data=None, M=None, M_id=None, method="BayesCpi", map=None, Pi=
             gebv = cg.matmul(res["alpha"])[:, 0]
             if comm is not None and comm.world > 1:
                 gebv = comm.sum_array(gebv)
+        if pve:  # README item (8), on the context that holds all genotyped individuals; relative to var(y) of the fit
+            from .pve import window_pve
+            samples = res["MCMCsamples"].get("alpha") if store_alpha else None
+            res["pve"] = window_pve(cg, res["alpha"] if samples is None else samples, windindx, vary=float(np.var(y, ddof=1)))
+            if windinfo is not None:
+                res["pve"].update(windinfo)
     res["u_last"] = res["g"]
     res["g"] = {"id": list(M_id), "gebv": gebv}
     res["e"] = {"id": [M_id[i] for i in rows], "e": res["e"]}

@@ -27,16 +27,7 @@ struct upd_view {
     const double *dd;            // ... and the changes by marker, zero where nothing moved (k_chain_dense's dd[])
 };
 
-// four consecutive individuals (row0 a multiple of 4) of one column, one genotype per byte: from the int8 matrix, or expanded in
-// registers from the 2-bit resident layout (individual 16 w + 4 k + b sits in bits [8 b + 2 k, 8 b + 2 k + 1] of word w)
-__device__ __forceinline__ int hb_ld4(const int8_t *X, int64_t ld, const uint32_t *X2, int64_t ld2w, int64_t col, int64_t row0)
-{
-    if (X2) {
-        const unsigned w = X2[col * ld2w + (row0 >> 4)];
-        return (int)((w >> ((row0 & 12) >> 1)) & 0x03030303u);
-    }
-    return *reinterpret_cast<const int *>(X + col * ld + row0);
-}
+// (hb_ld4, four consecutive individuals of one column from the int8 or the 2-bit layout: hb_wave.hpp — hb_pve.hip reads with it too)
 
 // exponent E with bound * 2^E < 2^54 (0 for an all-zero or non-finite bound)
 __device__ __forceinline__ int hb_fix_exp(double bound)

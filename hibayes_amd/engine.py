@@ -204,6 +204,25 @@ class Context:
         check(self.L.hb_ctx_matmul(self.h, A.ctypes.data, self.m, A.shape[1], out.ctypes.data, self.n))
         return out
 
+    def window_var(self, A, windindx, nw=None):
+        """(var, total): var[w - 1, r] = var(X_w alpha_w,r) over the individuals for every window id w of windindx (m ids in 1 .. nw) and every
+        record r (column of A, m x R), total[r] = var(X alpha_r); N - 1 denominators. On the device from the resident genotypes
+        (hb_ctx_window_var); hibayes_amd.window_pve() makes PVE and WPPA of them. nw: the number of windows where it is more than the largest id used
+        (the rows past it, like every window without an effect, are 0.0)."""
+        A = np.asfortranarray(A, dtype=np.float64).reshape(self.m, -1, order="F")
+        wi = np.asarray(windindx)
+        if wi.shape != (self.m,) or wi.dtype.kind not in "iu":
+            raise ValueError("windindx must hold one integer window id per marker")
+        if wi.min() < 1:
+            raise ValueError("windindx must hold window ids in 1 .. nw")
+        nw = int(wi.max()) if nw is None else int(nw)
+        if nw < wi.max():
+            raise ValueError("windindx must hold window ids in 1 .. nw")
+        wi = np.ascontiguousarray(wi, dtype=np.uint32)
+        var, total = np.zeros((nw, A.shape[1]), order="F"), np.zeros(A.shape[1])
+        check(self.L.hb_ctx_window_var(self.h, A.ctypes.data, self.m, A.shape[1], wi.ctypes.data, nw, var.ctypes.data, nw, total.ctypes.data))
+        return var, total
+
     def gram_band(self, p, l):
         P = self.panel
         G = np.zeros((P, P), dtype=np.int32)

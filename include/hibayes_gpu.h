@@ -697,6 +697,26 @@ int hb_ctx_matvec(hb_ctx *c, const double *alpha, double *out);
  * Eight records per pass, only over the columns with a non-zero effect in any of them. */
 int hb_ctx_matmul(hb_ctx *c, const double *A, int64_t ldA, int32_t R, double *out, int64_t ldo);
 
+/* The variance explained by windows of markers, item (8) of the reference README ("phenotypic/genetic variance explained (PVE) by single
+ * or multiple SNPs"), which the reference leaves to the R session after the GEBV step of R/bayes.r:303-308. For every record r (column of
+ * A, m x R, leading dimension ldA, on the host) and every window w (windindx: m ids in 1 .. nw):
+ *     var_out[r * ldv + (w - 1)] = var over the n individuals of g_w = X_w alpha_w,r, N - 1 denominator (R's var),
+ *     total_out[r]               = var(X alpha_r),
+ * from the resident genotypes of any layout (int8, 2-bit, fp64), eight records per pass over the columns with a non-zero effect in any of
+ * them (hb_pve.hip). Neither X alpha nor the n x nw matrix of window breeding values is ever stored. A window without a non-zero effect in a
+ * record's batch is not visited and gets 0.0 exactly. Deterministic, and a (window, record) value depends on that window's effects of
+ * that record alone: not on the other records, windows or ids. HB_ERR_INVALID: n < 2, a window id outside 1 .. nw, a non-finite effect, no
+ * genotypes on the device; HB_ERR_UNSUPPORTED: a row-sharded context (shard_rows). */
+int hb_ctx_window_var(hb_ctx *c, const double *A, int64_t ldA, int32_t R, const uint32_t *windindx, int32_t nw, double *var_out, int64_t ldv,
+                      double *total_out);
+/* The plan of one batch (hb_pveplan.hpp) for the tests; needs no device. A: m x nr effects, nr <= 8; s1: the m column sums over the n
+ * individuals; ld: rows of a resident column. Every array holds m entries of its kind: idx[m] the list (marker columns, sorted by window and
+ * marker), val[8 m] its effects, segs[3 m] (window 0-based, first entry, count) per window with an entry, shift[8 m] the segments' mean breeding
+ * values, total_shift[8] that of the whole list, chunks[2 m] (first segment, count) per column of workgroups; counts[4] = entries, segments,
+ * chunks, row blocks of 1024 rows. The launch is row blocks x chunks workgroups, and one more column for the total. */
+int hb_pve_plan(const double *A, int64_t ldA, int32_t m, int32_t nr, const uint32_t *windindx, int32_t nw, const double *s1, int32_t n, int64_t ld,
+                int32_t num_cus, int32_t *counts, int32_t *idx, double *val, int32_t *segs, double *shift, double *total_shift, int32_t *chunks);
+
 /* helpers for the host blocks that share yadj (reference src/Bayes.cpp:479-516) */
 int hb_ctx_residual_sums(hb_ctx *c, double *sum_r, double *sum_r2);
 int hb_ctx_residual_shift(hb_ctx *c, double a);                       /* yadj += a        */
