@@ -261,7 +261,7 @@ SYMBOLS = [
     "hb_ctx_download_gram_band", "hb_ctx_set_adaptive", "hb_ctx_get_pipeline", "hb_ctx_get_events", "hb_ctx_pipeline_note", "hb_ctx_matmul",
     "hb_comm_unique_id", "hb_comm_init", "hb_comm_world", "hb_comm_rank", "hb_comm_selftest", "hb_comm_destroy",
     "hb_ctx_debug_inject_abort", "hb_ctx_debug_get_pre", "hb_ctx_debug_get_mirrors", "hb_ctx_debug_get_cert", "hb_ctx_debug_get_opening",
-    "hb_ctx_set_matvec_kernel", "hb_ctx_time_stream_read",
+    "hb_ctx_set_matvec_kernel", "hb_ctx_time_stream_read", "hb_debug_live_buffers",
     "hb_run_create", "hb_run_step", "hb_run_state", "hb_run_ctx", "hb_run_finish", "hb_run_destroy",
     # ldmat(): R/ldm.r:31-112, src/tXXmat.cpp:43-77 (BigStat), :100-206 (tXXmat_Geno), :504-626 (tXXmat_Chr)
     "hb_ldm_build", "hb_ldm_info", "hb_ldm_download_dense", "hb_ldm_download_csc", "hb_ldm_destroy",
@@ -399,6 +399,7 @@ def lib():
     L.hb_ctx_debug_get_cert.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), vp, vp, vp]
     L.hb_ctx_debug_get_opening.argtypes = [vp, C.POINTER(i32), C.POINTER(dbl), C.POINTER(dbl), C.POINTER(i32), vp, vp, vp, vp]
     L.hb_ctx_set_matvec_kernel.argtypes = [vp, i32]
+    L.hb_debug_live_buffers.argtypes = [C.POINTER(i64), C.POINTER(i64)]
     L.hb_run_create.argtypes = [C.POINTER(BayesArgs), C.POINTER(vp)]
     L.hb_run_step.argtypes = [vp, i32, C.POINTER(i32)]
     L.hb_run_state.argtypes = [vp, C.POINTER(RunInfo)]

@@ -287,34 +287,17 @@ int chol_args(const char *who, const void *A, int64_t lda, int n, double lambda,
     return HB_OK;
 }
 
-// the buffers of one call; freed when it returns
-struct chol_mem {
-    int *info = nullptr;
-    double *P = nullptr, *W = nullptr;
-    ~chol_mem()
-    {
-        if (info) (void)hipFree(info);
-        if (P) (void)hipFree(P);
-        if (W) (void)hipFree(W);
-    }
-    template <typename T> int get(T **p, size_t bytes, const char *who, const char *what, int n)
-    {
-        if (hipMalloc(reinterpret_cast<void **>(p), bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            *p = nullptr;
-            char msg[200];
-            snprintf(msg, sizeof msg, "%s: hipMalloc: out of memory — %s of the %d x %d matrix needs %.1f GB on the device", who, what, n, n, 1e-9 * (double)bytes);
-            return hb_fail(HB_ERR_HIP, msg);
-        }
-        return HB_OK;
-    }
-    int get_info(const hb_cholplan &p, const char *who)
-    {
-        HB_TRY(get(&info, p.info_bytes, who, "the status word", p.n));
-        HB_HIP(hipMemsetAsync(info, 0, p.info_bytes, nullptr));
-        return HB_OK;
-    }
-};
+// the status word of one call, zeroed on the null stream, and its other buffers: "<what> of the n x n matrix" in a refusal's text
+int get_info(hb_bufs &m, const hb_cholplan &p, const char *who, int **info)
+{
+    HB_TRY(m.big(info, (size_t)p.info_bytes / sizeof(int), who, "the status word of the " + hb_dims(p.n) + " matrix"));
+    HB_HIP(hipMemsetAsync(*info, 0, p.info_bytes, nullptr));
+    return HB_OK;
+}
+int get_work(hb_bufs &m, size_t bytes, int n, const char *who, const char *what, double **w)
+{
+    return m.big(w, bytes / sizeof(double), who, std::string(what) + " of the " + hb_dims(n) + " matrix");
+}
 
 int factor_launch(const hb_cholplan &p, double *A, int64_t lda, int *info)
 {
@@ -368,11 +351,12 @@ int hb_chol_factor(double *A_dev, int64_t lda, int32_t n, int32_t device, double
     HB_TRY(chol_args("hb_chol_factor", A_dev, lda, n, lambda, info, true));
     HB_HIP(hipSetDevice(device));
     const hb_cholplan p = hb_cholplan_of(n);
-    chol_mem m;
-    HB_TRY(m.get_info(p, "hb_chol_factor"));
+    hb_bufs m;
+    int *dinfo = nullptr;
+    HB_TRY(get_info(m, p, "hb_chol_factor", &dinfo));
     if (lambda != 0.0) hipLaunchKernelGGL(k_chol_shift, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, A_dev, lda, n, lambda);
-    HB_TRY(factor_launch(p, A_dev, lda, m.info));
-    return fetch_info(m.info, info);
+    HB_TRY(factor_launch(p, A_dev, lda, dinfo));
+    return fetch_info(dinfo, info);
 }
 
 int hb_chol_invert_factor(double *L_dev, int64_t lda, int32_t n, int32_t device)
@@ -380,11 +364,13 @@ int hb_chol_invert_factor(double *L_dev, int64_t lda, int32_t n, int32_t device)
     HB_TRY(chol_args("hb_chol_invert_factor", L_dev, lda, n, 0.0, nullptr, false));
     HB_HIP(hipSetDevice(device));
     const hb_cholplan p = hb_cholplan_of(n);
-    chol_mem m;
-    HB_TRY(m.get_info(p, "hb_chol_invert_factor"));
-    HB_TRY(m.get(&m.P, p.panel_bytes, "hb_chol_invert_factor", "a block column", n));
-    HB_TRY(invert_launch(p, L_dev, lda, m.P, m.info));
-    return fetch_info(m.info, nullptr);
+    hb_bufs m;
+    int *dinfo = nullptr;
+    double *P = nullptr;
+    HB_TRY(get_info(m, p, "hb_chol_invert_factor", &dinfo));
+    HB_TRY(get_work(m, p.panel_bytes, n, "hb_chol_invert_factor", "a block column", &P));
+    HB_TRY(invert_launch(p, L_dev, lda, P, dinfo));
+    return fetch_info(dinfo, nullptr);
 }
 
 int hb_spd_inverse(double *A_dev, int64_t lda, int32_t n, int32_t device, double lambda, int32_t *info)
@@ -394,18 +380,20 @@ int hb_spd_inverse(double *A_dev, int64_t lda, int32_t n, int32_t device, double
     if (n > (1 << 30)) // (8 n^2 bytes would not fit a size_t, and no device holds 2^63 bytes)
         return hb_fail(HB_ERR_HIP, "hb_spd_inverse: out of memory — the work copy of a matrix of more than 2^30 rows cannot be allocated");
     const hb_cholplan p = hb_cholplan_of(n);
-    chol_mem m;
-    HB_TRY(m.get_info(p, "hb_spd_inverse"));
-    HB_TRY(m.get(&m.P, p.panel_bytes, "hb_spd_inverse", "a block column", n));
-    HB_TRY(m.get(&m.W, p.work_bytes, "hb_spd_inverse", "the work copy", n));
-    hipLaunchKernelGGL(k_chol_copy, dim3((unsigned)n, (unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, A_dev, lda, n, m.W, p.ldw, lambda, lambda != 0.0 ? 1 : 0);
+    hb_bufs m;
+    int *dinfo = nullptr;
+    double *P = nullptr, *W = nullptr;
+    HB_TRY(get_info(m, p, "hb_spd_inverse", &dinfo));
+    HB_TRY(get_work(m, p.panel_bytes, n, "hb_spd_inverse", "a block column", &P));
+    HB_TRY(get_work(m, p.work_bytes, n, "hb_spd_inverse", "the work copy", &W));
+    hipLaunchKernelGGL(k_chol_copy, dim3((unsigned)n, (unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, A_dev, lda, n, W, p.ldw, lambda, lambda != 0.0 ? 1 : 0);
     HB_HIP(hipGetLastError());
-    HB_TRY(factor_launch(p, m.W, p.ldw, m.info));
-    HB_TRY(invert_launch(p, m.W, p.ldw, m.P, m.info));
+    HB_TRY(factor_launch(p, W, p.ldw, dinfo));
+    HB_TRY(invert_launch(p, W, p.ldw, P, dinfo));
     const long long nt = p.blocks;
-    hipLaunchKernelGGL(k_chol_lauum, dim3((unsigned)(nt * (nt + 1) / 2)), dim3(256), 0, nullptr, m.W, p.ldw, n, A_dev, lda, m.info);
+    hipLaunchKernelGGL(k_chol_lauum, dim3((unsigned)(nt * (nt + 1) / 2)), dim3(256), 0, nullptr, W, p.ldw, n, A_dev, lda, dinfo);
     HB_HIP(hipGetLastError());
-    return fetch_info(m.info, info);
+    return fetch_info(dinfo, info);
 }
 
 int hb_chol_plan(int32_t n, int32_t cap, int32_t *nb, int64_t *ldw, int64_t *bytes, int32_t *nsteps, int32_t *k0, int32_t *width, int32_t *row_tiles,

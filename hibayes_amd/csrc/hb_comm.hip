@@ -107,9 +107,10 @@ int hb_comm_selftest(hb_comm *c)
 {
     if (!c || !c->comm) return hb_fail(HB_ERR_COMM, "hb_comm_selftest: no communicator");
     HB_HIP(hipSetDevice(c->device));
+    hb_bufs mem;
     double h[16], *d = nullptr;
     for (double &v : h) v = (double)(c->rank + 1);
-    HB_HIP(hipMalloc(reinterpret_cast<void **>(&d), sizeof(h)));
+    HB_TRY(mem.get(&d, 16));
     hipStream_t st = nullptr;
     HB_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
     HB_HIP(hipMemcpyAsync(d, h, sizeof(h), hipMemcpyHostToDevice, st));
@@ -122,7 +123,6 @@ int hb_comm_selftest(hb_comm *c)
             if (v != want) rc = hb_fail(HB_ERR_COMM, "hb_comm_selftest: the all-reduce returned a wrong sum");
     }
     (void)hipStreamDestroy(st);
-    (void)hipFree(d);
     return rc;
 }
 

@@ -41,40 +41,69 @@ void hb_line(int verbose, hb_log_fn log, void *log_user, const char *fmt, ...)
     else { fputs(buf, stdout); fputc('\n', stdout); fflush(stdout); }
 }
 
-template <typename T>
-static int dev_alloc(T **p, size_t count, bool zero = true)
-{
-    HB_HIP(hipMalloc(reinterpret_cast<void **>(p), std::max<size_t>(count, 1) * sizeof(T)));
-    if (zero) HB_HIP(hipMemset(*p, 0, std::max<size_t>(count, 1) * sizeof(T)));
-    return HB_OK;
-}
-
-// The few MB of words that one workgroup publishes write-through while workgroups on OTHER XCDs poll them (dots, correction sums,
-// changes of effect, move counts and lists, bounds, the flag block). HB_HANDOFF_ALLOC selects what kind of device memory they
-// live in: 0 = plain hipMalloc (coarse-grained: cached in every XCD's L2 — the polls and stores carry sc1 to get past it),
-// 1 = hipDeviceMallocUncached (MTYPE UC: no L2 copy anywhere, a store goes straight to the memory side), 2 = fine-grained
-// (coherent across agents). Round 5's experiment on the lost store of DESIGN.md §9.0; the arrays are small, the genotypes, Gram
-// blocks and everything streamed stay plain.
-static int g_handoff_kind = -1;
-template <typename T>
-static int dev_alloc_handoff(T **p, size_t count)
-{
-    if (g_handoff_kind < 0) {
-        const char *e = getenv("HB_HANDOFF_ALLOC");
-        g_handoff_kind = e ? std::max(0, std::min(2, atoi(e))) : 0;
-    }
-    const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-    if (g_handoff_kind == 0) HB_HIP(hipMalloc(reinterpret_cast<void **>(p), bytes));
-    else HB_HIP(hipExtMallocWithFlags(reinterpret_cast<void **>(p), bytes, g_handoff_kind == 1 ? hipDeviceMallocUncached : hipDeviceMallocFinegrained));
-    HB_HIP(hipMemset(*p, 0, bytes));
-    return HB_OK;
-}
-
 // normalise (pipeline, Lv, D) and derive the Gram band / version ring sizes (plan_geometry, hb_runplan.hpp)
 static void hb_pipeline_geometry(hb_ctx *c)
 {
     const hb_geometry g = plan_geometry(c->concurrent, c->pipeline, c->P, c->Lv, c->D);
     c->pipeline = g.pipeline, c->Lv = g.Lv, c->D = g.D, c->L = g.L, c->NB = g.NB;
+}
+
+// everything a context holds from its creation on, from its own hb_bufs; zero before the first use
+static int ctx_alloc(hb_ctx *c)
+{
+    const size_t mp = (size_t)c->m_pad;
+    HB_TRY(c->mem.zeroed(&c->X, (size_t)c->ld * mp, nullptr));
+    HB_TRY(c->mem.zeroed(&c->xpx, mp, nullptr));
+    HB_TRY(c->mem.zeroed(&c->vx, mp, nullptr));
+    HB_TRY(c->mem.zeroed(&c->s1, mp, nullptr));
+    HB_TRY(c->mem.zeroed(&c->g, mp, nullptr));
+    HB_TRY(c->mem.zeroed(&c->vargL, mp, nullptr));
+    HB_TRY(c->mem.zeroed(&c->alpha_sum, mp, nullptr));
+    HB_TRY(c->mem.zeroed(&c->alpha_sq, mp, nullptr));
+    HB_TRY(c->mem.zeroed(&c->tracker, mp, nullptr));
+    HB_TRY(c->mem.zeroed(&c->nzrate, mp, nullptr));
+    HB_TRY(c->mem.zeroed(&c->r, (size_t)c->ld * 8, nullptr));          // up to 8 versions; slot 0 is the residual between sweeps
+    HB_TRY(c->mem.zeroed(&c->u, (size_t)c->ld, nullptr));
+    HB_TRY(c->mem.zeroed(&c->r32, (size_t)c->ld * 8, nullptr));
+    HB_TRY(c->mem.zeroed(&c->rq, (size_t)c->ld * 8 * HB_ND, nullptr));
+    HB_TRY(c->mem.zeroed(&c->vexp, 8, nullptr));
+    HB_TRY(c->mem.zeroed(&c->gexp, (size_t)c->npanels + 1, nullptr));
+    HB_TRY(c->mem.handoff(&c->mb, ((size_t)c->npanels + 2) * HB_MBS, nullptr));
+    HB_TRY(c->mem.zeroed(&c->accq, (size_t)HB_ND * mp, nullptr));
+    HB_TRY(c->mem.zeroed(&c->xinfo, 2, nullptr));
+    HB_TRY(c->mem.zeroed(&c->thr, mp * (HB_MAX_FOLD - 1), nullptr));
+    HB_TRY(c->mem.zeroed(&c->invv, mp * (HB_MAX_FOLD - 1), nullptr));
+    HB_TRY(c->mem.zeroed(&c->sdz, mp * (HB_MAX_FOLD - 1), nullptr));
+    HB_TRY(c->mem.zeroed(&c->partial, mp * (size_t)c->nsplit, nullptr));
+    HB_TRY(c->mem.handoff(&c->dsum, mp, nullptr));
+    HB_TRY(c->mem.handoff(&c->fcorr, mp, nullptr));
+    HB_TRY(c->mem.handoff(&c->ddense, mp, nullptr));
+    HB_TRY(c->mem.handoff(&c->fcorr2, mp, nullptr));
+    HB_TRY(c->mem.zeroed(&c->dots, mp, nullptr));
+    HB_TRY(c->mem.handoff(&c->ev_count, (size_t)c->npanels * HB_EVS, nullptr));
+    HB_TRY(c->mem.handoff(&c->ev_idx, mp, nullptr));
+    HB_TRY(c->mem.handoff(&c->ev_delta, mp, nullptr));
+    HB_TRY(c->mem.zeroed(&c->acc, HB_ACC_N, nullptr));
+    HB_TRY(c->mem.zeroed(&c->d_in, 1, nullptr));
+    HB_TRY(c->mem.zeroed(&c->scratch, 8192, nullptr));
+    HB_TRY(c->mem.handoff(&c->flags, (size_t)4096, nullptr));
+    HB_TRY(c->mem.zeroed(&c->hot_slot, mp, nullptr));
+    HB_TRY(c->mem.zeroed(&c->hot_list, (size_t)(c->npanels + 1) * 256, nullptr));
+    HB_TRY(c->mem.zeroed(&c->thr0f, mp + 1024, nullptr));
+    HB_TRY(c->mem.zeroed(&c->opn, mp + 1024, nullptr));
+    HB_TRY(c->mem.zeroed(&c->ru_ws, (size_t)128, nullptr));
+    HB_TRY(c->mem.zeroed(&c->hot_n, (size_t)c->npanels, nullptr));
+    if (getenv("HB_DEBUG_ABORT")) {
+        HB_TRY(c->mem.zeroed(&c->ldiag, ((size_t)c->npanels + 2) * 4, nullptr));
+        c->ldiag_nblk.assign((size_t)c->npanels + 2, 0);
+    }
+    HB_TRY(c->mem.pin(&c->h_acc, HB_ACC_N));
+    HB_TRY(c->mem.pin(&c->h_in, 1));
+    HB_TRY(c->mem.pin(&c->h_flags, 64));
+    memset(c->h_in, 0, sizeof(hb_sweep_in)); // (model_index 0: no sweep yet, hb_ctx_debug_get_pre)
+    // the allocation memsets ran on the null stream, which the context's non-blocking streams do not wait for
+    HB_HIP(hipDeviceSynchronize());
+    return HB_OK;
 }
 
 extern "C" {
@@ -94,6 +123,13 @@ int hb_device_count(void)
 }
 
 size_t hb_exchange_count(int32_t n) { return (size_t)n + 16; }
+
+int hb_debug_live_buffers(int64_t *buffers, int64_t *bytes)
+{
+    if (buffers) *buffers = hb_live_count.load(std::memory_order_relaxed);
+    if (bytes) *bytes = hb_live_bytes.load(std::memory_order_relaxed);
+    return HB_OK;
+}
 
 // development aid (HB_DEBUG_SEGV=1): a native backtrace on SIGSEGV — there is no debugger in the image
 #include <execinfo.h>
@@ -158,15 +194,6 @@ int hb_ctx_create(const hb_ctx_params *p, hb_ctx **out)
     c->env_pinned = getenv("HB_PIPELINE") || getenv("HB_LOOKAHEAD") || getenv("HB_DOTGROUP");
     if (!c->pipeline && !getenv("HB_LOOKAHEAD")) c->Lv = 0;
     hb_pipeline_geometry(c);
-    int rc = HB_OK;
-#define TRY(x)                   \
-    do {                         \
-        rc = (x);                \
-        if (rc) {                \
-            hb_ctx_destroy(c);   \
-            return rc;           \
-        }                        \
-    } while (0)
     {
         hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
         if (e != hipSuccess) {
@@ -196,66 +223,12 @@ int hb_ctx_create(const hb_ctx_params *p, hb_ctx **out)
                 return hb_fail(HB_ERR_HIP, "hipEventCreate failed");
             }
     }
-    TRY(hbk_init_attrs());
-    const size_t mp = (size_t)c->m_pad;
-    TRY(dev_alloc(&c->X, (size_t)c->ld * mp));
-    TRY(dev_alloc(&c->xpx, mp));
-    TRY(dev_alloc(&c->vx, mp));
-    TRY(dev_alloc(&c->s1, mp));
-    TRY(dev_alloc(&c->g, mp));
-    TRY(dev_alloc(&c->vargL, mp));
-    TRY(dev_alloc(&c->alpha_sum, mp));
-    TRY(dev_alloc(&c->alpha_sq, mp));
-    TRY(dev_alloc(&c->tracker, mp));
-    TRY(dev_alloc(&c->nzrate, mp));
-    TRY(dev_alloc(&c->r, (size_t)c->ld * 8));          // up to 8 versions; slot 0 is the residual between sweeps
-    TRY(dev_alloc(&c->u, (size_t)c->ld));
-    TRY(dev_alloc(&c->r32, (size_t)c->ld * 8));
-    TRY(dev_alloc(&c->rq, (size_t)c->ld * 8 * HB_ND));
-    TRY(dev_alloc(&c->vexp, 8));
-    TRY(dev_alloc(&c->gexp, (size_t)c->npanels + 1));
-    TRY(dev_alloc_handoff(&c->mb, ((size_t)c->npanels + 2) * HB_MBS));
-    TRY(dev_alloc(&c->accq, (size_t)HB_ND * mp));
-    TRY(dev_alloc(&c->xinfo, 2));
-    TRY(dev_alloc(&c->thr, mp * (HB_MAX_FOLD - 1)));
-    TRY(dev_alloc(&c->invv, mp * (HB_MAX_FOLD - 1)));
-    TRY(dev_alloc(&c->sdz, mp * (HB_MAX_FOLD - 1)));
-    TRY(dev_alloc(&c->partial, mp * (size_t)c->nsplit));
-    TRY(dev_alloc_handoff(&c->dsum, mp));
-    TRY(dev_alloc_handoff(&c->fcorr, mp));
-    TRY(dev_alloc_handoff(&c->ddense, mp));
-    TRY(dev_alloc_handoff(&c->fcorr2, mp));
-    TRY(dev_alloc(&c->dots, mp));
-    TRY(dev_alloc_handoff(&c->ev_count, (size_t)c->npanels * HB_EVS));
-    TRY(dev_alloc_handoff(&c->ev_idx, mp));
-    TRY(dev_alloc_handoff(&c->ev_delta, mp));
-    TRY(dev_alloc(&c->acc, HB_ACC_N));
-    TRY(dev_alloc(&c->d_in, 1));
-    TRY(dev_alloc(&c->scratch, 8192));
-    TRY(dev_alloc_handoff(&c->flags, (size_t)4096));
-    TRY(dev_alloc(&c->hot_slot, mp));
-    TRY(dev_alloc(&c->hot_list, (size_t)(c->npanels + 1) * 256));
-    TRY(dev_alloc(&c->thr0f, mp + 1024));
-    TRY(dev_alloc(&c->opn, mp + 1024));
-    TRY(dev_alloc(&c->ru_ws, (size_t)128));
-    TRY(dev_alloc(&c->hot_n, (size_t)c->npanels));
-    if (getenv("HB_DEBUG_ABORT")) {
-        TRY(dev_alloc(&c->ldiag, ((size_t)c->npanels + 2) * 4));
-        c->ldiag_nblk.assign((size_t)c->npanels + 2, 0);
+    int rc = hbk_init_attrs();
+    if (!rc) rc = ctx_alloc(c);
+    if (rc) {
+        hb_ctx_destroy(c);
+        return rc;
     }
-    {
-        hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&c->h_acc), sizeof(double) * HB_ACC_N);
-        if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&c->h_in), sizeof(hb_sweep_in));
-        if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&c->h_flags), 256);
-        if (e != hipSuccess) {
-            hb_ctx_destroy(c);
-            return hb_fail(HB_ERR_HIP, std::string("hipHostMalloc: ") + hipGetErrorString(e));
-        }
-        memset(c->h_in, 0, sizeof(hb_sweep_in)); // (model_index 0: no sweep yet, hb_ctx_debug_get_pre)
-    }
-#undef TRY
-    // the allocation memsets ran on the null stream, which the context's non-blocking streams do not wait for
-    HB_HIP(hipDeviceSynchronize());
     {   // can the persistent pipeline run here at all?
         const char *why = nullptr;
         if (getenv("AMD_SERIALIZE_KERNEL") && atoi(getenv("AMD_SERIALIZE_KERNEL")) != 0) why = "AMD_SERIALIZE_KERNEL is set";
@@ -283,8 +256,7 @@ int hb_ctx_create(const hb_ctx_params *p, hb_ctx **out)
     return HB_OK;
 }
 
-static void blocks_free(hb_ctx *c);
-
+// graphs and events, then every buffer, then the streams (hb_bufs.hpp)
 void hb_ctx_destroy(hb_ctx *c)
 {
     if (!c) return;
@@ -303,21 +275,13 @@ void hb_ctx_destroy(hb_ctx *c)
     for (auto e : c->ev_chain) if (e) (void)hipEventDestroy(e);
     for (auto e : c->ev_upd) if (e) (void)hipEventDestroy(e);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
+    hb_poly_free(c);
+    hb_epsl_free(c);
+    c->mem.clear();
     if (c->s_chain) (void)hipStreamDestroy(c->s_chain);
     if (c->s_upd) (void)hipStreamDestroy(c->s_upd);
     if (c->s_warm) (void)hipStreamDestroy(c->s_warm);
     if (c->s_dbg) (void)hipStreamDestroy(c->s_dbg);
-    void *ptrs[] = {c->X, c->X2, c->Xd, c->gramd, c->xpx, c->vx, c->s1, c->g, c->vargL, c->alpha_sum, c->alpha_sq, c->tracker, c->nzrate, c->r, c->u,
-                    c->r32, c->rq, c->vexp, c->gexp, c->mb, c->accq, c->gram, c->xinfo, c->thr, c->invv, c->sdz, c->partial, c->dsum, c->fcorr, c->ddense, c->fcorr2, c->dots, c->ev_count, c->ev_idx,
-                    c->ev_delta, c->acc, c->d_in, c->scratch, c->dbg, c->lstamp, c->flags, c->ga, c->gB, c->gcmax, c->hot_slot, c->hot_list, c->hot_n, c->thr0f, c->opn, c->ru_ws, c->Cmat, c->zid, c->lev_buf, c->wind, c->wflag, c->wppa, c->snap, c->ldiag};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    blocks_free(c);
-    hb_poly_free(c);
-    hb_epsl_free(c);
-    if (c->h_acc) (void)hipHostFree(c->h_acc);
-    if (c->h_in) (void)hipHostFree(c->h_in);
-    if (c->h_flags) (void)hipHostFree(c->h_flags);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -349,8 +313,7 @@ static void invalidate(hb_ctx *c)
     if (c->layout == 64) { // integer genotypes over real ones: back to the int8 columns (the geometry stays where the real layout put it until its owner sets another)
         c->layout = 8;
         c->graph_model = -1;
-        if (c->Xd) (void)hipFree(c->Xd);
-        c->Xd = nullptr;
+        c->mem.drop(&c->Xd);
     }
 }
 
@@ -371,7 +334,7 @@ static void real_geometry(hb_ctx *c)
 
 static int real_alloc(hb_ctx *c)
 {
-    if (!c->Xd) HB_HIP(hipMalloc(reinterpret_cast<void **>(&c->Xd), sizeof(double) * (size_t)c->ld * c->m_pad));
+    if (!c->Xd) HB_TRY(c->mem.get(&c->Xd, (size_t)c->ld * c->m_pad));
     return HB_OK;
 }
 
@@ -397,17 +360,16 @@ int hb_ctx_upload_genotype_i8(hb_ctx *c, const int8_t *X, int64_t ld, int32_t co
 
 int hb_ctx_upload_genotype_f64(hb_ctx *c, const double *X, int64_t ld, int32_t col0, int32_t ncols)
 {
-    int rc = check_cols(c, col0, ncols, "hb_ctx_upload_genotype_f64");
-    if (rc) return rc;
-    rc = need_int8(c, "hb_ctx_upload_genotype_f64");
-    if (rc) return rc;
+    HB_TRY(check_cols(c, col0, ncols, "hb_ctx_upload_genotype_f64"));
+    HB_TRY(need_int8(c, "hb_ctx_upload_genotype_f64"));
+    int rc = HB_OK;
     if (!X || ld < c->n) return hb_fail(HB_ERR_INVALID, "hb_ctx_upload_genotype_f64: bad source");
     const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(ncols, (int64_t)(64 << 20) / std::max(1, c->n)));
+    hb_bufs tmp;
     double *stage = nullptr;
     int *dbad = nullptr;
-    HB_HIP(hipMalloc(reinterpret_cast<void **>(&stage), (size_t)chunk * c->n * sizeof(double)));
-    HB_HIP(hipMalloc(reinterpret_cast<void **>(&dbad), sizeof(int)));
-    HB_HIP(hipMemsetAsync(dbad, 0, sizeof(int), c->stream));
+    HB_TRY(tmp.get(&stage, (size_t)chunk * c->n));
+    HB_TRY(tmp.zeroed(&dbad, 1, c->stream));
     for (int c0 = 0; c0 < ncols && rc == HB_OK; c0 += chunk) {
         const int nc = std::min(chunk, ncols - c0);
         hipError_t e = hipMemcpy2DAsync(stage, (size_t)c->n * sizeof(double), X + (int64_t)(col0 + c0) * ld,
@@ -420,8 +382,6 @@ int hb_ctx_upload_genotype_f64(hb_ctx *c, const double *X, int64_t ld, int32_t c
     int bad = 0;
     if (rc == HB_OK && hipMemcpy(&bad, dbad, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
         rc = hb_fail(HB_ERR_HIP, "hipMemcpy failed");
-    (void)hipFree(stage);
-    (void)hipFree(dbad);
     invalidate(c);
     if (rc) return rc;
     if (bad)
@@ -435,18 +395,16 @@ int hb_ctx_upload_genotype_f64(hb_ctx *c, const double *X, int64_t ld, int32_t c
 // Real-valued genotypes (imputed dosages): every finite value is taken as it is, into the fp64 resident layout. The whole matrix at once.
 int hb_ctx_upload_genotype_real(hb_ctx *c, const double *X, int64_t ld)
 {
-    int rc = check_cols(c, 0, 0, "hb_ctx_upload_genotype_real");
-    if (rc) return rc;
+    HB_TRY(check_cols(c, 0, 0, "hb_ctx_upload_genotype_real"));
     if (!X || ld < c->n) return hb_fail(HB_ERR_INVALID, "hb_ctx_upload_genotype_real: bad source");
     if (c->row_reduce) return hb_fail(HB_ERR_UNSUPPORTED, "shard_rows runs on the int8 layout, not on the fp64 resident layout (real-valued genotypes)");
     HB_HIP(hipStreamSynchronize(c->stream));
-    rc = real_alloc(c);
-    if (rc) return rc;
+    HB_TRY(real_alloc(c));
     HB_HIP(hipMemsetAsync(c->Xd, 0, sizeof(double) * (size_t)c->ld * c->m_pad, c->stream));
     HB_HIP(hipMemcpy2DAsync(c->Xd, (size_t)c->ld * sizeof(double), X, (size_t)ld * sizeof(double), (size_t)c->n * sizeof(double), (size_t)c->m,
                             hipMemcpyHostToDevice, c->stream));
     int bad = 0;
-    rc = hbk_real_check(c, &bad);
+    const int rc = hbk_real_check(c, &bad);
     {
         std::lock_guard<std::mutex> lk(g_loaded_mu);
         g_loaded.insert(c);
@@ -474,10 +432,8 @@ int hb_ctx_download_genotype_real(hb_ctx *c, double *X, int64_t ld)
 int hb_ctx_upload_bed(hb_ctx *c, const uint8_t *bed, int64_t nbytes, int32_t nind, const int32_t *rows, int32_t col0,
                       int32_t ncols)
 {
-    int rc = check_cols(c, col0, ncols, "hb_ctx_upload_bed");
-    if (rc) return rc;
-    rc = need_int8(c, "hb_ctx_upload_bed");
-    if (rc) return rc;
+    HB_TRY(check_cols(c, col0, ncols, "hb_ctx_upload_bed"));
+    HB_TRY(need_int8(c, "hb_ctx_upload_bed"));
     const int64_t bpc = ((int64_t)nind + 3) / 4;
     if (!bed || nbytes < 3 + bpc * ((int64_t)col0 + ncols)) return hb_fail(HB_ERR_INVALID, "hb_ctx_upload_bed: file image too short");
     if (bed[0] != 0x6c || bed[1] != 0x1b || bed[2] != 0x01)
@@ -486,18 +442,17 @@ int hb_ctx_upload_bed(hb_ctx *c, const uint8_t *bed, int64_t nbytes, int32_t nin
     if (rows)
         for (int i = 0; i < c->n; i++)
             if (rows[i] < 0 || rows[i] >= nind) return hb_fail(HB_ERR_INVALID, "hb_ctx_upload_bed: row index out of range");
+    hb_bufs tmp;
     uint8_t *dbed = nullptr;
     int32_t *drows = nullptr;
-    HB_HIP(hipMalloc(reinterpret_cast<void **>(&dbed), (size_t)(bpc * ncols)));
+    HB_TRY(tmp.get(&dbed, (size_t)(bpc * ncols)));
     HB_HIP(hipMemcpy(dbed, bed + 3 + bpc * col0, (size_t)(bpc * ncols), hipMemcpyHostToDevice));
     if (rows) {
-        HB_HIP(hipMalloc(reinterpret_cast<void **>(&drows), sizeof(int32_t) * c->n));
+        HB_TRY(tmp.get(&drows, (size_t)c->n));
         HB_HIP(hipMemcpy(drows, rows, sizeof(int32_t) * c->n, hipMemcpyHostToDevice));
     }
-    rc = hbk_bed_decode(c, dbed, bpc, nind, drows, col0, ncols);
+    int rc = hbk_bed_decode(c, dbed, bpc, nind, drows, col0, ncols);
     if (rc == HB_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = hb_fail(HB_ERR_HIP, "sync failed");
-    (void)hipFree(dbed);
-    if (drows) (void)hipFree(drows);
     invalidate(c);
     return rc;
 }
@@ -517,24 +472,21 @@ int hb_ctx_generate_genotype(hb_ctx *c, uint64_t seed, int32_t mono_every)
 
 int hb_ctx_download_genotype(hb_ctx *c, int8_t *X, int64_t ld, int32_t col0, int32_t ncols)
 {
-    int rc = check_cols(c, col0, ncols, "hb_ctx_download_genotype");
-    if (rc) return rc;
+    HB_TRY(check_cols(c, col0, ncols, "hb_ctx_download_genotype"));
     if (c->layout == 64) return hb_fail(HB_ERR_INVALID, "hb_ctx_download_genotype: the context holds the fp64 resident layout (hb_ctx_download_genotype_real)");
     if (!c->X) { // 2-bit only: unpack a slab at a time into a scratch buffer
         const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(ncols, (int64_t)(256 << 20) / c->ld));
+        hb_bufs mem;
         int8_t *tmp = nullptr;
-        HB_HIP(hipMalloc(reinterpret_cast<void **>(&tmp), (size_t)chunk * c->ld));
-        hipError_t e = hipSuccess;
-        for (int c0 = 0; c0 < ncols && e == hipSuccess && rc == HB_OK; c0 += chunk) {
+        HB_TRY(mem.get(&tmp, (size_t)chunk * c->ld));
+        for (int c0 = 0; c0 < ncols; c0 += chunk) {
             const int nc = std::min(chunk, ncols - c0);
-            rc = hbk_unpack2(c, col0 + c0, nc, tmp);
-            if (rc == HB_OK) e = hipStreamSynchronize(c->stream);
-            if (rc == HB_OK && e == hipSuccess)
+            HB_TRY(hbk_unpack2(c, col0 + c0, nc, tmp));
+            hipError_t e = hipStreamSynchronize(c->stream);
+            if (e == hipSuccess)
                 e = hipMemcpy2D(X + (int64_t)c0 * ld, (size_t)ld, tmp, (size_t)c->ld, (size_t)c->n, (size_t)nc, hipMemcpyDeviceToHost);
+            if (e != hipSuccess) return hb_fail(HB_ERR_HIP, std::string("hb_ctx_download_genotype: ") + hipGetErrorString(e));
         }
-        (void)hipFree(tmp);
-        if (rc) return rc;
-        if (e != hipSuccess) return hb_fail(HB_ERR_HIP, std::string("hb_ctx_download_genotype: ") + hipGetErrorString(e));
         return HB_OK;
     }
     HB_HIP(hipMemcpy2D(X, (size_t)ld, c->X + (int64_t)col0 * c->ld, (size_t)c->ld, (size_t)c->n, (size_t)ncols,
@@ -567,21 +519,16 @@ int hb_ctx_marker_stats(hb_ctx *c, double *xpx, double *vx, double *sumvx, int32
 
 int hb_ctx_set_layout(hb_ctx *c, int32_t bits, int32_t keep_int8)
 {
-    int rc = check_cols(c, 0, 0, "hb_ctx_set_layout");
-    if (rc) return rc;
+    HB_TRY(check_cols(c, 0, 0, "hb_ctx_set_layout"));
     if (bits == 0) bits = c->layout == 64 ? 64 : 8;
     if (bits != 8 && bits != 2 && bits != 64) return hb_fail(HB_ERR_INVALID, "hb_ctx_set_layout: bits must be 8, 2 or 64");
     HB_HIP(hipStreamSynchronize(c->stream));
     if (bits == 64) { // the int8 columns converted on the device (the same numbers, as doubles)
         if (c->layout == 64) return HB_OK;
         if (c->row_reduce) return hb_fail(HB_ERR_UNSUPPORTED, "shard_rows runs on the int8 layout, not on the fp64 resident layout");
-        if (c->layout == 2 && !c->X) {
-            rc = hb_ctx_set_layout(c, 8, 1);
-            if (rc) return rc;
-        }
-        rc = real_alloc(c);
-        if (!rc) rc = hbk_real_from_i8(c);
-        if (rc) return rc;
+        if (c->layout == 2 && !c->X) HB_TRY(hb_ctx_set_layout(c, 8, 1));
+        HB_TRY(real_alloc(c));
+        HB_TRY(hbk_real_from_i8(c));
         HB_HIP(hipStreamSynchronize(c->stream));
         real_geometry(c);
         return HB_OK;
@@ -590,10 +537,8 @@ int hb_ctx_set_layout(hb_ctx *c, int32_t bits, int32_t keep_int8)
         return hb_fail(HB_ERR_UNSUPPORTED, "the context holds the fp64 resident layout (real-valued genotypes): it has no int8 or 2-bit form; upload integer genotypes instead");
     if (bits == 8) {
         if (!c->X) { // unpack the dropped int8 copy
-            HB_HIP(hipMalloc(reinterpret_cast<void **>(&c->X), (size_t)c->ld * c->m_pad));
-            HB_HIP(hipMemsetAsync(c->X, 0, (size_t)c->ld * c->m_pad, c->stream));
-            rc = hbk_unpack2(c, 0, c->m_pad, c->X);
-            if (rc) return rc;
+            HB_TRY(c->mem.zeroed(&c->X, (size_t)c->ld * c->m_pad, c->stream));
+            HB_TRY(hbk_unpack2(c, 0, c->m_pad, c->X));
             HB_HIP(hipStreamSynchronize(c->stream));
         }
         if (c->layout != 8) c->graph_model = -1;
@@ -603,26 +548,20 @@ int hb_ctx_set_layout(hb_ctx *c, int32_t bits, int32_t keep_int8)
     if (c->precise != 2)
         return hb_fail(HB_ERR_UNSUPPORTED, "the 2-bit resident layout needs the fixed-point mat-vec (precise = 2)");
     if (c->layout != 2) {
-        rc = need_int8(c, "hb_ctx_set_layout");
-        if (rc) return rc;
-        if (!c->stats_ready) {
-            rc = hbk_stats(c);
-            if (rc) return rc;
-        }
+        HB_TRY(need_int8(c, "hb_ctx_set_layout"));
+        if (!c->stats_ready) HB_TRY(hbk_stats(c));
         if (c->xmin < 0 || c->xmax > 3)
             return hb_fail(HB_ERR_UNSUPPORTED, "the 2-bit resident layout needs genotype codes 0..3 (this matrix holds " + std::to_string(c->xmin) +
                                                    ".." + std::to_string(c->xmax) + "): keep the int8 layout");
         c->ld2 = (c->ld + 511) / 512 * 128;
-        if (!c->X2) HB_HIP(hipMalloc(reinterpret_cast<void **>(&c->X2), (size_t)c->ld2 * c->m_pad));
-        rc = hbk_pack2(c);
-        if (rc) return rc;
+        if (!c->X2) HB_TRY(c->mem.get(&c->X2, (size_t)c->ld2 * c->m_pad / sizeof(uint32_t)));
+        HB_TRY(hbk_pack2(c));
         HB_HIP(hipStreamSynchronize(c->stream));
         c->layout = 2;
         c->graph_model = -1;
     }
     if (!keep_int8 && c->X) {
-        (void)hipFree(c->X);
-        c->X = nullptr;
+        c->mem.drop(&c->X);
         c->graph_model = -1;
     }
     return HB_OK;
@@ -676,26 +615,21 @@ int hb_ctx_set_adaptive(hb_ctx *c, int32_t on)
 
 int hb_ctx_build_gram(hb_ctx *c, double *seconds)
 {
-    int rc = check_cols(c, 0, 0, "hb_ctx_build_gram");
-    if (rc) return rc;
+    HB_TRY(check_cols(c, 0, 0, "hb_ctx_build_gram"));
     if (c->layout == 64) { // fp64 columns: the diagonal block of every panel, in fp64 (hb_real.hip)
         c->Lg = 0;
         c->graph_model = -1;
         c->gcert_ok = false;
         const size_t need = (size_t)c->m_pad * (size_t)c->P;
         if (need > c->gramd_cap) {
-            if (c->gramd) { (void)hipFree(c->gramd); c->gramd = nullptr; }
+            c->mem.drop(&c->gramd);
             c->gramd_cap = 0;
-            HB_HIP(hipMalloc(reinterpret_cast<void **>(&c->gramd), need * sizeof(double)));
+            HB_TRY(c->mem.get(&c->gramd, need));
             c->gramd_cap = need;
         }
-        if (!c->stats_ready) {
-            rc = hbk_stats(c);
-            if (rc) return rc;
-        }
+        if (!c->stats_ready) HB_TRY(hbk_stats(c));
         const auto t0 = hb_clk::now();
-        rc = hbk_real_gram(c);
-        if (rc) return rc;
+        HB_TRY(hbk_real_gram(c));
         HB_HIP(hipStreamSynchronize(c->stream));
         if (seconds) *seconds = hb_since(t0);
         c->gram_ready = true;
@@ -706,24 +640,19 @@ int hb_ctx_build_gram(hb_ctx *c, double *seconds)
     c->graph_model = -1; // the captured sweeps hold the old band's stride (and, after a re-allocation, its pointer)
     const size_t need = (size_t)c->m_pad * (size_t)c->P * (size_t)(c->Lg + 1);
     if (need > c->gram_cap) {
-        if (c->gram) { (void)hipFree(c->gram); c->gram = nullptr; }
+        c->mem.drop(&c->gram);
         c->gram_cap = 0;
-        HB_HIP(hipMalloc(reinterpret_cast<void **>(&c->gram), need * sizeof(int32_t)));
+        HB_TRY(c->mem.get(&c->gram, need));
         c->gram_cap = need;
     }
     HB_HIP(hipMemsetAsync(c->gram, 0, need * sizeof(int32_t), c->stream));
-    if (!c->stats_ready) {
-        rc = hbk_stats(c);
-        if (rc) return rc;
-    }
+    if (!c->stats_ready) HB_TRY(hbk_stats(c));
     const double amax = std::max(std::abs((double)c->xmin), std::abs((double)c->xmax));
     if (amax * amax * (double)c->n >= 2147483647.0)
         return hb_fail(HB_ERR_UNSUPPORTED, "genotype codes too large for the exact int32 Gram matrix at this n");
     const auto t0 = hb_clk::now();
-    rc = hb_build_gram_impl(c);
-    if (rc) return rc;
-    rc = hb_build_gcert(c); // (the rank-one part of the band and the bound on the rest: the group chain's certificate)
-    if (rc) return rc;
+    HB_TRY(hb_build_gram_impl(c));
+    HB_TRY(hb_build_gcert(c)); // (the rank-one part of the band and the bound on the rest: the group chain's certificate)
     HB_HIP(hipStreamSynchronize(c->stream));
     if (seconds) *seconds = hb_since(t0);
     c->gram_ready = true;
@@ -853,22 +782,19 @@ int hb_ctx_dot(hb_ctx *c, int32_t col0, int32_t ncols, double *d)
 
 int hb_ctx_matvec(hb_ctx *c, const double *alpha, double *out)
 {
-    int rc = check_cols(c, 0, 0, "hb_ctx_matvec");
-    if (rc) return rc;
+    HB_TRY(check_cols(c, 0, 0, "hb_ctx_matvec"));
     if (!alpha || !out) return hb_fail(HB_ERR_INVALID, "hb_ctx_matvec: null argument");
+    hb_bufs mem;
     double *da = nullptr, *dout = nullptr;
-    HB_HIP(hipMalloc(reinterpret_cast<void **>(&da), sizeof(double) * (size_t)c->m_pad));
-    HB_HIP(hipMalloc(reinterpret_cast<void **>(&dout), sizeof(double) * (size_t)c->ld));
+    HB_TRY(mem.get(&da, (size_t)c->m_pad));
+    HB_TRY(mem.get(&dout, (size_t)c->ld));
     hipError_t e = hipMemset(da, 0, sizeof(double) * (size_t)c->m_pad);
     if (e == hipSuccess) e = hipMemcpy(da, alpha, sizeof(double) * c->m, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
-        rc = hbk_xalpha(c, da, dout);
-        if (rc == HB_OK) e = hipStreamSynchronize(c->stream);
-        if (rc == HB_OK && e == hipSuccess) e = hipMemcpy(out, dout, sizeof(double) * c->n, hipMemcpyDeviceToHost);
+        HB_TRY(hbk_xalpha(c, da, dout));
+        e = hipStreamSynchronize(c->stream);
+        if (e == hipSuccess) e = hipMemcpy(out, dout, sizeof(double) * c->n, hipMemcpyDeviceToHost);
     }
-    (void)hipFree(da);
-    (void)hipFree(dout);
-    if (rc) return rc;
     if (e != hipSuccess) return hb_fail(HB_ERR_HIP, std::string("hb_ctx_matvec: ") + hipGetErrorString(e));
     return HB_OK;
 }
@@ -877,19 +803,20 @@ int hb_ctx_matvec(hb_ctx *c, const double *alpha, double *out)
 // R/bayes.r:303-305, eight records per pass over the columns that carry a non-zero effect in any of them
 int hb_ctx_matmul(hb_ctx *c, const double *A, int64_t ldA, int32_t R, double *out, int64_t ldo)
 {
-    int rc = check_cols(c, 0, 0, "hb_ctx_matmul");
-    if (rc) return rc;
+    HB_TRY(check_cols(c, 0, 0, "hb_ctx_matmul"));
     if (!A || !out || R < 0 || ldA < c->m || ldo < c->n) return hb_fail(HB_ERR_INVALID, "hb_ctx_matmul: bad argument");
     if (R == 0) return HB_OK;
     const int RB = 8;
+    hb_bufs mem;
     int *didx = nullptr;
     double *dval = nullptr, *dout = nullptr;
-    HB_HIP(hipMalloc(reinterpret_cast<void **>(&didx), sizeof(int) * (size_t)c->m));
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&dval), sizeof(double) * (size_t)c->m * RB);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&dout), sizeof(double) * (size_t)c->ld * RB);
+    HB_TRY(mem.get(&didx, (size_t)c->m));
+    HB_TRY(mem.get(&dval, (size_t)c->m * RB));
+    HB_TRY(mem.get(&dout, (size_t)c->ld * RB));
+    hipError_t e = hipSuccess;
     std::vector<int> idx;
     std::vector<double> val, ho((size_t)c->ld * RB);
-    for (int r0 = 0; r0 < R && e == hipSuccess && rc == HB_OK; r0 += RB) {
+    for (int r0 = 0; r0 < R; r0 += RB) {
         const int nr = std::min(RB, R - r0);
         idx.clear();
         val.clear();
@@ -906,17 +833,12 @@ int hb_ctx_matmul(hb_ctx *c, const double *A, int64_t ldA, int32_t R, double *ou
             if (e == hipSuccess) e = hipMemcpyAsync(dval, val.data(), sizeof(double) * (size_t)nnz * RB, hipMemcpyHostToDevice, c->stream);
         }
         if (e != hipSuccess) break;
-        rc = hbk_xmat(c, didx, dval, nnz, dout);
-        if (rc) break;
+        HB_TRY(hbk_xmat(c, didx, dval, nnz, dout));
         e = hipMemcpyAsync(ho.data(), dout, sizeof(double) * (size_t)c->ld * RB, hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) break;
         for (int r = 0; r < nr; r++) std::memcpy(out + (size_t)(r0 + r) * ldo, ho.data() + (size_t)r * c->ld, sizeof(double) * c->n);
     }
-    (void)hipFree(didx);
-    if (dval) (void)hipFree(dval);
-    if (dout) (void)hipFree(dout);
-    if (rc) return rc;
     if (e != hipSuccess) return hb_fail(HB_ERR_HIP, std::string("hb_ctx_matmul: ") + hipGetErrorString(e));
     return HB_OK;
 }
@@ -1022,12 +944,11 @@ int hb_ctx_snapshot(hb_ctx *c, int model_index, bool store, bool count_pip)
     }
     if (off > c->snap_cap) {
         HB_HIP(hipStreamSynchronize(c->stream));
-        if (c->snap) (void)hipFree(c->snap);
-        c->snap = nullptr;
+        c->mem.drop(&c->snap);
         c->snap_cap = 0;
         // (room for every segment a later sweep of the run may add: the counters and moments start after the burn-in)
         const size_t cap = off + (sizeof(double) * 3 + sizeof(uint32_t)) * mp + 9 * (size_t)c->nw + 8 * 256;
-        HB_HIP(hipMalloc(reinterpret_cast<void **>(&c->snap), cap));
+        HB_TRY(c->mem.get(&c->snap, cap));
         c->snap_cap = cap;
     }
     c->snap_segs = segs;
@@ -1159,12 +1080,11 @@ int hb_ctx_residual_shift(hb_ctx *c, double a)
 
 int hb_ctx_set_covariates(hb_ctx *c, const double *Cmat, int32_t nc)
 {
-    int rc = check_cols(c, 0, 0, "hb_ctx_set_covariates");
-    if (rc) return rc;
-    if (c->Cmat) { (void)hipFree(c->Cmat); c->Cmat = nullptr; }
+    HB_TRY(check_cols(c, 0, 0, "hb_ctx_set_covariates"));
+    c->mem.drop(&c->Cmat);
     c->nc = 0;
     if (!Cmat || nc <= 0) return HB_OK;
-    HB_HIP(hipMalloc(reinterpret_cast<void **>(&c->Cmat), sizeof(double) * (size_t)c->n * nc));
+    HB_TRY(c->mem.get(&c->Cmat, (size_t)c->n * nc));
     HB_HIP(hipMemcpy(c->Cmat, Cmat, sizeof(double) * (size_t)c->n * nc, hipMemcpyHostToDevice));
     c->nc = nc;
     return HB_OK;
@@ -1192,10 +1112,9 @@ int hb_ctx_cov_axpy(hb_ctx *c, int32_t i, double a)
 
 int hb_ctx_set_levels(hb_ctx *c, const int32_t *zid, int32_t nr, const int32_t *nlev)
 {
-    int rc = check_cols(c, 0, 0, "hb_ctx_set_levels");
-    if (rc) return rc;
-    if (c->zid) { (void)hipFree(c->zid); c->zid = nullptr; }
-    if (c->lev_buf) { (void)hipFree(c->lev_buf); c->lev_buf = nullptr; }
+    HB_TRY(check_cols(c, 0, 0, "hb_ctx_set_levels"));
+    c->mem.drop(&c->zid);
+    c->mem.drop(&c->lev_buf);
     c->nr = 0;
     c->nlev.clear();
     c->lev_first.clear();
@@ -1212,9 +1131,9 @@ int hb_ctx_set_levels(hb_ctx *c, const int32_t *zid, int32_t nr, const int32_t *
         for (int i = 0; i < c->n; i++)
             if (zid[(size_t)t * c->n + i] < 0 || zid[(size_t)t * c->n + i] >= nlev[t])
                 return hb_fail(HB_ERR_INVALID, "hb_ctx_set_levels: level index out of range");
-    HB_HIP(hipMalloc(reinterpret_cast<void **>(&c->zid), sizeof(int32_t) * (size_t)c->n * nr));
+    HB_TRY(c->mem.get(&c->zid, (size_t)c->n * nr));
     HB_HIP(hipMemcpy(c->zid, zid, sizeof(int32_t) * (size_t)c->n * nr, hipMemcpyHostToDevice));
-    HB_HIP(hipMalloc(reinterpret_cast<void **>(&c->lev_buf), sizeof(double) * (size_t)mx));
+    HB_TRY(c->mem.get(&c->lev_buf, (size_t)mx));
     c->nr = nr;
     c->lev_total = tot;
     return HB_OK;
@@ -1242,35 +1161,25 @@ int hb_ctx_level_axpy(hb_ctx *c, int32_t term, const double *delta)
     return hbk_level_axpy(c, term, c->lev_buf);
 }
 
-// one sweep in two halves, so that a caller can enqueue more work on the stream (the multi-GPU exchange) before the single
-// host synchronisation of the iteration
-static void blocks_free(hb_ctx *c)
-{
-    if (c->blk) (void)hipFree(c->blk);
-    if (c->blk_zz) (void)hipFree(c->blk_zz);
-    if (c->blk_z) (void)hipFree(c->blk_z);
-    if (c->h_blk) (void)hipHostFree(c->h_blk);
-    if (c->h_z) (void)hipHostFree(c->h_z);
-    c->blk = c->blk_zz = c->blk_z = c->h_blk = c->h_z = nullptr;
-    c->blk_n = 0;
-}
-
 int hb_ctx_blocks_setup(hb_ctx *c, const double *cpc, const double *zz, const double *vrtmp0)
 {
-    int rc = check_cols(c, 0, 0, "hb_ctx_blocks_setup");
-    if (rc) return rc;
-    blocks_free(c);
+    HB_TRY(check_cols(c, 0, 0, "hb_ctx_blocks_setup"));
+    c->mem.drop(&c->blk);
+    c->mem.drop(&c->blk_zz);
+    c->mem.drop(&c->blk_z);
+    c->mem.drop(&c->h_blk);
+    c->mem.drop(&c->h_z);
+    c->blk_n = 0;
     c->blk_cpc.assign(cpc, cpc + c->nc);
     const int nb = c->nc + c->lev_total + 2 * c->nr;
     if (nb == 0) return HB_OK;
-    HB_HIP(hipMalloc(reinterpret_cast<void **>(&c->blk), sizeof(double) * nb));
-    HB_HIP(hipMemsetAsync(c->blk, 0, sizeof(double) * nb, c->stream)); // (on the context's stream: a null-stream memset is not ordered before it)
-    HB_HIP(hipHostMalloc(reinterpret_cast<void **>(&c->h_blk), sizeof(double) * nb));
+    HB_TRY(c->mem.zeroed(&c->blk, (size_t)nb, c->stream)); // (on the context's stream: a null-stream memset is not ordered before it)
+    HB_TRY(c->mem.pin(&c->h_blk, (size_t)nb));
     std::memset(c->h_blk, 0, sizeof(double) * nb);
     if (c->lev_total) {
-        HB_HIP(hipMalloc(reinterpret_cast<void **>(&c->blk_zz), sizeof(double) * c->lev_total));
-        HB_HIP(hipMalloc(reinterpret_cast<void **>(&c->blk_z), sizeof(double) * c->lev_total));
-        HB_HIP(hipHostMalloc(reinterpret_cast<void **>(&c->h_z), sizeof(double) * c->lev_total));
+        HB_TRY(c->mem.get(&c->blk_zz, (size_t)c->lev_total));
+        HB_TRY(c->mem.get(&c->blk_z, (size_t)c->lev_total));
+        HB_TRY(c->mem.pin(&c->h_z, (size_t)c->lev_total));
         HB_HIP(hipMemcpyAsync(c->blk_zz, zz, sizeof(double) * c->lev_total, hipMemcpyHostToDevice, c->stream));
         HB_HIP(hipMemcpyAsync(c->blk + c->nc + c->lev_total, vrtmp0, sizeof(double) * c->nr, hipMemcpyHostToDevice, c->stream));
         HB_HIP(hipStreamSynchronize(c->stream)); // (the caller's arrays may be temporaries)
@@ -1316,6 +1225,8 @@ int hb_ctx_blocks_state(hb_ctx *c, double *beta, double *estR, double *vrtmp, do
     return HB_OK;
 }
 
+// one sweep in two halves, so that a caller can enqueue more work on the stream (the multi-GPU exchange) before the single
+// host synchronisation of the iteration
 int hb_ctx_sweep_begin(hb_ctx *c, const hb_sweep_in *in)
 {
     int rc = check_cols(c, 0, 0, "hb_ctx_sweep");
@@ -1410,11 +1321,10 @@ int hb_ctx_get_counters(hb_ctx *c, double *nzrate, double *alpha_sum, double *al
 
 int hb_ctx_set_windows(hb_ctx *c, const uint32_t *windindx, int32_t nw)
 {
-    int rc = check_cols(c, 0, 0, "hb_ctx_set_windows");
-    if (rc) return rc;
-    if (c->wind) { (void)hipFree(c->wind); c->wind = nullptr; }
-    if (c->wflag) { (void)hipFree(c->wflag); c->wflag = nullptr; }
-    if (c->wppa) { (void)hipFree(c->wppa); c->wppa = nullptr; }
+    HB_TRY(check_cols(c, 0, 0, "hb_ctx_set_windows"));
+    c->mem.drop(&c->wind);
+    c->mem.drop(&c->wflag);
+    c->mem.drop(&c->wppa);
     c->nw = 0;
     c->graph_model = -1; // the captured graph holds the old pointers
     if (!windindx || nw <= 0) return HB_OK;
@@ -1422,12 +1332,10 @@ int hb_ctx_set_windows(hb_ctx *c, const uint32_t *windindx, int32_t nw)
         if (windindx[i] < 1 || (int)windindx[i] > nw) return hb_fail(HB_ERR_INVALID, "hb_ctx_set_windows: window id out of range");
     std::vector<uint32_t> w(c->m_pad, 1u);
     std::memcpy(w.data(), windindx, sizeof(uint32_t) * c->m);
-    HB_HIP(hipMalloc(reinterpret_cast<void **>(&c->wind), sizeof(uint32_t) * c->m_pad));
+    HB_TRY(c->mem.get(&c->wind, (size_t)c->m_pad));
     HB_HIP(hipMemcpy(c->wind, w.data(), sizeof(uint32_t) * c->m_pad, hipMemcpyHostToDevice));
-    HB_HIP(hipMalloc(reinterpret_cast<void **>(&c->wflag), (size_t)nw));
-    HB_HIP(hipMemsetAsync(c->wflag, 0, (size_t)nw, c->stream));
-    HB_HIP(hipMalloc(reinterpret_cast<void **>(&c->wppa), sizeof(double) * nw));
-    HB_HIP(hipMemsetAsync(c->wppa, 0, sizeof(double) * nw, c->stream));
+    HB_TRY(c->mem.zeroed(&c->wflag, (size_t)nw, c->stream));
+    HB_TRY(c->mem.zeroed(&c->wppa, (size_t)nw, c->stream));
     c->nw = nw;
     return HB_OK;
 }
@@ -1485,8 +1393,7 @@ int hb_ctx_set_profiling(hb_ctx *c, int32_t on)
     if (!c) return hb_fail(HB_ERR_INVALID, "hb_ctx_set_profiling: null context");
     c->profiling = (on & 1) != 0;
     if ((on & 2) && !c->dbg) { // bit 1: cycle stamps inside k_chain (development aid)
-        HB_HIP(hipMalloc(reinterpret_cast<void **>(&c->dbg), sizeof(long long) * 32 * (size_t)c->npanels));
-        HB_HIP(hipMemsetAsync(c->dbg, 0, sizeof(long long) * 32 * (size_t)c->npanels, c->stream));
+        HB_TRY(c->mem.zeroed(&c->dbg, 32 * (size_t)c->npanels, c->stream));
         c->graph_model = -1;
     }
     if (((on & 8) != 0) != (c->lstamp != nullptr)) {
@@ -1494,14 +1401,12 @@ int hb_ctx_set_profiling(hb_ctx *c, int32_t on)
         // (hb_ctx_matvec_stamps): the in-situ duration of the pipeline's launches, chain and update rows running beside them
         if (on & 8) {
             const size_t cnt = (size_t)(c->npanels + 1) * HB_LSTAMP_BLOCKS * 2;
-            HB_HIP(hipMalloc(reinterpret_cast<void **>(&c->lstamp), sizeof(unsigned long long) * cnt));
-            HB_HIP(hipMemsetAsync(c->lstamp, 0, sizeof(unsigned long long) * cnt, c->stream));
+            HB_TRY(c->mem.zeroed(&c->lstamp, cnt, c->stream));
             c->lstamp_nblk.assign((size_t)c->npanels + 1, 0);
             c->lstamp_cols.assign((size_t)c->npanels + 1, 0);
         } else {
             HB_HIP(hipStreamSynchronize(c->stream));
-            (void)hipFree(c->lstamp);
-            c->lstamp = nullptr;
+            c->mem.drop(&c->lstamp);
         }
         c->graph_model = -1;
     }

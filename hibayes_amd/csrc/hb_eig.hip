@@ -535,20 +535,14 @@ int hb_eig_upload(const double *A_host, int64_t lda_host, int32_t n, int32_t dev
     HB_TRY(no_device("hb_eig_upload"));
     HB_HIP(hipSetDevice(device));
     const int64_t ld = (int64_t)n + (n & 1);
+    hb_bufs mem;
     double *p = nullptr;
-    if (hipMalloc(reinterpret_cast<void **>(&p), sizeof(double) * (size_t)ld * (size_t)n) != hipSuccess) {
-        (void)hipGetLastError();
-        char msg[160];
-        snprintf(msg, sizeof msg, "hb_eig_upload: hipMalloc: out of memory — the %d x %d matrix needs %.1f GB on the device", n, n, 8e-9 * (double)n * (double)n);
-        return hb_fail(HB_ERR_HIP, msg);
-    }
+    HB_TRY(mem.big(&p, (size_t)ld * (size_t)n, "hb_eig_upload", "the " + hb_dims(n) + " matrix"));
     hipError_t e = ld != n ? hipMemset(p, 0, sizeof(double) * (size_t)ld * (size_t)n) : hipSuccess;
     if (e == hipSuccess)
         e = hipMemcpy2D(p, sizeof(double) * (size_t)ld, A_host, sizeof(double) * (size_t)lda_host, sizeof(double) * (size_t)n, (size_t)n, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(p);
-        return hb_fail(HB_ERR_HIP, std::string("hb_eig_upload: ") + hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return hb_fail(HB_ERR_HIP, std::string("hb_eig_upload: ") + hipGetErrorString(e));
+    mem.release(p); // the caller's from here (hb_eig_release)
     *A_dev = p;
     *lda = ld;
     return HB_OK;
@@ -629,34 +623,22 @@ int hb_eig_vectors(hb_eig *h, const double *Z_host, int64_t ldz, double **K_dev,
     if (Z_host && ldz < n) return hb_fail(HB_ERR_INVALID, "hb_eig_vectors: leading dimension smaller than n");
     HB_TRY(no_device("hb_eig_vectors"));
     HB_HIP(hipSetDevice(h->device));
+    hb_bufs mem;
     double *K = nullptr;
-    const size_t kbytes = sizeof(double) * (size_t)h->ldk * (size_t)h->ldk;
-    if (hipMalloc(reinterpret_cast<void **>(&K), kbytes) != hipSuccess) {
-        (void)hipGetLastError();
-        char msg[160];
-        snprintf(msg, sizeof msg, "hb_eig_vectors: hipMalloc: out of memory — the %d x %d eigenvector matrix needs %.1f GB on the device", n, n, 1e-9 * (double)kbytes);
-        return hb_fail(HB_ERR_HIP, msg);
-    }
-    auto run = [&]() -> int {
-        HB_HIP(hipMemsetAsync(K, 0, kbytes, h->stream));
-        if (Z_host) {
-            // column strips of at most 256 MB: the pageable copy is staged strip by strip
-            const int strip = (int)std::max<int64_t>(1, ((int64_t)256 << 20) / ((int64_t)sizeof(double) * n));
-            for (int j = 0; j < n; j += strip)
-                HB_HIP(hipMemcpy2DAsync(K + (int64_t)j * h->ldk, sizeof(double) * (size_t)h->ldk, Z_host + (int64_t)j * ldz, sizeof(double) * (size_t)ldz,
-                                        sizeof(double) * (size_t)n, (size_t)std::min(strip, n - j), hipMemcpyHostToDevice, h->stream));
-        } else
-            hipLaunchKernelGGL(k_eig_identity, dim3(blocks(n)), dim3(ET), 0, h->stream, K, h->ldk, n);
-        HB_HIP(hipGetLastError());
-        HB_TRY(back_transform(h, K));
-        HB_HIP(hipStreamSynchronize(h->stream));
-        return HB_OK;
-    };
-    const int rc = run();
-    if (rc) {
-        (void)hipFree(K);
-        return rc;
-    }
+    HB_TRY(mem.big(&K, (size_t)h->ldk * (size_t)h->ldk, "hb_eig_vectors", "the " + hb_dims(n) + " eigenvector matrix"));
+    HB_HIP(hipMemsetAsync(K, 0, sizeof(double) * (size_t)h->ldk * (size_t)h->ldk, h->stream));
+    if (Z_host) {
+        // column strips of at most 256 MB: the pageable copy is staged strip by strip
+        const int strip = (int)std::max<int64_t>(1, ((int64_t)256 << 20) / ((int64_t)sizeof(double) * n));
+        for (int j = 0; j < n; j += strip)
+            HB_HIP(hipMemcpy2DAsync(K + (int64_t)j * h->ldk, sizeof(double) * (size_t)h->ldk, Z_host + (int64_t)j * ldz, sizeof(double) * (size_t)ldz,
+                                    sizeof(double) * (size_t)n, (size_t)std::min(strip, n - j), hipMemcpyHostToDevice, h->stream));
+    } else
+        hipLaunchKernelGGL(k_eig_identity, dim3(blocks(n)), dim3(ET), 0, h->stream, K, h->ldk, n);
+    HB_HIP(hipGetLastError());
+    HB_TRY(back_transform(h, K));
+    HB_HIP(hipStreamSynchronize(h->stream));
+    mem.release(K); // the caller's from here (hb_eig_release)
     *K_dev = K;
     *ldk = h->ldk;
     return HB_OK;
@@ -692,7 +674,7 @@ int hb_eig_download(const double *M_dev, int64_t ld_dev, int32_t n, int32_t devi
 
 void hb_eig_release(double *M_dev)
 {
-    if (M_dev) (void)hipFree(M_dev);
+    hb_free_released(M_dev);
 }
 
 void hb_eig_destroy(hb_eig *h)

@@ -41,6 +41,7 @@ struct hb_epsl {
     std::vector<int64_t> h_indptr; // the pattern, kept for a change of plan (hb_ctx_epsl_debug_set)
     std::vector<int32_t> h_indices;
     hb_epsl_sched plan;
+    hb_bufs mem; // every device and pinned buffer above
 };
 
 namespace {
@@ -277,11 +278,6 @@ void hb_epsl_free(hb_ctx *c)
 {
     hb_epsl *p = c ? c->epsl : nullptr;
     if (!p) return;
-    void *ptrs[] = {p->indptr, p->indices, p->rec_ptr, p->rec, p->idx, p->rows, p->steps, p->data, p->diag, p->zz, p->yJ, p->x, p->xold, p->b, p->t, p->xsum,
-                    p->parts, p->st};
-    for (void *v : ptrs)
-        if (v) (void)hipFree(v);
-    if (p->h_st) (void)hipHostFree(p->h_st);
     delete p;
     c->epsl = nullptr;
 }
@@ -432,46 +428,40 @@ int hb_ctx_epsl_setup(hb_ctx *c, const hb_epsl_desc *d)
         for (int64_t k = G.indptr[i]; k < G.indptr[i + 1]; k++)
             if (G.indices[k] == i) diag[i] = G.data[k];
 
-    auto fail = [&](int rc_) { hb_epsl_free(c); return rc_; };
-#define EPSL_TRY(expr)                                                                                   \
-    do {                                                                                                 \
-        hipError_t _e = (expr);                                                                          \
-        if (_e != hipSuccess) return fail(hb_fail(HB_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e))); \
-    } while (0)
     const size_t nch = (size_t)std::max((n + ET - 1) / ET, (q + ET - 1) / ET);
     p->steps_cap = q;
-    EPSL_TRY(hipMalloc(reinterpret_cast<void **>(&p->indptr), sizeof(int64_t) * (size_t)(q + 1)));
-    EPSL_TRY(hipMalloc(reinterpret_cast<void **>(&p->indices), sizeof(int32_t) * (size_t)std::max<int64_t>(nnz, 1)));
-    EPSL_TRY(hipMalloc(reinterpret_cast<void **>(&p->data), sizeof(double) * (size_t)std::max<int64_t>(nnz, 1)));
-    EPSL_TRY(hipMalloc(reinterpret_cast<void **>(&p->rec_ptr), sizeof(int32_t) * (size_t)(q + 1)));
-    EPSL_TRY(hipMalloc(reinterpret_cast<void **>(&p->rec), sizeof(int32_t) * (size_t)ne));
-    EPSL_TRY(hipMalloc(reinterpret_cast<void **>(&p->idx), sizeof(int32_t) * (size_t)ne));
-    EPSL_TRY(hipMalloc(reinterpret_cast<void **>(&p->rows), sizeof(int32_t) * (size_t)q));
-    EPSL_TRY(hipMalloc(reinterpret_cast<void **>(&p->steps), sizeof(int32_t) * (size_t)5 * (size_t)p->steps_cap));
-    EPSL_TRY(hipMalloc(reinterpret_cast<void **>(&p->yJ), sizeof(double) * (size_t)n));
-    EPSL_TRY(hipMalloc(reinterpret_cast<void **>(&p->parts), sizeof(double) * nch));
-    double **vecs[] = {&p->diag, &p->zz, &p->x, &p->xold, &p->b, &p->t, &p->xsum};
-    for (double **v : vecs) {
-        EPSL_TRY(hipMalloc(reinterpret_cast<void **>(v), sizeof(double) * (size_t)q));
-        EPSL_TRY(hipMemset(*v, 0, sizeof(double) * (size_t)q));
-    }
-    EPSL_TRY(hipMalloc(reinterpret_cast<void **>(&p->st), sizeof(double) * 8));
-    EPSL_TRY(hipMemset(p->st, 0, sizeof(double) * 8));
-    EPSL_TRY(hipHostMalloc(reinterpret_cast<void **>(&p->h_st), sizeof(double) * 8));
-    std::memset(p->h_st, 0, sizeof(double) * 8);
-    EPSL_TRY(hipMemcpy(p->indptr, G.indptr, sizeof(int64_t) * (size_t)(q + 1), hipMemcpyHostToDevice));
-    EPSL_TRY(hipMemcpy(p->indices, G.indices, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice));
-    EPSL_TRY(hipMemcpy(p->data, G.data, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice));
-    EPSL_TRY(hipMemcpy(p->rec_ptr, rec_ptr.data(), sizeof(int32_t) * (size_t)(q + 1), hipMemcpyHostToDevice));
-    EPSL_TRY(hipMemcpy(p->rec, rec.data(), sizeof(int32_t) * (size_t)ne, hipMemcpyHostToDevice));
-    EPSL_TRY(hipMemcpy(p->idx, idx.data(), sizeof(int32_t) * (size_t)ne, hipMemcpyHostToDevice));
-    EPSL_TRY(hipMemcpy(p->diag, diag.data(), sizeof(double) * (size_t)q, hipMemcpyHostToDevice));
-    EPSL_TRY(hipMemcpy(p->zz, zz.data(), sizeof(double) * (size_t)q, hipMemcpyHostToDevice));
-    EPSL_TRY(hipMemcpy(p->yJ, d->y_J, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
-#undef EPSL_TRY
-    rc = epsl_plan_upload(c);
-    if (rc) return fail(rc);
-    return HB_OK;
+    auto build = [&]() -> int {
+        hb_bufs &M = p->mem;
+        HB_TRY(M.get(&p->indptr, (size_t)(q + 1)));
+        HB_TRY(M.get(&p->indices, (size_t)nnz));
+        HB_TRY(M.get(&p->data, (size_t)nnz));
+        HB_TRY(M.get(&p->rec_ptr, (size_t)(q + 1)));
+        HB_TRY(M.get(&p->rec, (size_t)ne));
+        HB_TRY(M.get(&p->idx, (size_t)ne));
+        HB_TRY(M.get(&p->rows, (size_t)q));
+        HB_TRY(M.get(&p->steps, (size_t)5 * (size_t)p->steps_cap));
+        HB_TRY(M.get(&p->yJ, (size_t)n));
+        HB_TRY(M.get(&p->parts, nch));
+        // (zeroed on the null stream, like the copies behind them: those return after them)
+        double **vecs[] = {&p->diag, &p->zz, &p->x, &p->xold, &p->b, &p->t, &p->xsum};
+        for (double **v : vecs) HB_TRY(M.zeroed(v, (size_t)q, nullptr));
+        HB_TRY(M.zeroed(&p->st, 8, nullptr));
+        HB_TRY(M.pin(&p->h_st, 8));
+        std::memset(p->h_st, 0, sizeof(double) * 8);
+        HB_HIP(hipMemcpy(p->indptr, G.indptr, sizeof(int64_t) * (size_t)(q + 1), hipMemcpyHostToDevice));
+        HB_HIP(hipMemcpy(p->indices, G.indices, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice));
+        HB_HIP(hipMemcpy(p->data, G.data, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice));
+        HB_HIP(hipMemcpy(p->rec_ptr, rec_ptr.data(), sizeof(int32_t) * (size_t)(q + 1), hipMemcpyHostToDevice));
+        HB_HIP(hipMemcpy(p->rec, rec.data(), sizeof(int32_t) * (size_t)ne, hipMemcpyHostToDevice));
+        HB_HIP(hipMemcpy(p->idx, idx.data(), sizeof(int32_t) * (size_t)ne, hipMemcpyHostToDevice));
+        HB_HIP(hipMemcpy(p->diag, diag.data(), sizeof(double) * (size_t)q, hipMemcpyHostToDevice));
+        HB_HIP(hipMemcpy(p->zz, zz.data(), sizeof(double) * (size_t)q, hipMemcpyHostToDevice));
+        HB_HIP(hipMemcpy(p->yJ, d->y_J, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+        return epsl_plan_upload(c);
+    };
+    rc = build();
+    if (rc) hb_epsl_free(c);
+    return rc;
 }
 
 int hb_ctx_epsl_step(hb_ctx *c, double vare, double veps_in, uint64_t seed, int64_t iter, double zJ, double chis, double s2_df)

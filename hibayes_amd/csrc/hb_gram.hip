@@ -134,10 +134,12 @@ int hb_build_gcert(hb_ctx *c)
 {
     c->gcert_ok = false;
     if (!c->gcert_on || c->P % 4 != 0 || c->row_reduce) return HB_OK; // (row-sharded mode: the local blocks are partial sums)
-    if (!c->ga) {
-        HB_HIP(hipMalloc(reinterpret_cast<void **>(&c->ga), sizeof(int32_t) * (size_t)c->m_pad));
-        HB_HIP(hipMalloc(reinterpret_cast<void **>(&c->gB), sizeof(int32_t) * (size_t)c->m_pad));
-        HB_HIP(hipMalloc(reinterpret_cast<void **>(&c->gcmax), sizeof(int32_t) * (size_t)c->m_pad));
+    if (!c->gcmax) { // (the last of the three: all of them or none)
+        c->mem.drop(&c->ga);
+        c->mem.drop(&c->gB);
+        HB_TRY(c->mem.get(&c->ga, (size_t)c->m_pad));
+        HB_TRY(c->mem.get(&c->gB, (size_t)c->m_pad));
+        HB_TRY(c->mem.get(&c->gcmax, (size_t)c->m_pad));
     }
     hipLaunchKernelGGL(k_g16_ab, dim3((c->m_pad + 255) / 256), dim3(256), 0, c->stream, c->s1, c->m_pad, (double)c->n, c->ga, c->gB);
     HB_HIP(hipMemsetAsync(c->gcmax, 0, sizeof(int32_t) * (size_t)c->m_pad, c->stream));
@@ -158,15 +160,14 @@ int hb_build_gram_impl(hb_ctx *c)
     const size_t colbytes = (size_t)c->ld * c->P;
     int chunk = (int)std::max<size_t>(1, ((size_t)1 << 31) / colbytes); // ~2 GB of panels per window
     chunk = std::min(chunk, c->npanels);
+    hb_bufs mem;
     int8_t *win = nullptr;
-    HB_HIP(hipMalloc(reinterpret_cast<void **>(&win), colbytes * (size_t)(chunk + c->Lg)));
-    int rc = HB_OK;
-    for (int pa = 0; pa < c->npanels && rc == HB_OK; pa += chunk) {
+    HB_TRY(mem.get(&win, colbytes * (size_t)(chunk + c->Lg)));
+    for (int pa = 0; pa < c->npanels; pa += chunk) {
         const int pb = std::min(c->npanels, pa + chunk), first = std::max(0, pa - c->Lg);
-        rc = hbk_unpack2(c, first * c->P, (pb - first) * c->P, win);
-        if (rc == HB_OK) rc = gram_launch(c, win - (int64_t)first * (int64_t)colbytes, pa, pb);
-        if (rc == HB_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = hb_fail(HB_ERR_HIP, "hb_ctx_build_gram: window build failed");
+        HB_TRY(hbk_unpack2(c, first * c->P, (pb - first) * c->P, win));
+        HB_TRY(gram_launch(c, win - (int64_t)first * (int64_t)colbytes, pa, pb));
+        if (hipStreamSynchronize(c->stream) != hipSuccess) return hb_fail(HB_ERR_HIP, "hb_ctx_build_gram: window build failed");
     }
-    (void)hipFree(win);
-    return rc;
+    return HB_OK;
 }

@@ -37,6 +37,7 @@ struct hb_poly {
     double *h_st = nullptr;  // pinned mirror, filled by the sweep's fetch
     int cpc = 0, nchunk = 0; // columns per chunk of k_poly_kw, chunks
     int stored = 0;          // records accumulated in k_sum
+    hb_bufs mem;             // every buffer above but a borrowed K
 };
 
 namespace {
@@ -377,10 +378,6 @@ void hb_poly_free(hb_ctx *c)
 {
     hb_poly *p = c ? c->poly : nullptr;
     if (!p) return;
-    void *ptrs[] = {p->K_own, p->Kval, p->k_cur, p->k_sum, p->t, p->w, p->ev, p->Kg, p->qt, p->parts, p->vec, p->st};
-    for (void *q : ptrs)
-        if (q) (void)hipFree(q);
-    if (p->h_st) (void)hipHostFree(p->h_st);
     delete p;
     c->poly = nullptr;
 }
@@ -480,13 +477,7 @@ int hb_grm_build(hb_ctx *c, double lambda, int32_t flags, double *G_host, double
 
     hb_bufs mem;
     struct { double *G = nullptr, *d = nullptr; long long *a = nullptr; } B;
-    if (hipMalloc(reinterpret_cast<void **>(&B.G), sizeof(double) * (size_t)n * (size_t)n) != hipSuccess) {
-        (void)hipGetLastError();
-        char msg[160];
-        snprintf(msg, sizeof msg, "hb_grm_build: hipMalloc: out of memory — the %d x %d matrix needs %.1f GB on the device", n, n, 8e-9 * (double)n * (double)n);
-        return hb_fail(HB_ERR_HIP, msg);
-    }
-    mem.dev.push_back(B.G);
+    HB_TRY(mem.big(&B.G, (size_t)n * (size_t)n, "hb_grm_build", "the " + hb_dims(n) + " matrix"));
     HB_TRY(mem.get(&B.d, (size_t)(n + 1)));
     HB_TRY(mem.zeroed(&B.a, (size_t)n, c->stream));
     long long *S = reinterpret_cast<long long *>(B.G);
@@ -528,7 +519,7 @@ int hb_grm_build(hb_ctx *c, double lambda, int32_t flags, double *G_host, double
 
 void hb_grm_free(double *G_dev)
 {
-    if (G_dev) (void)hipFree(G_dev);
+    hb_free_released(G_dev);
 }
 
 int hb_ctx_poly_setup(hb_ctx *c, const double *Kival, const double *Ki, int64_t ld, int32_t on_device)
@@ -549,44 +540,32 @@ int hb_ctx_poly_setup(hb_ctx *c, const double *Kival, const double *Ki, int64_t 
     c->poly = p;
     p->n = n;
     p->ld = on_device ? ld : (int64_t)n + (n & 1);
-    auto fail = [&](int rc) { hb_poly_free(c); return rc; };
-#define POLY_TRY(expr)                                                                                   \
-    do {                                                                                                 \
-        hipError_t _e = (expr);                                                                          \
-        if (_e != hipSuccess) return fail(hb_fail(HB_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e))); \
-    } while (0)
-    if (on_device) p->K = Ki;
-    else {
-        if (hipMalloc(reinterpret_cast<void **>(&p->K_own), sizeof(double) * (size_t)p->ld * (size_t)n) != hipSuccess) {
-            (void)hipGetLastError();
-            char msg[160];
-            snprintf(msg, sizeof msg, "hb_ctx_poly_setup: hipMalloc: out of memory — the %d x %d eigenvector matrix needs %.1f GB on the device", n, n, 8e-9 * (double)n * (double)n);
-            return fail(hb_fail(HB_ERR_HIP, msg));
+    auto build = [&]() -> int {
+        if (on_device) p->K = Ki;
+        else {
+            HB_TRY(p->mem.big(&p->K_own, (size_t)p->ld * (size_t)n, "hb_ctx_poly_setup", "the " + hb_dims(n) + " eigenvector matrix"));
+            if (p->ld != n) HB_HIP(hipMemsetAsync(p->K_own, 0, sizeof(double) * (size_t)p->ld * (size_t)n, nullptr));
+            HB_HIP(hipMemcpy2D(p->K_own, sizeof(double) * (size_t)p->ld, Ki, sizeof(double) * (size_t)ld, sizeof(double) * (size_t)n, (size_t)n, hipMemcpyHostToDevice));
+            p->K = p->K_own;
         }
-        if (p->ld != n) POLY_TRY(hipMemset(p->K_own, 0, sizeof(double) * (size_t)p->ld * (size_t)n));
-        POLY_TRY(hipMemcpy2D(p->K_own, sizeof(double) * (size_t)p->ld, Ki, sizeof(double) * (size_t)ld, sizeof(double) * (size_t)n, (size_t)n, hipMemcpyHostToDevice));
-        p->K = p->K_own;
-    }
-    // chunks of k_poly_kw: a function of n alone (the summation order must not depend on the device), about 2048 workgroups, chunks of >= 64 columns
-    const int rowblocks = ((n + 1) / 2 + PT - 1) / PT;
-    const int want = std::max(1, 2048 / rowblocks);
-    p->cpc = std::max(64, (n + want - 1) / want);
-    p->nchunk = (n + p->cpc - 1) / p->cpc;
-    const size_t vl = sizeof(double) * (size_t)(p->ld + 2);
-    double **vecs[] = {&p->Kval, &p->k_cur, &p->k_sum, &p->t, &p->w, &p->ev, &p->Kg, &p->qt, &p->vec};
-    for (double **v : vecs) {
-        POLY_TRY(hipMalloc(reinterpret_cast<void **>(v), vl));
-        POLY_TRY(hipMemset(*v, 0, vl));
-    }
-    POLY_TRY(hipMalloc(reinterpret_cast<void **>(&p->parts), sizeof(double) * (size_t)p->ld * (size_t)p->nchunk));
-    POLY_TRY(hipMemset(p->parts, 0, sizeof(double) * (size_t)p->ld * (size_t)p->nchunk));
-    POLY_TRY(hipMalloc(reinterpret_cast<void **>(&p->st), sizeof(double) * 4));
-    POLY_TRY(hipMemset(p->st, 0, sizeof(double) * 4));
-    POLY_TRY(hipHostMalloc(reinterpret_cast<void **>(&p->h_st), sizeof(double) * 4));
-    std::memset(p->h_st, 0, sizeof(double) * 4);
-    POLY_TRY(hipMemcpy(p->Kval, Kival, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
-#undef POLY_TRY
-    return HB_OK;
+        // chunks of k_poly_kw: a function of n alone (the summation order must not depend on the device), about 2048 workgroups, chunks of >= 64 columns
+        const int rowblocks = ((n + 1) / 2 + PT - 1) / PT;
+        const int want = std::max(1, 2048 / rowblocks);
+        p->cpc = std::max(64, (n + want - 1) / want);
+        p->nchunk = (n + p->cpc - 1) / p->cpc;
+        // (zeroed on the null stream, like the copy of Kval behind them: that copy returns after them)
+        double **vecs[] = {&p->Kval, &p->k_cur, &p->k_sum, &p->t, &p->w, &p->ev, &p->Kg, &p->qt, &p->vec};
+        for (double **v : vecs) HB_TRY(p->mem.zeroed(v, (size_t)(p->ld + 2), nullptr));
+        HB_TRY(p->mem.zeroed(&p->parts, (size_t)p->ld * (size_t)p->nchunk, nullptr));
+        HB_TRY(p->mem.zeroed(&p->st, 4, nullptr));
+        HB_TRY(p->mem.pin(&p->h_st, 4));
+        std::memset(p->h_st, 0, sizeof(double) * 4);
+        HB_HIP(hipMemcpy(p->Kval, Kival, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+        return HB_OK;
+    };
+    const int rc = build();
+    if (rc) hb_poly_free(c);
+    return rc;
 }
 
 int hb_ctx_poly_step(hb_ctx *c, double vare, double vb_in, uint64_t seed, int64_t iter, double chis, double s2_df)

@@ -8,66 +8,16 @@
 #include <vector>
 #include "../../include/hibayes_gpu.h"
 #include "hb_matvecplan.hpp"
+#include "hb_bufs.hpp" // HB_HIP, HB_TRY, hb_bufs: every device and pinned allocation
 
-// thread-local last error (hb_last_error)
+// thread-local last error (hb_last_error); hb_fail is declared in hb_bufs.hpp
 void hb_set_error(const std::string &msg);
-int hb_fail(int status, const std::string &msg);
-
-#define HB_HIP(expr)                                                                         \
-    do {                                                                                     \
-        hipError_t _e = (expr);                                                              \
-        if (_e != hipSuccess)                                                                \
-            return hb_fail(HB_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));   \
-    } while (0)
-
-// a call that has already reported its failure (hb_fail): pass its status on
-#define HB_TRY(x)             \
-    do {                      \
-        const int _rc = (x);  \
-        if (_rc) return _rc;  \
-    } while (0)
 
 // one line of a verbose run: to the caller's callback, or to stdout
 void hb_line(int verbose, hb_log_fn log, void *log_user, const char *fmt, ...);
 
 using hb_clk = std::chrono::steady_clock;
 inline double hb_since(hb_clk::time_point t0) { return std::chrono::duration<double>(hb_clk::now() - t0).count(); }
-
-// the device and pinned allocations of one call or run, freed on every way out. An owner that also holds a graph or a stream
-// destroys the graph, calls clear() and destroys the stream, in that order.
-struct hb_bufs {
-    std::vector<void *> dev, pinned;
-    hb_bufs() = default;
-    hb_bufs(const hb_bufs &) = delete;
-    hb_bufs &operator=(const hb_bufs &) = delete;
-    ~hb_bufs() { clear(); }
-    void clear()
-    {
-        for (void *q : dev) (void)hipFree(q);
-        for (void *q : pinned) (void)hipHostFree(q);
-        dev.clear();
-        pinned.clear();
-    }
-    template <typename T> int get(T **p, size_t count) // device memory, as hipMalloc leaves it
-    {
-        HB_HIP(hipMalloc(reinterpret_cast<void **>(p), std::max<size_t>(count, 1) * sizeof(T)));
-        dev.push_back(*p);
-        return HB_OK;
-    }
-    template <typename T> int zeroed(T **p, size_t count, hipStream_t s) // device memory, zeroed on stream s
-    {
-        HB_TRY(get(p, count));
-        HB_HIP(hipMemsetAsync(*p, 0, std::max<size_t>(count, 1) * sizeof(T), s));
-        return HB_OK;
-    }
-    template <typename T> int pin(T **p, size_t count) // pinned host memory
-    {
-        HB_HIP(hipHostMalloc(reinterpret_cast<void **>(p), std::max<size_t>(count, 1) * sizeof(T)));
-        pinned.push_back(*p);
-        return HB_OK;
-    }
-    void release(void *q) { dev.erase(std::remove(dev.begin(), dev.end(), q), dev.end()); } // the caller keeps q
-};
 
 // layout of the per-sweep scalar block the kernels accumulate into / the host reads back
 // Words that one workgroup writes through and others read behind a flag — the panels' move counts, the groups' bounds on max |yadj| —
@@ -120,6 +70,7 @@ struct hb_ctx {
     hipStream_t s_warm = nullptr;      // k_warm where k_fwd has s_upd (BayesR)
     std::vector<hipEvent_t> ev_dot, ev_chain, ev_upd; // cross-stream dependencies of one sweep
     hipEvent_t ev_fork = nullptr;
+    hb_bufs mem; // every device and pinned buffer below, whoever allocates it (hb_ctx.hip, hb_gram.hip): hb_ctx_destroy clears it between the graphs and the streams
 
     int8_t *X = nullptr;
     // 2-bit resident layout (hb_dotq2.hpp; hb_ctx_set_layout): layout == 2 makes the sweep's kernels read X2; X may then be dropped

@@ -940,7 +940,7 @@ __global__ __launch_bounds__(256) void k_copy_segs(seg_args s)
     char *dst = s.a[k];
     const char *src = s.b[k];
     const size_t nb = s.bytes[k], n16 = nb / 16;
-    // (every buffer is a hipMalloc allocation or a 256-byte aligned offset into one)
+    // (every buffer is a device allocation of hb_bufs or a 256-byte aligned offset into one)
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += (size_t)gridDim.x * blockDim.x)
         reinterpret_cast<uint4 *>(dst)[i] = reinterpret_cast<const uint4 *>(src)[i];
     if (blockIdx.x == 0)

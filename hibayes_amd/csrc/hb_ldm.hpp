@@ -29,6 +29,7 @@ struct hb_ldm {
     int32_t *d_runn = nullptr; // [m] ... and how many there are (contiguous: rows are sorted)
     int64_t csc_nnz = 0;
     std::vector<int32_t> grp_lo, grp_hi; // per group: the rows [lo, hi) its columns touch (lo == hi: none)
+    hb_bufs mem; // every pinned and device buffer above
 };
 
 #define HB_LDM_GS 512 // markers per group of the sparse sweep (SS_GS, hb_sbayes_sparse.hpp)

@@ -182,17 +182,17 @@ int host_reserve(hb_ldm *l, int64_t need)
     const int64_t cap = std::max<int64_t>(need, std::max<int64_t>(l->h_cap * 2, 1 << 16));
     int32_t *ni = nullptr;
     double *nv = nullptr;
-    HB_HIP(hipHostMalloc(reinterpret_cast<void **>(&ni), sizeof(int32_t) * (size_t)cap));
-    if (hipHostMalloc(reinterpret_cast<void **>(&nv), sizeof(double) * (size_t)cap) != hipSuccess) {
-        (void)hipHostFree(ni);
+    HB_TRY(l->mem.pin(&ni, (size_t)cap));
+    if (l->mem.pin(&nv, (size_t)cap)) {
+        l->mem.drop(&ni);
         return hb_fail(HB_ERR_HIP, "hb_ldm_build: out of pinned host memory");
     }
     if (l->h_used) {
         std::memcpy(ni, l->h_idx, sizeof(int32_t) * (size_t)l->h_used);
         std::memcpy(nv, l->h_val, sizeof(double) * (size_t)l->h_used);
     }
-    if (l->h_idx) (void)hipHostFree(l->h_idx);
-    if (l->h_val) (void)hipHostFree(l->h_val);
+    l->mem.drop(&l->h_idx);
+    l->mem.drop(&l->h_val);
     l->h_idx = ni;
     l->h_val = nv;
     l->h_cap = cap;
@@ -278,17 +278,14 @@ int build(hb_ctx *c, const int32_t *chr, bool sparse, double chisq, int64_t stri
         l->col_off.assign(m, 0);
         l->col_cnt.assign(m, 0);
     } else {
-        HB_HIP(hipHostMalloc(reinterpret_cast<void **>(&l->h_dense), sizeof(double) * (size_t)m * (size_t)m));
+        HB_TRY(l->mem.pin(&l->h_dense, (size_t)m * (size_t)m));
     }
     if (!Xfull && !winA) HB_TRY(D.get(&winA, (size_t)ld * (size_t)std::min(w, m)));
     // a dense device copy for the sampler is kept when it fits beside the context and the staging with room to spare
     {
         size_t fr = 0, tot = 0;
         const size_t need = sizeof(double) * (size_t)m * (size_t)m;
-        if (hipMemGetInfo(&fr, &tot) == hipSuccess && need <= fr / 2 && hipMalloc(reinterpret_cast<void **>(&l->d_dense), need) != hipSuccess) {
-            (void)hipGetLastError();
-            l->d_dense = nullptr;
-        }
+        if (hipMemGetInfo(&fr, &tot) == hipSuccess && need <= fr / 2) (void)l->mem.try_get(&l->d_dense, (size_t)m * (size_t)m); // (refused: nullptr and no error, built on demand)
     }
     ld_epi e{c->s1, d_mean, d_xx, d_chr, (double)c->n, chisq};
     const auto kstrip = sparse ? k_ld_strip<true> : k_ld_strip<false>;
@@ -380,7 +377,7 @@ int hb_ldm_device_dense(hb_ldm *l, const double **out)
         const int m = l->m;
         double *d = nullptr;
         hb_bufs D;
-        HB_TRY(D.get(&d, (size_t)m * (size_t)m)); // (released below once the copy is complete)
+        HB_TRY(D.get(&d, (size_t)m * (size_t)m)); // (the handle's below, once the copy is complete)
         if (l->kind == HB_LDM_KIND_DENSE) {
             HB_HIP(hipMemcpy(d, l->h_dense, sizeof(double) * (size_t)m * (size_t)m, hipMemcpyHostToDevice));
         } else {
@@ -420,7 +417,7 @@ int hb_ldm_device_dense(hb_ldm *l, const double **out)
                 j0 = j1;
             }
         }
-        D.release(d);
+        D.give(l->mem, d);
         l->d_dense = d;
     }
     *out = l->d_dense;
@@ -501,7 +498,7 @@ int hb_ldm_device_csc(hb_ldm *l, hb_ldm_csc *out)
         HB_HIP(hipMemcpy(d_runn, runn.data(), sizeof(int32_t) * m, hipMemcpyHostToDevice));
         HB_HIP(hipMemcpy(d_ri, ri.data(), sizeof(int32_t) * ri.size(), hipMemcpyHostToDevice));
         HB_HIP(hipMemcpy(d_va, va.data(), sizeof(double) * va.size(), hipMemcpyHostToDevice));
-        D.dev.clear(); // kept: the handle owns them from here
+        for (void *q : {(void *)d_cp, (void *)d_run, (void *)d_ri, (void *)d_cnt, (void *)d_runn, (void *)d_va}) D.give(l->mem, q); // the handle's from here
         l->d_run = d_run;
         l->d_ri = d_ri;
         l->d_cnt = d_cnt;
@@ -519,13 +516,7 @@ extern "C" {
 void hb_ldm_destroy(hb_ldm *l)
 {
     if (!l) return;
-    if (l->d_dense || l->h_dense || l->h_idx || l->h_val || l->d_cp) (void)hipSetDevice(l->device);
-    if (l->d_dense) (void)hipFree(l->d_dense);
-    for (void *q : {(void *)l->d_cp, (void *)l->d_ri, (void *)l->d_va, (void *)l->d_cnt, (void *)l->d_run, (void *)l->d_runn})
-        if (q) (void)hipFree(q);
-    if (l->h_dense) (void)hipHostFree(l->h_dense);
-    if (l->h_idx) (void)hipHostFree(l->h_idx);
-    if (l->h_val) (void)hipHostFree(l->h_val);
+    if (!l->mem.dev.empty() || !l->mem.pinned.empty()) (void)hipSetDevice(l->device);
     delete l;
 }
 

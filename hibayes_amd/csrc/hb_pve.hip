@@ -232,7 +232,7 @@ int hb_ctx_window_var(hb_ctx *c, const double *A, int64_t ldA, int32_t R, const 
                 int k1 = k0, nsg = 0;
                 while (k1 <= nch && (k1 == k0 || (size_t)(nsg + hchunks[2 * k1 + 1]) <= fit) && k1 - k0 < 65535) nsg += hchunks[2 * k1 + 1], k1++;
                 if ((size_t)nsg > part_segs) {
-                    if (dpart) { bufs.release(dpart); HB_HIP(hipStreamSynchronize(c->stream)); HB_HIP(hipFree(dpart)); dpart = nullptr; }
+                    if (dpart) { HB_HIP(hipStreamSynchronize(c->stream)); bufs.drop(&dpart); }
                     HB_TRY(bufs.get(&dpart, (size_t)nsg * nrb * 2 * RB));
                     part_segs = (size_t)nsg;
                 }

@@ -57,6 +57,7 @@ struct hb_run {
     hb_ctx *c = nullptr;
     bool own_ctx = false;
     double *r0 = nullptr, *u0 = nullptr, *xbuf_own = nullptr, *xbuf = nullptr;
+    hb_bufs mem; // r0, u0, xbuf_own
     size_t xcount = 0;
     // ---- state of the chain ----
     static constexpr double h2 = 0.5; // :119-124
@@ -103,9 +104,7 @@ struct hb_run {
 
     ~hb_run()
     {
-        if (r0) (void)hipFree(r0);
-        if (u0) (void)hipFree(u0);
-        if (xbuf_own) (void)hipFree(xbuf_own);
+        mem.clear(); // (buffers before the context's streams: hb_bufs.hpp)
         if (c && own_ctx) hb_ctx_destroy(c);
     }
 
@@ -641,11 +640,11 @@ int hb_run::open_exchange()
     if (sharded || rowmode) {
         if (a.exchange_buf) xbuf = static_cast<double *>(a.exchange_buf);
         else {
-            HB_HIP(hipMalloc(reinterpret_cast<void **>(&xbuf_own), sizeof(double) * xcount));
+            HB_TRY(mem.get(&xbuf_own, xcount));
             xbuf = xbuf_own;
         }
-        HB_HIP(hipMalloc(reinterpret_cast<void **>(&r0), sizeof(double) * n));
-        HB_HIP(hipMalloc(reinterpret_cast<void **>(&u0), sizeof(double) * n));
+        HB_TRY(mem.get(&r0, (size_t)n));
+        HB_TRY(mem.get(&u0, (size_t)n));
     }
     if (rowmode) {
         c->row_reduce = &hb_run::row_hook;

@@ -554,11 +554,7 @@ int stedc_run(const double *d, const double *e, int n, double *w, double *Z, dou
     HB_TRY(mem.get(&g_rnj, n)); HB_TRY(mem.get(&g_cp, (size_t)4 * n)); HB_TRY(mem.get(&g_order, n));
     HB_TRY(mem.get(&g_M, std::max<size_t>(1, tree.merges.size())));
     const bool any_merge = !tree.merges.empty();
-    if (any_merge && hipMalloc(reinterpret_cast<void **>(&g_Ut), sizeof(double) * (size_t)n * SS) != hipSuccess) {
-        (void)hipGetLastError();
-        return hb_fail(HB_ERR_HIP, "hb_eig_tridiagonal: hipMalloc: out of memory for the strip of U");
-    }
-    if (any_merge) mem.dev.push_back(g_Ut);
+    if (any_merge) HB_TRY(mem.big(&g_Ut, (size_t)n * SS, "hb_eig_tridiagonal", "the strip of U of the " + hb_dims(n) + " eigenvector matrix"));
     HB_HIP(hipMemcpyAsync(g_dt, dt.data(), sizeof(double) * n, hipMemcpyHostToDevice, st));
     HB_HIP(hipMemcpyAsync(g_es, es.data(), sizeof(double) * n, hipMemcpyHostToDevice, st));
     {
@@ -755,15 +751,12 @@ int hb_eig_tridiagonal(const double *d_host, const double *e_host, int32_t n, in
     HB_HIP(hipSetDevice(device));
     const int64_t ld = ((int64_t)n + 63) / 64 * 64;
     const size_t bytes = sizeof(double) * (size_t)ld * (size_t)ld;
+    hb_bufs mem;
     double *Z = nullptr, *W = nullptr;
-    if (hipMalloc(reinterpret_cast<void **>(&Z), bytes) != hipSuccess || hipMalloc(reinterpret_cast<void **>(&W), bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        if (Z) (void)hipFree(Z);
-        char msg[200];
-        snprintf(msg, sizeof msg, "hb_eig_tridiagonal: hipMalloc: out of memory — the %d x %d eigenvector matrix and its workspace need %.1f GB on the device", n, n,
-                 2e-9 * (double)bytes);
-        return hb_fail(HB_ERR_HIP, msg);
-    }
+    char both[96]; // (the call holds two such matrices: the refusal of either tells the total as well)
+    snprintf(both, sizeof both, " (the call needs it and a workspace as large, %.1f GB together)", 2e-9 * (double)bytes);
+    HB_TRY(mem.big(&Z, (size_t)ld * (size_t)ld, "hb_eig_tridiagonal", "the " + hb_dims(n) + " eigenvector matrix" + both));
+    HB_TRY(mem.big(&W, (size_t)ld * (size_t)ld, "hb_eig_tridiagonal", "the workspace of the " + hb_dims(n) + " eigenvector matrix" + both));
     hipStream_t st = nullptr;
     double *Zf = nullptr;
     auto run = [&]() -> int {
@@ -777,12 +770,8 @@ int hb_eig_tridiagonal(const double *d_host, const double *e_host, int32_t n, in
         (void)hipStreamSynchronize(st);
         (void)hipStreamDestroy(st);
     }
-    if (rc) {
-        (void)hipFree(Z);
-        (void)hipFree(W);
-        return rc;
-    }
-    (void)hipFree(Zf == Z ? W : Z);
+    if (rc) return rc;
+    mem.release(Zf); // the caller's from here (hb_eig_release, or hb_eig_vectors_dev takes it over); the other of the two goes with this call
     *Z_dev = Zf;
     *ldz = ld;
     return HB_OK;

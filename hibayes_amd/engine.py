@@ -11,6 +11,14 @@ MODEL_INDEX = {"BayesRR": 1, "BayesA": 2, "BayesB": 3, "BayesBpi": 3, "BayesC": 
                "BayesL": 5, "BayesR": 6}
 
 
+def live_buffers():
+    """(buffers, bytes): the device and pinned buffers the library holds in this process right now, over every context, run and handle
+    (hb_debug_live_buffers). Back at its earlier value after every close(), destroy and free."""
+    nb, by = C.c_int64(), C.c_int64()
+    check(lib().hb_debug_live_buffers(C.byref(nb), C.byref(by)))
+    return nb.value, by.value
+
+
 class Context:
     def __init__(self, n, m, device=0, panel=0, precise=2, m_offset=0, seed=666666):
         self.L = lib()

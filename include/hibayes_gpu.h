@@ -501,6 +501,8 @@ int hb_cg_run_sparse(const hb_cg_args *args, hb_ldm *ldm, hb_cg_out *out);
  * ------------------------------------------------------------------------------------ */
 #define HB_GRM_RAW 1
 int hb_grm_build(hb_ctx *c, double lambda, int32_t flags, double *G_host, double **G_dev);
+/* Frees hb_grm_build's G_dev. Only a device matrix that this library handed out (hb_grm_build, hb_eig_upload, hb_eig_vectors, hb_eig_tridiagonal):
+ * NULL and any other pointer are left alone — memory the caller allocated itself is the caller's to free. */
 void hb_grm_free(double *G_dev);
 
 /* ------------------------------------------------------------------------------------
@@ -552,7 +554,8 @@ int hb_stedc_plan(int32_t n, const int32_t *splits, int32_t nsplit, int32_t cap,
 int hb_stedc_stats(double *out, int32_t count);
 /* An n x n device matrix of this interface — K (the Ki of R/bayes.r:292-294), or the reduced A (src/rm.cpp:46-52) — to a host column-major array. */
 int hb_eig_download(const double *M_dev, int64_t ld_dev, int32_t n, int32_t device, double *M_host, int64_t ld_host);
-/* Frees what hb_eig_upload, hb_eig_vectors or hb_eig_tridiagonal allocated (the Ki of R/bayes.r:292-294 once the fit is done). */
+/* Frees what hb_eig_upload, hb_eig_vectors or hb_eig_tridiagonal allocated (the Ki of R/bayes.r:292-294 once the fit is done), or hb_grm_build's
+ * G_dev. Only those: NULL and a pointer this library did not hand out are left alone — memory the caller allocated itself is the caller's to free. */
 void hb_eig_release(double *M_dev);
 /* Ends the borrowing of A_dev and frees the handle's panels (src/rm.cpp:46-52 keeps nothing either). NULL is allowed. */
 void hb_eig_destroy(hb_eig *h);
@@ -917,6 +920,11 @@ int hb_ctx_debug_get_cert(hb_ctx *c, int32_t *ok, int32_t *Lg, int32_t *ga, int3
  * pointers may be NULL. Fails before the first pipelined sweep. */
 int hb_ctx_debug_get_opening(hb_ctx *c, int32_t *nslot, double *kappa, double *candf, int32_t *has_opn, float *thr0f, int32_t *opn,
                              int32_t *slot_of, int32_t *hotpack);
+/* Debug read-out for the ownership tests (tests/test_gpu_ownership.py): what the library holds in this process right now — *buffers: the device
+ * and pinned host buffers allocated and not yet freed, over every context, run and handle and every buffer handed to the caller (hb_grm_build's
+ * G_dev, hb_eig_upload's A_dev, ...); *bytes: their sizes added up. (0, 0) when the library is loaded, and back at its earlier value after every
+ * destroy, free and release and after every call that fails. Needs no device and touches none; either pointer may be NULL. */
+int hb_debug_live_buffers(int64_t *buffers, int64_t *bytes);
 
 #ifdef __cplusplus
 }
