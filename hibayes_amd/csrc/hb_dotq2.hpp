@@ -23,7 +23,8 @@
 // w & 0x30303030 leave them scaled by 1, 4, 16, and (w >> 1) & 0x60606060 by 32 (0xc0 would be a negative int8) — and each scale
 // sums into its own accumulator; the four are combined exactly at the tile's end (a sum of multiples of 4^k shifts back without
 // loss). Five mask operations per 16 genotypes instead of seven, and four independent dot4 chains per plane instead of one.
-// The scale-32 sums bound a tile: rows x 96 x 128 < 2^31, i.e. at most 174 000 individuals per tile (the host splits taller columns).
+// The scale-32 sums bound a tile: that accumulator sees one row in four, and (rows / 4) x 96 x 128 < 2^31 holds up to 174 762 of them,
+// i.e. at most 699 050 individuals per tile (the host splits taller columns: plan_matvec keeps a tile at 131 072).
 
 // RS: individuals per stage (512 or 256). A 1-KiB DMA piece holds 4096 / RS columns x RS individuals of the tile, or 1024 / RS
 // digit planes x RS individuals.

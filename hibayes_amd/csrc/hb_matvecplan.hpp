@@ -111,7 +111,9 @@ static inline hb_matvec_plan plan_matvec(const hb_matvec_shape &s, const hb_matv
         // waves stream better than many short ones; tools/dotq_bench.hip)
         const int nst = (int)(s.ld / HBQ_RS), ncg = ncols / 64;
         const int ns = std::max(1, std::min(nst, (int)((double)k.dotq_tiles / ncg + 0.5)));
-        const int NS = std::min(1024, (nst + ns - 1) / ns); // (int32 accumulators: NS * 128 rows * 127 * 128 < 2^31)
+        // (int32 accumulators, digits in [-128, 127] against every int8 code, -128 included — hb_ctx_upload_genotype_i8 admits it:
+        // NS * 128 rows * 128 * 128 < 2^31 holds up to NS = 1023; at 1024 a column of -128 on planes of -128 sums to 2^31 and wraps)
+        const int NS = std::min(1023, (nst + ns - 1) / ns);
         return tiled(HB_MV_DOTQ, nst, NS, ncg, ncg * ((nst + NS - 1) / NS), s.dense ? HBU_LDS : HBQ_LDS);
     }
     // the 2-bit resident layout (hb_dotq2.hpp): about two long-lived waves per compute unit
@@ -136,7 +138,9 @@ static inline hb_matvec_plan plan_matvec(const hb_matvec_shape &s, const hb_matv
     // (the matrix-core kernel streams best with few, long tiles — its per-stage work is an eighth of the v_dot4 kernel's, so a tile's fixed
     // costs weigh more: ~800 tiles per 3584-column launch)
     int ns = std::max(1, std::min(std::max(1, nst / 4), (int)((double)(mfma && !k.dotq2_tiles_set ? ((q2m_g == 0 || q2m_g == 3) ? 900 : 800) : k.dotq2_tiles) / ncg + 0.5)));
-    // (int32 accumulators of genotypes scaled by up to 32 — Q2_SCALED, k_dotq2m: rows x 96 x 128 < 2^31 bounds a tile at 174 000 individuals)
+    // (int32 accumulators of genotypes scaled by up to 32 — Q2_SCALED, k_dotq2m. The scale-32 accumulator sees one row in four, 174 762 of
+    // them at 96 x 128 stay below 2^31: the true bound of a tile is 4 x 2^31 / (96 x 128) = 699 050 individuals. The floor below keeps a
+    // tile at 131 072, well inside it)
     ns = std::max(ns, (int)(((int64_t)nst * RS + 131071) / 131072));
     const int lds = mfma ? q2m_lds(q2m_ct, q2m_g) : q2_lds(cpl, RS);
     if (mfma && (q2m_g == 0 || q2m_g == 3) && !k.dotq2_tiles_set) {
