@@ -11,6 +11,7 @@ Public surface mirrors the reference's for this path (YinLiLin/hibayes v3.1.0):
     grm_inverse() / spd_inverse()  src/rm.cpp:39-42, src/solver.cpp:159-259 (make_grm(inverse = TRUE): solve(), Cholesky on the device, LU on the host)
     impute_device()  R/ssbayes.r:295-307 (the single-step model's imputation as a batched conjugate-gradient solve on the device)
     window_pve()  README item (8), after R/bayes.r:303-308 (the variance explained by windows of markers, per record: PVE and variance-based WPPA)
+    ld_window_pve()  README item (8), after R/sbayes.r:231-234 (the same from the LD matrix of the summary-level model; sbrm(pve=True))
 All compute runs in libhibayes_gpu.so (hand-written gfx950 HIP kernels behind include/hibayes_gpu.h).
 """
 from ._lib import HibayesError, lib, LIB_PATH
@@ -26,8 +27,8 @@ from .ssbayes import ssbrm, ssbrm_prepare, make_ped, make_Ainv
 from .impute import impute_device
 from .plink import read_plink, read_table, decode_bed, attach_bigmatrix, read_bigmatrix, write_bigmatrix
 from .windows import cutwind_by_bp, cutwind_by_num
-from .pve import window_pve
+from .pve import ld_window_pve, window_pve
 
 __all__ = ["Bayes", "ibrm", "read_plink", "read_table", "decode_bed", "attach_bigmatrix", "read_bigmatrix", "write_bigmatrix", "Context", "cutwind_by_bp",
-           "cutwind_by_num", "SBayesD", "SBayesS", "sbrm", "conjgt_den", "conjgt_spa", "sbrm_cg", "ldmat", "LDMatrix", "make_grm", "eigh", "grm_inverse", "spd_inverse", "solver_lu", "chol_factor", "ssbrm", "ssbrm_prepare", "make_ped", "make_Ainv", "impute_device", "window_pve", "HibayesError", "lib", "LIB_PATH"]
+           "cutwind_by_num", "SBayesD", "SBayesS", "sbrm", "conjgt_den", "conjgt_spa", "sbrm_cg", "ldmat", "LDMatrix", "make_grm", "eigh", "grm_inverse", "spd_inverse", "solver_lu", "chol_factor", "ssbrm", "ssbrm_prepare", "make_ped", "make_Ainv", "impute_device", "window_pve", "ld_window_pve", "HibayesError", "lib", "LIB_PATH"]
 __version__ = "0.1.0"

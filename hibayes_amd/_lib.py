@@ -286,6 +286,8 @@ SYMBOLS = [
     "hb_chol_factor", "hb_chol_invert_factor", "hb_spd_inverse", "hb_chol_plan",
     # window PVE: README item (8), after the GEBV step of R/bayes.r:303-308 (hb_pve.hip)
     "hb_ctx_window_var", "hb_pve_plan",
+    # the same on the LD matrix for the summary-level model, after R/sbayes.r:231-234 (hb_ldquad.hip)
+    "hb_ldm_window_var", "hb_ldm_diagonal",
 ]
 
 
@@ -450,6 +452,8 @@ def lib():
     L.hb_chol_plan.argtypes = [i32, i32] + [vp] * 8
     L.hb_ctx_window_var.argtypes = [vp, vp, i64, i32, vp, i32, vp, i64, vp]
     L.hb_pve_plan.argtypes = [vp, i64, i32, i32, vp, i32, vp, i32, i64, i32] + [vp] * 7
+    L.hb_ldm_window_var.argtypes = [vp, vp, i64, i32, i32, vp, i32, vp, i64, vp]
+    L.hb_ldm_diagonal.argtypes = [vp, vp]
     _lib = L
     return L
 

@@ -63,6 +63,38 @@ class LDMatrix:
         check(self.L.hb_ldm_download_csc(self._handle(), indptr.ctypes.data, indices.ctypes.data, data.ctypes.data))
         return sp.csc_matrix((data, indices, indptr), shape=self.shape)
 
+    def window_var(self, A, windindx, nw=None):
+        """(var, total): var[w - 1, r] = alpha_w,r' V_ww alpha_w,r over the stored entries of the matrix for every window id w of windindx (m ids
+        in 1 .. nw) and every record r (column of A, m x R), total[r] = alpha_r' V alpha_r. On the device from the copy the handle's kind reads
+        (hb_ldm_window_var); hibayes_amd.ld_window_pve() makes PVE and WPPA of them. Nothing is clamped: a thresholded matrix is indefinite and
+        a form may be negative. nw: the number of windows where it is more than the largest id used (the rows past it, like every window
+        without an effect, are 0.0)."""
+        m = self.shape[0]
+        A = np.asfortranarray(A, dtype=np.float64)
+        if A.ndim == 1:
+            A = A.reshape(-1, 1, order="F")
+        if A.ndim != 2:
+            raise ValueError("A must be (m,) or (m, R)")
+        wi = np.asarray(windindx)
+        if wi.shape != (m,) or wi.dtype.kind not in "iu":
+            raise ValueError("windindx must hold one integer window id per marker")
+        if wi.min() < 1:
+            raise ValueError("windindx must hold window ids in 1 .. nw")
+        nw = int(wi.max()) if nw is None else int(nw)
+        if nw < wi.max():
+            raise ValueError("windindx must hold window ids in 1 .. nw")
+        wi = np.ascontiguousarray(wi, dtype=np.uint32)
+        var, total = np.zeros((nw, A.shape[1]), order="F"), np.zeros(A.shape[1])
+        check(self.L.hb_ldm_window_var(self._handle(), A.ctypes.data, max(A.shape[0], 1), A.shape[0], A.shape[1], wi.ctypes.data, nw, var.ctypes.data, nw,
+                                       total.ctypes.data))
+        return var, total
+
+    def diagonal(self):
+        """The m diagonal entries, from the copy the handle's kind reads (hb_ldm_diagonal); 0.0 where a sparse matrix stores none."""
+        out = np.zeros(self.shape[0])
+        check(self.L.hb_ldm_diagonal(self._handle(), out.ctypes.data))
+        return out
+
     def close(self):
         if self.h:
             self.L.hb_ldm_destroy(self.h)

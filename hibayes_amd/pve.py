@@ -3,7 +3,11 @@ list of what hibayes estimates. The reference leaves it to the R session after i
 apply(geno, 2, var) * alpha^2 / var(pheno): right for one marker, wrong for a window of markers in LD, where the quantity is var(X_w alpha_w).
 Here the window variances of every stored record come from the resident genotypes in one pass (Context.window_var, hb_pve.hip), and with
 them the posterior mean PVE of a window and the variance-based WPPA of Fernando et al.: the share of records in which the window explains more
-than a threshold of the genetic variance."""
+than a threshold of the genetic variance.
+
+ld_window_pve(): the same for the summary-level model, where there are no genotypes. sbrm() (R/sbayes.r:231-234) returns the windows' WPPA and
+stops there; the variance a window explains is the quadratic form alpha_w' V_ww alpha_w on the LD matrix the sampler swept, taken from the
+handle's device copy in one pass per batch of records (LDMatrix.window_var, hb_ldquad.hip)."""
 import numpy as np
 
 from .engine import Context
@@ -119,4 +123,61 @@ def window_pve(M, alpha, windindx=None, *, vary=None, threshold=None, device=0):
     finally:
         if own:
             ctx.close()
+    return pve_summary(var, total, vary, threshold)
+
+
+def sbayes_vary(sumstat, diag):
+    """var(y) as SBayesD() and SBayesS() take it from the summary statistics (src/SBayesD.cpp:93-115): sumstat m x 4 (MAF, BETA, SE, NMISS; NaN =
+    NA), diag the LD matrix's diagonal. n = the mean of the finite NMISS cut to an integer (:33-34), xpx_k = diag_k n, and over the markers with
+    BETA, SE and NMISS all present yy_k = xpx_k (BETA^2 + (NMISS - 2) SE^2); vary = (sum yy_k / their count) / (n - 1)."""
+    ss = np.asarray(sumstat, dtype=np.float64)
+    if ss.ndim != 2 or ss.shape[1] != 4:
+        raise ValueError("sumstat must have the four columns MAF, BETA, SE, NMISS")
+    d = np.asarray(diag, dtype=np.float64)
+    if d.shape != (ss.shape[0],):
+        raise ValueError("diag must hold one entry per marker")
+    nm = ss[:, 3]
+    if not np.isfinite(nm).any():
+        raise ValueError("Lack of NMISS.")
+    n = int(nm[np.isfinite(nm)].mean())
+    est = ~(np.isnan(ss[:, 1]) | np.isnan(ss[:, 2]) | np.isnan(ss[:, 3]))
+    if not est.any():
+        raise ValueError("Lack of SE.")
+    yyi = (d[est] * n) * (ss[est, 1] * ss[est, 1] + (ss[est, 3] - 2.0) * ss[est, 2] * ss[est, 2])
+    return float(yyi.sum() / int(est.sum()) / (n - 1))
+
+
+def ld_window_pve(ldm, alpha, windindx=None, *, vary=None, threshold=None, device=0):
+    """ldm: an LDMatrix (ldmat(..., keep_on_device=True), LDMatrix.from_scipy), a scipy sparse matrix, or a square ndarray — the last two are
+    handed over as CSC (LDMatrix.from_scipy; an ndarray with its exact zeros dropped), so they must equal their transpose; alpha, windindx,
+    vary and threshold as in window_pve(). Returns window_pve()'s dict, with var[w, r] = alpha_w,r' V_ww alpha_w,r and
+    total[r] = alpha_r' V alpha_r over the stored entries. windindx=None: every marker its own window, var = diag(V) alpha^2 as the closed
+    form, and only the total comes from the pass. A thresholded LD matrix is indefinite: a negative var or total is a finding and is
+    returned as computed."""
+    from .ldm import LDMatrix
+    own = None
+    if not isinstance(ldm, LDMatrix):
+        import scipy.sparse as sp
+        if not sp.issparse(ldm):
+            V = np.asarray(ldm, dtype=np.float64)
+            if V.ndim != 2 or V.shape[0] != V.shape[1]:
+                raise ValueError("ldm must be an LDMatrix, a scipy sparse matrix or a square array")
+            ldm = sp.csc_matrix(V)
+        elif ldm.ndim != 2 or ldm.shape[0] != ldm.shape[1]:
+            raise ValueError("ldm must be an LDMatrix, a scipy sparse matrix or a square array")
+    m = ldm.shape[0]
+    a, w, nw = check_pve_args(m, alpha, windindx, vary, threshold)
+    if not isinstance(ldm, LDMatrix):
+        ldm = own = LDMatrix.from_scipy(ldm, device=device)
+    try:
+        if w is None:
+            var = ldm.diagonal()[:, None] * a * a
+            # (the total alone is wanted: the pass with one window, whose form — the total once more, added per column — is dropped. A total's bits
+            # do not depend on the window map, so this is the total every other map gives.)
+            total = ldm.window_var(a, np.ones(m, dtype=np.uint32))[1]
+        else:
+            var, total = ldm.window_var(a, w)
+    finally:
+        if own is not None:
+            own.close()
     return pve_summary(var, total, vary, threshold)

@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import LOG_FN, SBayesArgs, SBayesOut, check, lib
+from ._lib import LOG_FN, HibayesError, SBayesArgs, SBayesOut, check, lib
 from .ldm import LDMatrix
 
 
@@ -114,14 +114,21 @@ def _run(sparse, sumstat, ldm, model, Pi, niter, nburn, thin, fold, windindx, vg
 
 def sbrm(sumstat, ldm, method="BayesB", map=None, Pi=None, fold=None, niter=None, nburn=None, thin=5, windsize=None, windnum=None,
          windindx=None, vg=None, dfvg=None, s2vg=None, ve=None, dfve=None, s2ve=None, printfreq=100, seed=666666, threads=4, verbose=True,
-         sparse_ld=False, **kw):
+         sparse_ld=False, pve=False, **kw):
     """sbrm() of the reference (R/sbayes.r:101-239): the ldm type check (:126-132), GWAS windows cut from `map` by windsize /
     windnum (:135-187; res["gwas"] then carries WIND / CHR / NUM / START / END / WPPA like the reference's data frame, :231-234),
     defaults (:189-203), the column selection sumstat[, c(4, 5, 6, 8)] of the 8-column COJO table (:207), then SBayesD() — or, with
     sparse_ld=True and a scipy sparse `ldm` or an LDMatrix, SBayesS(), as :213 does for a dgCMatrix: .bed -> ldmat(chisq=...,
     keep_on_device=True) -> sbrm(sparse_ld=True) with no dense matrix on either side. Without sparse_ld a scipy sparse `ldm` is
     refused, and an LDMatrix runs through SBayesD() as the dense matrix. method = "CG" is refused here: its arm of sbrm() is
-    sbrm_cg() (hibayes_amd/cg.py)."""
+    sbrm_cg() (hibayes_amd/cg.py).
+    `pve`: also return res["pve"] = ld_window_pve(...) — the variance explained by every window (windindx, or the windows cut by windsize /
+    windnum; without either, by every marker) in every stored record of the effects (without store_alpha: in their posterior mean), as the
+    quadratic form on the LD matrix the sampler ran on, relative to the sampler's own var(y) (src/SBayesD.cpp:93-115); see
+    hibayes_amd.ld_window_pve. Where the windows were cut here, the table WIND / CHR / NUM / START / END comes with it. A host matrix is
+    handed to the library once, as a handle, before the fit — it must equal its transpose in value bits, and one that does not is refused
+    before anything is fitted. A sparse one is swept from that same handle; a dense one is swept as it was passed, and the handle holds the
+    same values as CSC (12 B per stored entry in pinned memory: pass an LDMatrix from ldmat(keep_on_device=True) to avoid the copy)."""
     is_sparse = False
     try:
         import scipy.sparse as sp
@@ -177,8 +184,31 @@ def sbrm(sumstat, ldm, method="BayesB", map=None, Pi=None, fold=None, niter=None
     ss = np.asarray(sumstat, dtype=np.float64)
     if ss.ndim == 2 and ss.shape[1] >= 8:      # the COJO table (:207); a 4-column matrix is taken as MAF, BETA, SE, NMISS already
         ss = ss[:, [3, 4, 5, 7]]
-    res = (SBayesS if sparse_ld else SBayesD)(ss, ldm, method, Pi, niter=niter, nburn=nburn, thin=thin, fold=fold, windindx=windindx, vg=vg, dfvg=dfvg, s2vg=s2vg,
-                  ve=ve, dfve=dfve, s2ve=s2ve, outfreq=printfreq, threads=threads, verbose=verbose, seed=seed, **kw)
+    own = None
+    try:
+        pve_ld = ldm
+        if pve and not isinstance(ldm, LDMatrix):
+            # a host matrix becomes a handle once, BEFORE the fit: hb_ldm_from_csc refuses one that does not equal its transpose in value bits, and
+            # that must not cost a finished chain. A sparse matrix is then swept from this handle (SBayesS() would make the same one for itself);
+            # a dense one is swept by SBayesD() as it was passed and the handle, its CSC with the exact zeros dropped, serves the pass alone.
+            import scipy.sparse as sp
+            try:
+                pve_ld = own = LDMatrix.from_scipy(ldm if is_sparse else sp.csc_matrix(np.asarray(ldm, dtype=np.float64)), device=kw.get("device", 0))
+            except HibayesError as e:
+                raise HibayesError(e.status, "sbrm(pve=True): %s (the variance explained is a quadratic form on the matrix; nothing was fitted)" % e) from None
+            if sparse_ld:
+                ldm = pve_ld
+        res = (SBayesS if sparse_ld else SBayesD)(ss, ldm, method, Pi, niter=niter, nburn=nburn, thin=thin, fold=fold, windindx=windindx, vg=vg, dfvg=dfvg, s2vg=s2vg,
+                      ve=ve, dfve=dfve, s2ve=s2ve, outfreq=printfreq, threads=threads, verbose=verbose, seed=seed, **kw)
+        if pve:  # README item (8), on the matrix the sampler ran on; relative to the sampler's own var(y)
+            from .pve import ld_window_pve, sbayes_vary
+            samples = res["MCMCsamples"].get("alpha")
+            res["pve"] = ld_window_pve(pve_ld, res["alpha"] if samples is None else samples, windindx, vary=sbayes_vary(ss, pve_ld.diagonal()))
+            if windinfo is not None:
+                res["pve"].update(windinfo)
+    finally:
+        if own is not None:
+            own.close()
     if windinfo is not None:
         res["gwas"] = dict(windinfo, WPPA=res["gwas"])
     res["call"] = "b ~ nD^{-1}V alpha + e"

@@ -356,7 +356,7 @@ def ssbrm_prepare(formula, data=None, M=None, M_id=None, pedigree=None, maf=0.01
 def ssbrm(formula, data=None, M=None, M_id=None, pedigree=None, method="BayesCpi", map=None, Pi=None, fold=None, niter=None, nburn=None, thin=5,
           windsize=None, windnum=None, maf=0.01, dfvr=None, s2vr=None, vg=None, dfvg=None, s2vg=None, ve=None, dfve=None, s2ve=None,
           printfreq=100, seed=666666, threads=4, verbose=True, *, windindx=None, device=0, panel=0, store_alpha=True, store_epsilon=True,
-          gebv_samples=False, one_parent="reference", chunk=512, impute="host", impute_tol=1e-12):
+          gebv_samples=False, one_parent="reference", chunk=512, impute="host", impute_tol=1e-12, pve=False):
     """Mirror of ssbrm() (reference R/ssbayes.r:115-351), with ibrm()'s conventions for `formula`, `data` and the keyword extras: the
     single-step model for a population of which only a part is genotyped. `pedigree`: three columns (id, sire, dam). The non-genotyped
     individuals' genotypes are imputed from the pedigree in the set-up — on the host through a sparse factor, or with `impute="device"` by a
@@ -364,7 +364,10 @@ def ssbrm(formula, data=None, M=None, M_id=None, pedigree=None, method="BayesCpi
     block — J, the Gibbs pass over the non-genotyped individuals, the variance of epsilon — on the device.
     Returns Bayes()'s fields plus Veps, J, epsilon {"id", "epsilon"}, g {"id", "gebv"} over the genotyped, then the non-genotyped
     individuals (the linear form of :325 applied to the posterior means; `gebv_samples=True` also returns the full MCMCsamples["g"]) and
-    e {"id", "e"}. `one_parent`: make_Ainv()'s — the default reproduces the reference's A^-1."""
+    e {"id", "e"}. `one_parent`: make_Ainv()'s — the default reproduces the reference's A^-1.
+    `pve`: also return res["pve"] = window_pve(...) — the variance explained by every window (or, without windows, by every marker) in every
+    stored record of the effects (without store_alpha: in their posterior mean) over all individuals, genotyped and imputed, relative to
+    var(y) of the fit; see hibayes_amd.window_pve. Where the windows were cut here, their table comes with it."""
     if method not in SS_METHODS:
         raise ValueError("'arg' should be one of " + ", ".join(SS_METHODS))
     windinfo = None
@@ -434,6 +437,12 @@ def ssbrm(formula, data=None, M=None, M_id=None, pedigree=None, method="BayesCpi
                 gs = gs + np.outer(Jall, mc["J"].ravel())
                 gs[ng:] += mc["epsilon"]
             mc["g"] = gs
+        if pve:  # README item (8), on the context that holds all individuals; relative to var(y) of the fit
+            from .pve import window_pve
+            samples = mc.get("alpha") if store_alpha else None
+            res["pve"] = window_pve(cg, res["alpha"] if samples is None else samples, windindx, vary=float(np.var(pr["y"], ddof=1)))
+            if windinfo is not None:
+                res["pve"].update(windinfo)
     if has_eps:
         res["epsilon"] = {"id": list(pr["Mn_id"]), "epsilon": res["epsilon"]}
     res["u_last"] = res["g"]

@@ -720,6 +720,24 @@ int hb_ctx_window_var(hb_ctx *c, const double *A, int64_t ldA, int32_t R, const 
 int hb_pve_plan(const double *A, int64_t ldA, int32_t m, int32_t nr, const uint32_t *windindx, int32_t nw, const double *s1, int32_t n, int64_t ld,
                 int32_t num_cus, int32_t *counts, int32_t *idx, double *val, int32_t *segs, double *shift, double *total_shift, int32_t *chunks);
 
+/* The same item (8) for the summary-level model, where there are no genotypes: sbrm() (R/sbayes.r:231-234) returns the windows' WPPA and leaves
+ * the variance they explain to the R session. The quantity is the quadratic form on the LD matrix of the handle, from the copy its kind reads —
+ * HB_LDM_KIND_DENSE the dense device copy, every other kind the device CSC (nothing m x m is allocated for those) — (hb_ldquad.hip). For every
+ * record r (column of A, rows x R with rows == m, leading dimension ldA, on the host, finite) and every window w (windindx: m ids in 1 .. nw,
+ * a window's markers need not be contiguous):
+ *     var_out[r * ldv + (w - 1)] = sum_{j in w} alpha_jr t_jr,  t_jr = sum_{i in w, (i, j) stored} V_ij alpha_ir,
+ *     total_out[r]               = sum_j alpha_jr T_jr,         T_jr = sum_{i, (i, j) stored} V_ij alpha_ir,
+ * eight records per pass over the columns with a non-zero effect in any of them. Every term is selected, (alpha != 0 ? V alpha : 0.0), so a
+ * NaN or Inf entry (the sparse kinds keep NaN for monomorphic markers) reaches a result only where both effects are non-zero. Nothing is
+ * clamped: a thresholded matrix is indefinite and a negative form is stored as computed. A window without a non-zero effect in a record's
+ * batch is not visited and gets 0.0 exactly. Deterministic, no floating-point atomics; a (window, record) value depends on that window's
+ * effects of that record alone: not on the other records, windows or ids. HB_ERR_INVALID: a null handle, rows != m, R < 1, a non-finite
+ * effect, a window id outside 1 .. nw. */
+int hb_ldm_window_var(hb_ldm *ldm, const double *A, int64_t ldA, int32_t rows, int32_t R, const uint32_t *windindx, int32_t nw, double *var_out,
+                      int64_t ldv, double *total_out);
+/* out[j] = V_jj for the m markers, from the copy the handle's kind reads (0.0 where a sparse matrix stores no diagonal entry) */
+int hb_ldm_diagonal(hb_ldm *ldm, double *out);
+
 /* helpers for the host blocks that share yadj (reference src/Bayes.cpp:479-516) */
 int hb_ctx_residual_sums(hb_ctx *c, double *sum_r, double *sum_r2);
 int hb_ctx_residual_shift(hb_ctx *c, double a);                       /* yadj += a        */
