@@ -372,7 +372,7 @@ int hb_ctx_upload_genotype_f64(hb_ctx *c, const double *X, int64_t ld, int32_t c
     HB_TRY(tmp.zeroed(&dbad, 1, c->stream));
     for (int c0 = 0; c0 < ncols && rc == HB_OK; c0 += chunk) {
         const int nc = std::min(chunk, ncols - c0);
-        hipError_t e = hipMemcpy2DAsync(stage, (size_t)c->n * sizeof(double), X + (int64_t)(col0 + c0) * ld,
+        hipError_t e = hipMemcpy2DAsync(stage, (size_t)c->n * sizeof(double), X + (int64_t)c0 * ld, // (X is the first uploaded column)
                                         (size_t)ld * sizeof(double), (size_t)c->n * sizeof(double), (size_t)nc,
                                         hipMemcpyHostToDevice, c->stream);
         if (e != hipSuccess) { rc = hb_fail(HB_ERR_HIP, hipGetErrorString(e)); break; }

@@ -605,7 +605,8 @@ void hb_ctx_destroy(hb_ctx *c);
 int hb_ctx_panel(const hb_ctx *c);
 int64_t hb_ctx_ld(const hb_ctx *c);     /* device leading dimension of X in bytes */
 
-/* Genotypes -> device int8, column-major. ncols columns starting at col0. */
+/* Genotypes -> device int8, column-major. ncols columns starting at col0. For both upload calls X is the address of the
+ * first uploaded column (the source of device column col0), with ld >= n elements from one column to the next. */
 int hb_ctx_upload_genotype_i8(hb_ctx *c, const int8_t *X, int64_t ld, int32_t col0, int32_t ncols);
 /* doubles are checked for integrality and range, never rounded silently */
 int hb_ctx_upload_genotype_f64(hb_ctx *c, const double *X, int64_t ld, int32_t col0, int32_t ncols);
